@@ -17,6 +17,12 @@ N=1 digest), the ranks exchange their (key,count) buckets with one all-to-all ov
 `python bench.py --gpus N` with no WORLD_SIZE in the environment starts the N ranks itself (fresh
 child processes through torch.distributed.run, from a parent that has made no GPU call) and relays
 rank 0's JSON line.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the --steps steps and prints the line (reads/s, ms_per_step, the
+per-stage times and the roofline figures of the timed steps).  `--full` adds the measurements that cost
+runs of their own -- the FASTA ingest rate, the steps with two batches in flight (`overlap`), the CPU
+baselines -- and the per-kernel tables and partitions.  `--dump-outputs DIR` writes the final transcripts of the last timed step as .npy arrays
+(dump_outputs below), so that two builds can be compared output for output on the same seeded batch.
 """
 import argparse, json, os, sys, time
 
@@ -142,6 +148,35 @@ def _final_sha(final):
     for sq in sorted(final.values()):
         h.update(sq.encode() + b"\n")
     return h.hexdigest()[:16]
+
+
+DUMP_BYTES = 64_000_000        # --dump-outputs: every array of the dump together, .npy headers included
+
+
+def dump_outputs(final, out_dir, seed=20240501):
+    """--dump-outputs: the final transcripts ({name: sequence}, file order) of the last timed step as .npy arrays in out_dir:
+      transcript_lengths.npy       float64 [n]  bases of every transcript
+      transcript_name_lengths.npy  float64 [n]  characters of every name
+      sample_index.npy             float64 [m]  the transcripts written out in full, ascending: all n of them, or -- where their
+                                                bytes would pass DUMP_BYTES -- a fixed, seeded sample
+      sample_bases.npy             float32      their sequences one after the other, A C G T = 0 1 2 3 (any other letter 4)
+      sample_names.npy             float32      their names one after the other, as byte values
+    The batch is seeded: the same arguments give the same arrays on every run of a build."""
+    items = list(final.items())
+    n = len(items)
+    lens = np.array([len(s) for _, s in items], dtype=np.float64)
+    name_lens = np.array([len(nm) for nm, _ in items], dtype=np.float64)
+    room = (DUMP_BYTES - 4096 - 24 * n) // 4                  # float32 values left beside the [n] arrays (the index is at most [n] too)
+    order = np.random.default_rng(seed).permutation(n)
+    pick = np.sort(order[:int((np.cumsum((lens + name_lens)[order]) <= room).sum())]).tolist()
+    code = np.full(256, 4, dtype=np.float32)
+    code[np.frombuffer(b"ACGT", np.uint8)] = np.arange(4)
+    arrays = {"transcript_lengths": lens, "transcript_name_lengths": name_lens, "sample_index": np.array(pick, dtype=np.float64),
+              "sample_bases": code[np.frombuffer("".join(items[i][1] for i in pick).encode(), np.uint8)],
+              "sample_names": np.frombuffer("".join(items[i][0] for i in pick).encode(), np.uint8).astype(np.float32)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def ingest_rate(ctx, r1, r2, n_pairs):
@@ -519,9 +554,14 @@ def build_parser():
     ap.add_argument("--overlap-steps", type=int, default=-1,
                     help="one GPU: after the timed steps, that many more with two batches in flight (the host-bound half of a step on a second "
                          "context and thread beside the next batch's GPU-bound half); reported as `overlap`, never as `value` (default: 6 at "
-                         "the default workload, 0 = off)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                         "the default workload with --full, else 0; 0 = off)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--force-distributed", action="store_true", help="run the multi-GPU code path even with one rank")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the measurements beside the headline: FASTA ingest rate and `value_with_ingest`, "
+                         "two batches in flight (`overlap`, see --overlap-steps) and the CPU baselines (one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the final transcripts of the last timed step to DIR as .npy arrays (float32 / float64, at most 64 MB)")
     return ap
 
 
@@ -577,7 +617,10 @@ def main():
     sys.stdout.flush()
     json_fd = os.dup(1)
     os.dup2(2, 1)
-    args = build_parser().parse_args()
+    ap = build_parser()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config == "0":
         args.config = ""
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -772,6 +815,8 @@ def main():
                     sys.stderr.write("  step %d: no stage checksums (run with SHN_EXT_DIGEST=1 to have shn_ext_digests of every step)\n" % i)
             sys.stderr.flush()
             os._exit(3)
+        if args.dump_outputs:
+            dump_outputs(last.res["final"] if use_dist else last.R.final, args.dump_outputs)
     tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if (dist and dist.get_backend() == "gloo") else dev)
     if dist:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -874,19 +919,6 @@ def main():
         dom = max(kt, key=lambda k: kt[k][0])
         bdom = max((k for k in kt if k in per_read), key=lambda k: kt[k][0])
         r_dom, r_bw = roof(dom), roof(bdom)
-        # every timed kernel against the HBM roof (algorithmic bytes of DESIGN.md section 3 / SURVEY 8d, time from the HIP-event timers)
-        kernel_table = []
-        for name in sorted(kt, key=lambda k: -kt[k][0]):
-            q = roof(name)
-            kernel_table.append({"kernel": q["kernel"], "timer": name, "ms_per_step": kt[name][0] / args.steps, "launches_per_step": q["launches_per_step"],
-                                 "algorithmic_GB_per_step": per_step_bytes[name] / 1e9, "algorithmic_bytes_per_read": per_step_bytes[name] / max(1, n_reads),
-                                 "achieved_GBs": q["achieved"], "frac_of_hbm_peak": q["frac"], "traffic_bytes_per_launch_pmc": q["traffic"]})
-            if q["traffic"]:
-                # how busy the memory system is with this kernel, its waste included: PMC traffic per launch / the launch's time, against
-                # the 8 TB/s of streams and -- as 128-byte requests -- against the 48.4 G/s of independent random loads (a gather's roof)
-                tg = q["traffic"] / (q["avg_launch_ms"] * 1e-3) / 1e9
-                kernel_table[-1].update({"traffic_GBs_pmc": tg, "traffic_frac_of_hbm_peak": tg / HBM_PEAK_GBS,
-                                         "requests_frac_of_random_access_roof": tg / 128.0 / 48.4})
         # the whole path against the HBM roof on the survey's byte model -- 2.5 KB per 100 bp read (1.23 KB of it counting)
         BYTES_PER_READ_8D = 2500.0
         e2e_gbs = job_reads * args.steps / dt * BYTES_PER_READ_8D / 1e9
@@ -955,7 +987,6 @@ def main():
                        "extension_iterations": ext["iterations"], "extension_walks": ext["n_walks"],
                        "extension_walk_steps": steps_all, "extension_dense_rounds": ext.get("dense_rounds"),
                        "extension_walks_settled_by_chain": ext.get("settled_walks"),
-                       "partitions": (len(last.res["partitions"]) if use_dist else {k: [v["n_reads_routed"], v["n_k1mers"]] for k, v in last.R.partitions.items()}),
                        "windows_per_step": total, "distinct_k1mers": distinct},
             "roofline": r_dom,
             "roofline_bandwidth_kernel": r_bw,
@@ -966,10 +997,26 @@ def main():
                                       "achieved": (25.0 + 16.0 * W) * n_reads / (timers["count.total"][0] / args.steps * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
                                       "unit": "GB/s", "frac": (25.0 + 16.0 * W) * n_reads / (timers["count.total"][0] / args.steps * 1e-3) / 1e9 / HBM_PEAK_GBS,
                                       "ms_per_step": timers["count.total"][0] / args.steps} if "count.total" in timers else None),
-            "kernel_table": kernel_table,
-            "kernel_ms_per_step": {k: v[0] / args.steps for k, v in sorted(timers.items())},
-            "kernel_launches_per_step": {k: v[1] / args.steps for k, v in sorted(timers.items())},
         }
+        if args.full:
+            # every timed kernel against the HBM roof (algorithmic bytes of DESIGN.md section 3 / SURVEY 8d, time from the HIP-event timers)
+            # and the partitions of the last step: three quarters of the line at configs[2], kept out of the plain line
+            kernel_table = []
+            for name in sorted(kt, key=lambda k: -kt[k][0]):
+                q = roof(name)
+                kernel_table.append({"kernel": q["kernel"], "timer": name, "ms_per_step": kt[name][0] / args.steps, "launches_per_step": q["launches_per_step"],
+                                     "algorithmic_GB_per_step": per_step_bytes[name] / 1e9, "algorithmic_bytes_per_read": per_step_bytes[name] / max(1, n_reads),
+                                     "achieved_GBs": q["achieved"], "frac_of_hbm_peak": q["frac"], "traffic_bytes_per_launch_pmc": q["traffic"]})
+                if q["traffic"]:
+                    # how busy the memory system is with this kernel, its waste included: PMC traffic per launch / the launch's time, against
+                    # the 8 TB/s of streams and -- as 128-byte requests -- against the 48.4 G/s of independent random loads (a gather's roof)
+                    tg = q["traffic"] / (q["avg_launch_ms"] * 1e-3) / 1e9
+                    kernel_table[-1].update({"traffic_GBs_pmc": tg, "traffic_frac_of_hbm_peak": tg / HBM_PEAK_GBS,
+                                             "requests_frac_of_random_access_roof": tg / 128.0 / 48.4})
+            out["config"]["partitions"] = (len(last.res["partitions"]) if use_dist else {k: [v["n_reads_routed"], v["n_k1mers"]] for k, v in last.R.partitions.items()})
+            out.update({"kernel_table": kernel_table,
+                        "kernel_ms_per_step": {k: v[0] / args.steps for k, v in sorted(timers.items())},
+                        "kernel_launches_per_step": {k: v[1] / args.steps for k, v in sorted(timers.items())}})
         # the pinned digest of the configuration (the one the full-size GPU tests check): a run whose every step agrees with itself
         # but not with the pin fails too
         try:
@@ -983,16 +1030,16 @@ def main():
                              % (out["config"]["transcripts_sha256_16"], args.config, pin))
             sys.stderr.flush()
             os._exit(4)
-        if world == 1 and not use_dist:
+        if args.full and world == 1 and not use_dist:
             # ingest-inclusive rate: the resident step plus reading the batch from FASTA text at the measured ingest rate (no overlap
             # between ingest and the step assumed)
             ing = ingest_rate(ctx, r1, r2, min(len(r1), 5_000_000))
             out["ingest"] = ing
             out["value_with_ingest"] = 1.0 / (1.0 / out["value"] + 1.0 / ing["reads_per_s"])
-        n_ov = args.overlap_steps if args.overlap_steps >= 0 else (6 if (is_config and args.config == "2") else 0)
+        n_ov = args.overlap_steps if args.overlap_steps >= 0 else (6 if (args.full and is_config and args.config == "2") else 0)
         if world == 1 and not use_dist and n_ov > 0:
             out["overlap"] = overlapped_steps(ctx, sets, store, args.K, n_ov, out["config"]["transcripts_sha256_16"], n_reads)
-        if not args.no_cpu_baseline and world == 1:          # the CPU baseline is timed on rank 0 of the N=1 run only
+        if args.full and not args.no_cpu_baseline and world == 1:          # the CPU baseline is timed on rank 0 of the N=1 run only
             # bounded sample: ~10-15 s of one core through the whole path (at configs[2] a read costs the pure-Python path ~5x more
             # than at configs[1]: nearly every k1-mer of a 25k-read sample is new), + ~5 s for the counting stage alone / threaded
             # ~30 s of host work: 1 M reads (500,000 pairs) through the whole path, native where a native host form exists.

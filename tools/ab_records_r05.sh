@@ -3,7 +3,7 @@
 mkdir -p gpurun_out/ab
 timeout 900 python -m pytest tests/test_e2e_gpu.py -x -q -m gpu -k "minimizer_bucketed" > gpurun_out/ab/e2e.txt 2>&1; tail -2 gpurun_out/ab/e2e.txt
 timeout 900 python -m pytest tests/test_midsize_gpu.py -x -q -m gpu > gpurun_out/ab/mid.txt 2>&1; tail -2 gpurun_out/ab/mid.txt
-B="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --overlap-steps 0"
+B="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --overlap-steps 0 --full"
 $B > gpurun_out/ab/lds2.json 2> gpurun_out/ab/lds2.err
 SHN_REC_LDS=0 $B > gpurun_out/ab/dict.json 2> gpurun_out/ab/dict.err
 SHN_HIP_LIB=$PWD/ab/libshannon_hip_fly4.so $B > gpurun_out/ab/lds4.json 2> gpurun_out/ab/lds4.err

@@ -6,7 +6,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"; export TMPDIR=/tmp
 CFG=${1:-2}
 O=$PWD/gpurun_out/r03p; W=/tmp/r03p_$CFG; mkdir -p $O $W
-if [ -z "$SKIP_BENCH" ]; then python3 bench.py --config $CFG --steps 20 --warmup 5 > $O/bench_config$CFG.json 2> $O/bench_config$CFG.err; fi
+if [ -z "$SKIP_BENCH" ]; then python3 bench.py --full --config $CFG --steps 20 --warmup 5 > $O/bench_config$CFG.json 2> $O/bench_config$CFG.err; fi
 # (the profiled passes run the graph stage on one thread and one stream: rocprofv3 aborts when threads it has not seen create streams)
 export SHN_GRAPH_THREADS=1 SHN_GRAPH_FORK=0
 rocprofv3 --kernel-trace --stats --output-format csv -d $W/kt -o kt -- python3 bench.py --config $CFG --no-cpu-baseline --overlap-steps 0 --steps 2 --warmup 1 > $O/kt_$CFG.log 2>&1

@@ -55,7 +55,7 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
 }
 
 constexpr uint32_t EMPTY = 0xFFFFFFFFu;
-constexpr int MAXW = 16;                                  // reads of up to 512 bases
+constexpr int MAXW = 16;                                  // reads of up to 512 bases in registers (longer: dd_insert_wide)
 
 // MW: compile-time bound of the words per read (the words of a slot stay in registers: a run-time bound put them in scratch)
 template <int MW>
@@ -82,6 +82,30 @@ __global__ void dd_insert(SlotSrc S, uint64_t nh, uint32_t* __restrict__ tab, ui
       bool same = true;
 #pragma unroll
       for (uint32_t t = 0; t < (uint32_t)MW; t++) if (t < S.wpr && same) same = slot_word(S, osrc, orc, t) == w[t];
+      if (same) { atomicMin(&tab[s], (uint32_t)j); slot_of[j] = (uint32_t)s; break; }
+      s = (s + 1) & mask;
+    }
+  }
+}
+
+// reads of more than MAXW words: the same insert with the words read again for every comparison instead of kept in registers
+__global__ void dd_insert_wide(SlotSrc S, uint64_t nh, uint32_t* __restrict__ tab, uint64_t mask, uint32_t* __restrict__ slot_of) {
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nh; j += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t* src; bool rc;
+    slot_origin(S, j, src, rc);
+    uint64_t h = 0x9E3779B97F4A7C15ULL;
+    for (uint32_t t = 0; t < S.wpr; t++) h = mix64(h ^ slot_word(S, src, rc, t)) + 0x9E3779B97F4A7C15ULL * (t + 1);
+    uint64_t s = h & mask;
+    while (true) {
+      uint32_t cur = tab[s];
+      if (cur == EMPTY) {
+        cur = atomicCAS(&tab[s], EMPTY, (uint32_t)j);
+        if (cur == EMPTY) { slot_of[j] = (uint32_t)s; break; }
+      }
+      const uint64_t* osrc; bool orc;
+      slot_origin(S, cur, osrc, orc);
+      bool same = true;
+      for (uint32_t t = 0; t < S.wpr && same; t++) same = slot_word(S, osrc, orc, t) == slot_word(S, src, rc, t);
       if (same) { atomicMin(&tab[s], (uint32_t)j); slot_of[j] = (uint32_t)s; break; }
       s = (s + 1) & mask;
     }
@@ -136,8 +160,8 @@ extern "C" int shn_reads_dedup(shn_ctx* ctx, const shn_reads* a, const shn_reads
                                uint64_t* n_distinct, uint32_t* slot_out, uint32_t* count_out, int32_t* mate_out, uint8_t* role_out) {
   if (!ctx || !a || !n_distinct || (n && (!didx || !slot_out || !count_out || !mate_out || !role_out)) || (paired && !b))
     return shn_fail(SHN_ERR_ARG, "shn_reads_dedup: NULL argument");
-  if (!a->fixed_len || a->wpr > (uint32_t)MAXW || (b && (b->fixed_len != a->fixed_len || b->wpr != a->wpr)))
-    return shn_fail(SHN_ERR_ARG, "shn_reads_dedup: fixed-length read sets of one length (<= 512 bases) only");
+  if (!a->fixed_len || (b && (b->fixed_len != a->fixed_len || b->wpr != a->wpr)))
+    return shn_fail(SHN_ERR_ARG, "shn_reads_dedup: fixed-length read sets of one length only");
   const uint64_t nm = paired ? 2 : 1, nh = n * nm;
   *n_distinct = 0;
   if (!nh) return SHN_OK;
@@ -178,7 +202,8 @@ extern "C" int shn_reads_dedup(shn_ctx* ctx, const shn_reads* a, const shn_reads
   const uint32_t grid = (uint32_t)std::min<uint64_t>(cdiv(nh, 256), 1u << 20);
   { TimerRegion tdi(ctx, T_DD_INSERT); tdi.bytes(nh * ((uint64_t)a->wpr * 8 * 2 + 4 + 4 + 4));      // per read slot: its index, its words and the words of the slot it meets, the table word, its slot written
     if (a->wpr <= 4) hipLaunchKernelGGL(dd_insert<4>, dim3(grid), dim3(256), 0, s, S, nh, d_tab, T - 1, d_slot);
-    else hipLaunchKernelGGL(dd_insert<MAXW>, dim3(grid), dim3(256), 0, s, S, nh, d_tab, T - 1, d_slot); }
+    else if (a->wpr <= (uint32_t)MAXW) hipLaunchKernelGGL(dd_insert<MAXW>, dim3(grid), dim3(256), 0, s, S, nh, d_tab, T - 1, d_slot);
+    else hipLaunchKernelGGL(dd_insert_wide, dim3(grid), dim3(256), 0, s, S, nh, d_tab, T - 1, d_slot); }
   hipLaunchKernelGGL(dd_tally, dim3(grid), dim3(256), 0, s, nh, d_tab, d_slot, d_first, d_cnt, d_last, d_flag);
   TRYD(hipGetLastError());
   uint64_t nd = 0;
@@ -215,8 +240,8 @@ void shn_dedup_destroy(shn_dedup* d) {
 int shn_reads_dedup_dev(shn_ctx* ctx, const shn_reads* a, const shn_reads* b, const uint32_t* didx, const uint32_t* d_didx, uint64_t n, int paired,
                         shn_dedup** out) {
   if (!ctx || !a || !out || (n && !didx && !d_didx) || (paired && !b)) return shn_fail(SHN_ERR_ARG, "shn_reads_dedup_dev: NULL argument");
-  if (!a->fixed_len || a->wpr > (uint32_t)MAXW || (b && (b->fixed_len != a->fixed_len || b->wpr != a->wpr)))
-    return shn_fail(SHN_ERR_ARG, "shn_reads_dedup_dev: fixed-length read sets of one length (<= 512 bases) only");
+  if (!a->fixed_len || (b && (b->fixed_len != a->fixed_len || b->wpr != a->wpr)))
+    return shn_fail(SHN_ERR_ARG, "shn_reads_dedup_dev: fixed-length read sets of one length only");
   const uint64_t nm = paired ? 2 : 1, nh = n * nm;
   if (nh >= (1ULL << 31)) return shn_fail(SHN_ERR_ARG, "shn_reads_dedup_dev: more than 2^31 read slots");
   const uint64_t n_in = a->n_reads;
@@ -252,7 +277,8 @@ int shn_reads_dedup_dev(shn_ctx* ctx, const shn_reads* a, const shn_reads* b, co
   const uint32_t grid = (uint32_t)std::min<uint64_t>(cdiv(nh, 256), 1u << 20);
   { TimerRegion tdi(ctx, T_DD_INSERT); tdi.bytes(nh * ((uint64_t)a->wpr * 8 * 2 + 4 + 4 + 4));      // per read slot: its index, its words and the words of the slot it meets, the table word, its slot written
     if (a->wpr <= 4) hipLaunchKernelGGL(dd_insert<4>, dim3(grid), dim3(256), 0, s, S, nh, d_tab, T - 1, d_slot);
-    else hipLaunchKernelGGL(dd_insert<MAXW>, dim3(grid), dim3(256), 0, s, S, nh, d_tab, T - 1, d_slot); }
+    else if (a->wpr <= (uint32_t)MAXW) hipLaunchKernelGGL(dd_insert<MAXW>, dim3(grid), dim3(256), 0, s, S, nh, d_tab, T - 1, d_slot);
+    else hipLaunchKernelGGL(dd_insert_wide, dim3(grid), dim3(256), 0, s, S, nh, d_tab, T - 1, d_slot); }
   hipLaunchKernelGGL(dd_tally, dim3(grid), dim3(256), 0, s, nh, d_tab, d_slot, d_first, d_cnt, d_last, d_flag);
   TRYD(hipGetLastError());
   uint64_t nd = 0;

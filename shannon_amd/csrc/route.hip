@@ -8,12 +8,16 @@
 // and reverse complements are computed on chip from the packed forward reads.  A read (pair) with
 // any non-ACGT base is dropped (:336, :376).  Probes: k1-windows at 0,k1,2k1,... while i < len-k1,
 // plus the last window; the read goes to the union of the partition sets of the probes that hit.
+// get_comps has no bound on that union: a pair whose union outgrows the MAXP registers of the
+// routing kernel is listed by the counting pass and collected again, uncapped, by route_wide_kernel
+// into a buffer as large as the sets it hit.
 #include "common.h"
 #include <cstring>
 #include <algorithm>
 
 #define RBLK 256
-#define MAXP 32   // distinct partitions one read (pair) can hit: 2 mates x probes x set size, deduplicated
+#define MAXP 32   // distinct partitions of one read (pair) the routing kernel keeps in registers (more: route_wide_kernel)
+#define WIDE 0x80000000u   // counting pass: counts[d] of a pair with more = WIDE | sum of the sizes of the sets it hit
 
 struct RView {
   const uint64_t* words; const uint64_t* woff; const uint32_t* len; const uint8_t* bad;
@@ -73,11 +77,12 @@ __device__ __forceinline__ uint32_t pd_find(const ProbeDict& D, uint64_t key, in
   return j >= 0 ? tvals[j] : 0u;
 }
 
-// collects the partitions hit by one read into loc[] (dedup), returns new count
+// collects the partitions hit by one read into loc[] (dedup, room for `cap`), returns new count; `hits` adds up the sizes of the
+// sets hit (a bound on the distinct partitions), `full` notes a partition that found no room
 __device__ __forceinline__ int collect(const RView& v, uint64_t r, bool rc, int k, const uint64_t* __restrict__ tkeys,
                                        const uint32_t* __restrict__ tvals, const uint64_t* __restrict__ boff, int bits, const ProbeDict& D,
                                        const uint32_t* __restrict__ set_off, const uint32_t* __restrict__ set_mem,
-                                       uint32_t* loc, int nloc, uint32_t* overflow) {
+                                       uint32_t* loc, int nloc, int cap, uint32_t& hits, bool& full) {
   uint32_t len = v.len ? v.len[r] : v.fixed_len;
   if (len < (uint32_t)k) {
     // get_rmers on a short read returns [read[-R:]] = the whole read, which is not a k1-mer key: no hit
@@ -95,12 +100,42 @@ __device__ __forceinline__ int collect(const RView& v, uint64_t r, bool rc, int 
     int64_t j = D.lines ? -1 : shn_table_find_k(tkeys, boff, bits, key, 2 * k);
     if (val || j >= 0) {
       uint32_t sid = (val ? val : tvals[j]) - 1;
-      for (uint32_t m = set_off[sid]; m < set_off[sid + 1]; m++) {
+      const uint32_t m0 = set_off[sid], m1 = set_off[sid + 1];
+      hits = hits + (m1 - m0) < hits ? 0xFFFFFFFFu : hits + (m1 - m0);
+      for (uint32_t m = m0; m < m1; m++) {
         uint32_t p = set_mem[m];
         bool seen = false;
         for (int q = 0; q < nloc; q++) seen |= (loc[q] == p);
-        if (!seen) { if (nloc < MAXP) loc[nloc++] = p; else atomicExch(overflow, 1u); }
+        if (!seen) { if (nloc < cap) loc[nloc++] = p; else full = true; }
       }
+    }
+  }
+  return nloc;
+}
+
+// the partitions of doubled read (pair) d, as get_comps finds them for the read files of shannon.py:396-424
+__device__ __forceinline__ int collect_read(uint64_t d, const RView& a, const RView& b, int paired, int ss, int k, const uint64_t* __restrict__ tkeys,
+                                            const uint32_t* __restrict__ tvals, const uint64_t* __restrict__ boff, int bits, const ProbeDict& D,
+                                            const uint32_t* __restrict__ set_off, const uint32_t* __restrict__ set_mem,
+                                            uint32_t* loc, int cap, uint32_t& hits, bool& full) {
+  const uint64_t N = a.n;
+  const bool second = d >= N;
+  const uint64_t i = second ? d - N : d;
+  int nloc = 0;
+  if (ss) {
+    // -s / --ss (shannon.py:407-411): the read files are reads (SE) or reads_1 and RC(reads_2) (PE), not doubled: index d < N only
+    const bool dropped = second || (a.bad && a.bad[i]) || (paired && b.bad && b.bad[i]);
+    if (!dropped) {
+      nloc = collect(a, i, false, k, tkeys, tvals, boff, bits, D, set_off, set_mem, loc, nloc, cap, hits, full);
+      if (paired) nloc = collect(b, i, true, k, tkeys, tvals, boff, bits, D, set_off, set_mem, loc, nloc, cap, hits, full);
+    }
+  } else if (!paired) {
+    if (!(a.bad && a.bad[i])) nloc = collect(a, i, second, k, tkeys, tvals, boff, bits, D, set_off, set_mem, loc, nloc, cap, hits, full);
+  } else {
+    const RView& src = second ? b : a;        // d<N: (R1, RC(R1)); d>=N: (RC(R2), R2)
+    if (!(src.bad && src.bad[i])) {
+      nloc = collect(src, i, second, k, tkeys, tvals, boff, bits, D, set_off, set_mem, loc, nloc, cap, hits, full);   // mate 1
+      nloc = collect(src, i, !second, k, tkeys, tvals, boff, bits, D, set_off, set_mem, loc, nloc, cap, hits, full);  // mate 2
     }
   }
   return nloc;
@@ -111,45 +146,64 @@ __global__ __launch_bounds__(RBLK) void route_kernel(RView a, RView b, int paire
                                                      const uint32_t* __restrict__ tvals, const uint64_t* __restrict__ boff, int bits, ProbeDict D,
                                                      const uint32_t* __restrict__ set_off, const uint32_t* __restrict__ set_mem,
                                                      uint32_t* __restrict__ counts, const uint64_t* __restrict__ offs,
-                                                     uint64_t* __restrict__ out, uint32_t* __restrict__ overflow, uint2* __restrict__ first2) {
+                                                     uint64_t* __restrict__ out, uint32_t* __restrict__ n_wide, uint2* __restrict__ first2) {
   uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   uint64_t N = a.n;
   if (d >= 2 * N) return;
-  // the counting pass leaves the first two partitions of every pair behind: the filling pass probes again only for the pairs
-  // that hit more (nearly every pair hits one partition or none; the probes are the cost of this kernel)
-  if (FILL && first2) {
+  if (FILL) {
     const uint32_t n = counts[d];
-    if (n <= 2) {
+    if (n > MAXP) return;                     // (route_wide_fill_kernel writes the pairs with more)
+    // the counting pass leaves the first two partitions of every pair behind: the filling pass probes again only for the pairs
+    // that hit more (nearly every pair hits one partition or none; the probes are the cost of this kernel)
+    if (first2 && n <= 2) {
       if (n) { const uint2 f = first2[d]; const uint64_t o = offs[d]; out[o] = ((uint64_t)f.x << 32) | (uint64_t)(uint32_t)d; if (n > 1) out[o + 1] = ((uint64_t)f.y << 32) | (uint64_t)(uint32_t)d; }
       return;
     }
   }
   uint32_t loc[MAXP];
-  int nloc = 0;
-  bool second = d >= N;
-  uint64_t i = second ? d - N : d;
-  bool dropped;
-  if (ss) {
-    // -s / --ss (shannon.py:407-411): the read files are reads (SE) or reads_1 and RC(reads_2) (PE), not doubled: index d < N only
-    dropped = second || (a.bad && a.bad[i]) || (paired && b.bad && b.bad[i]);
-    if (!dropped) {
-      nloc = collect(a, i, false, k, tkeys, tvals, boff, bits, D, set_off, set_mem, loc, nloc, overflow);
-      if (paired) nloc = collect(b, i, true, k, tkeys, tvals, boff, bits, D, set_off, set_mem, loc, nloc, overflow);
-    }
-  } else if (!paired) {
-    dropped = a.bad && a.bad[i];
-    if (!dropped) nloc = collect(a, i, second, k, tkeys, tvals, boff, bits, D, set_off, set_mem, loc, nloc, overflow);
-  } else {
-    const RView& src = second ? b : a;        // d<N: (R1, RC(R1)); d>=N: (RC(R2), R2)
-    dropped = src.bad && src.bad[i];
-    if (!dropped) {
-      nloc = collect(src, i, second, k, tkeys, tvals, boff, bits, D, set_off, set_mem, loc, nloc, overflow);   // mate 1
-      nloc = collect(src, i, !second, k, tkeys, tvals, boff, bits, D, set_off, set_mem, loc, nloc, overflow);  // mate 2
-    }
+  uint32_t hits = 0;
+  bool full = false;
+  const int nloc = collect_read(d, a, b, paired, ss, k, tkeys, tvals, boff, bits, D, set_off, set_mem, loc, MAXP, hits, full);
+  if (!FILL) {
+    if (full) { counts[d] = WIDE | min(hits, ~WIDE); atomicAdd(n_wide, 1u); return; }
+    counts[d] = (uint32_t)nloc; if (first2) first2[d] = make_uint2(nloc > 0 ? loc[0] : 0u, nloc > 1 ? loc[1] : 0u); return;
   }
-  if (!FILL) { counts[d] = (uint32_t)nloc; if (first2) first2[d] = make_uint2(nloc > 0 ? loc[0] : 0u, nloc > 1 ? loc[1] : 0u); return; }
   uint64_t o = offs[d];
   for (int q = 0; q < nloc; q++) out[o + q] = ((uint64_t)loc[q] << 32) | (uint64_t)(uint32_t)d;
+}
+
+// ---- pairs that hit more than MAXP partitions (rare: long reads, small partitions).  The counting pass marked them WIDE with a
+// bound on their partitions; listed here, each collects its partitions again into a buffer of that size and gets its true count.
+__global__ void route_wide_list_kernel(uint32_t* __restrict__ counts, uint64_t n2, uint32_t* __restrict__ n_listed, uint32_t* __restrict__ wide_d,
+                                       uint32_t* __restrict__ wide_room) {
+  const uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (d >= n2) return;
+  const uint32_t c = counts[d];
+  if (!(c & WIDE)) return;
+  const uint32_t j = atomicAdd(n_listed, 1u);
+  wide_d[j] = (uint32_t)d;
+  wide_room[j] = c & ~WIDE;
+}
+__global__ __launch_bounds__(RBLK) void route_wide_kernel(RView a, RView b, int paired, int ss, int k, const uint64_t* __restrict__ tkeys,
+                                                          const uint32_t* __restrict__ tvals, const uint64_t* __restrict__ boff, int bits, ProbeDict D,
+                                                          const uint32_t* __restrict__ set_off, const uint32_t* __restrict__ set_mem, uint32_t n_wide,
+                                                          const uint32_t* __restrict__ wide_d, const uint32_t* __restrict__ wide_room,
+                                                          const uint64_t* __restrict__ wide_off, uint32_t* __restrict__ buf, uint32_t* __restrict__ counts) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_wide) return;
+  uint32_t hits = 0;
+  bool full = false;                          // (cannot happen: the room is the sum of the sizes of the sets the pair hits)
+  counts[wide_d[j]] = (uint32_t)collect_read(wide_d[j], a, b, paired, ss, k, tkeys, tvals, boff, bits, D, set_off, set_mem, buf + wide_off[j],
+                                             (int)wide_room[j], hits, full);
+}
+__global__ void route_wide_fill_kernel(uint32_t n_wide, const uint32_t* __restrict__ wide_d, const uint64_t* __restrict__ wide_off,
+                                       const uint32_t* __restrict__ buf, const uint32_t* __restrict__ counts, const uint64_t* __restrict__ offs,
+                                       uint64_t* __restrict__ out) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_wide) return;
+  const uint32_t d = wide_d[j];
+  const uint64_t o = offs[d];
+  for (uint32_t q = 0; q < counts[d]; q++) out[o + q] = ((uint64_t)buf[wide_off[j] + q] << 32) | (uint64_t)d;
 }
 
 __global__ void split_u64_kernel(const uint64_t* __restrict__ in, uint64_t n, uint32_t* __restrict__ hi, uint32_t* __restrict__ lo) {
@@ -264,8 +318,8 @@ extern "C" int shn_route_reads_mode(shn_ctx* ctx, const shn_reads* r1, const shn
   uint32_t* d_sm = d_so + n_sets + 1;
   HIP_TRY(hipMemcpyAsync(d_so, set_off, (size_t)(n_sets + 1) * 4, hipMemcpyHostToDevice, s));
   if (n_mem) HIP_TRY(hipMemcpyAsync(d_sm, set_members, (size_t)n_mem * 4, hipMemcpyHostToDevice, s));
-  uint32_t* d_ovf = (uint32_t*)pflag;
-  HIP_TRY(hipMemsetAsync(d_ovf, 0, 4, s));
+  uint32_t* d_nwide = (uint32_t*)pflag;                 // [0] pairs over MAXP partitions, [1] of them listed
+  HIP_TRY(hipMemsetAsync(d_nwide, 0, 8, s));
   RView a = rview(r1), b = r2 ? rview(r2) : rview(r1);
   shn_routes* R = new shn_routes();
   memset(R, 0, sizeof(*R));
@@ -288,13 +342,30 @@ extern "C" int shn_route_reads_mode(shn_ctx* ctx, const shn_reads* r1, const shn
   void* pf2 = nullptr;
   uint2* d_first2 = shn_ws(ctx)[30].get((N2 + 1) * 8, &pf2) == 0 ? (uint2*)pf2 : nullptr;          // (without it the second pass probes again)
   hipLaunchKernelGGL(route_kernel<false>, dim3(grid), dim3(RBLK), 0, s, a, b, r2 ? 1 : 0, strand_specific ? 1 : 0, k1, probe->d_keys, probe->d_counts,
-                     probe->d_bucket_off, probe->bits, D, d_so, d_sm, (uint32_t*)pcnt, nullptr, nullptr, d_ovf, d_first2);
+                     probe->d_bucket_off, probe->bits, D, d_so, d_sm, (uint32_t*)pcnt, nullptr, nullptr, d_nwide, d_first2);
+  uint32_t n_wide = 0;
+  HIP_TRY(hipMemcpyAsync(&n_wide, d_nwide, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  ShnDevBufs wbufs(s);
+  uint32_t *d_wd = nullptr, *d_wroom = nullptr, *d_wbuf = nullptr;
+  uint64_t* d_woff = nullptr;
+  if (n_wide) {
+    // the pairs over MAXP partitions: listed, collected again into room of their own, their counts made exact
+#define TRYW(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { delete R; return shn_fail(SHN_ERR_HIP, std::string("shn_route_reads: ") + hipGetErrorString(e_)); } } while (0)
+    TRYW(wbufs.get(&d_wd, (size_t)n_wide * 4));
+    TRYW(wbufs.get(&d_wroom, (size_t)n_wide * 4));
+    TRYW(wbufs.get(&d_woff, (size_t)(n_wide + 1) * 8));
+    hipLaunchKernelGGL(route_wide_list_kernel, dim3(grid), dim3(RBLK), 0, s, (uint32_t*)pcnt, N2, d_nwide + 1, d_wd, d_wroom);
+    uint64_t room = 0;
+    if ((rc = shn_device_scan_u32(ctx, d_wroom, n_wide, d_woff, &room))) { delete R; return rc; }
+    TRYW(wbufs.get(&d_wbuf, (size_t)(room + 1) * 4));
+    hipLaunchKernelGGL(route_wide_kernel, dim3((uint32_t)cdiv(n_wide, RBLK)), dim3(RBLK), 0, s, a, b, r2 ? 1 : 0, strand_specific ? 1 : 0, k1, probe->d_keys,
+                       probe->d_counts, probe->d_bucket_off, probe->bits, D, d_so, d_sm, n_wide, d_wd, d_wroom, d_woff, d_wbuf, (uint32_t*)pcnt);
+    TRYW(hipGetLastError());
+#undef TRYW
+  }
   uint64_t total = 0;
   if ((rc = shn_device_scan_u32(ctx, (uint32_t*)pcnt, N2, (uint64_t*)poff, &total))) { delete R; return rc; }
-  uint32_t ovf = 0;
-  HIP_TRY(hipMemcpyAsync(&ovf, d_ovf, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (ovf) { delete R; return shn_fail(SHN_ERR_OVERFLOW, "shn_route_reads: a read hit more than 32 partitions"); }
   if (total >= 0xFFFFFFFFULL) { delete R; return shn_fail(SHN_ERR_OVERFLOW, "shn_route_reads: more than 2^32 routed pairs"); }
   R->n = total;
   void *pk, *pk2, *pv, *pv2;
@@ -302,7 +373,10 @@ extern "C" int shn_route_reads_mode(shn_ctx* ctx, const shn_reads* r1, const shn
       (rc = shn_ws(ctx)[10].get((total + 2) * 4, &pv)) || (rc = shn_ws(ctx)[12].get((total + 2) * 4, &pv2))) { delete R; return rc; }
   if (total) {
     hipLaunchKernelGGL(route_kernel<true>, dim3(grid), dim3(RBLK), 0, s, a, b, r2 ? 1 : 0, strand_specific ? 1 : 0, k1, probe->d_keys, probe->d_counts,
-                       probe->d_bucket_off, probe->bits, D, d_so, d_sm, (uint32_t*)pcnt, (const uint64_t*)poff, (uint64_t*)pk, d_ovf, d_first2);
+                       probe->d_bucket_off, probe->bits, D, d_so, d_sm, (uint32_t*)pcnt, (const uint64_t*)poff, (uint64_t*)pk, d_nwide, d_first2);
+    if (n_wide)
+      hipLaunchKernelGGL(route_wide_fill_kernel, dim3((uint32_t)cdiv(n_wide, RBLK)), dim3(RBLK), 0, s, n_wide, d_wd, d_woff, d_wbuf, (const uint32_t*)pcnt,
+                         (const uint64_t*)poff, (uint64_t*)pk);
     // pairs were written in doubled-read order; a stable sort on the partition id keeps that order
     HIP_TRY(hipMemsetAsync(pv, 0, total * 4, s));
     int pbits = 1;

@@ -645,6 +645,11 @@ class ReadStore(object):
         """the reads are device.RaggedCodes (reads of different lengths from shn_reads_ingest_ragged)"""
         return isinstance(self.r1, device.RaggedCodes)
 
+    @property
+    def widths_differ(self):
+        """the two mate files are code matrices of two different read lengths (the gathers go read by read)"""
+        return self.r2 is not None and getattr(self.r1, "ndim", 0) == 2 and getattr(self.r2, "ndim", 0) == 2 and self.r1.shape[1] != self.r2.shape[1]
+
     def _gather_ragged(self, idx, mate, ss):
         """gather_codes / gather_codes_ss over RaggedCodes: the reads' codes as stored, one after the other, + offsets + rc flags"""
         idx = np.asarray(idx, dtype=np.int64)
@@ -701,7 +706,7 @@ class ReadStore(object):
         n = self.n
         if self.ragged and len(idx):
             return self._gather_ragged(idx, mate, False)
-        if len(idx) == 0 or isinstance(self.r1[0], str):
+        if len(idx) == 0 or isinstance(self.r1[0], str) or self.widths_differ:
             b, o = self.gather(idx, mate)
             return b, o, None, 0
         second = idx >= n
@@ -734,7 +739,7 @@ class ReadStore(object):
         byte layout shn_mbgraph_run takes.  Vectorised for code matrices."""
         idx = np.asarray(idx, dtype=np.int64)
         n = self.n
-        if len(idx) and not isinstance(self.r1[0], str) and not self.ragged:
+        if len(idx) and not isinstance(self.r1[0], str) and not self.ragged and not self.widths_differ:
             second = idx >= n
             i = np.where(second, idx - n, idx)
             if mate == 1:

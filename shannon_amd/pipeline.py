@@ -190,7 +190,8 @@ def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3
             return isinstance(m, np.ndarray) and m.dtype == np.uint8 and m.ndim == 2 and m.flags["C_CONTIGUOUS"]
         # reads kept as code matrices + GPU unitigs: partitions name their reads by rows (SHN_GRAPH_ROWS=0: gather them on the host)
         # (strand-specific runs hand the reads over as gathered rows + strand flags: the rows mode knows the doubled layout only)
-        rows_mode = (unitigs is not None and d1 is not None and _matrix(store.r1) and (not paired or _matrix(store.r2)) and
+        # (mates of two different lengths: the duplicate search on the device takes read sets of one length)
+        rows_mode = (unitigs is not None and d1 is not None and _matrix(store.r1) and (not paired or (_matrix(store.r2) and store.r2.shape[1] == store.r1.shape[1])) and
                      (not paired or d2 is not None) and os.environ.get("SHN_GRAPH_ROWS", "1") != "0" and not ss)
 
         # the sparse flow of a partition right behind its graph, on the same thread (one algorithm_SF.py process per component in

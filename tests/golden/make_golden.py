@@ -12,7 +12,7 @@ Fixture files (all plain data):
 Each artefact file carries a "standins" note: Jellyfish -> exact brute-force counter;
 gpmetis -> hand-written partition vectors; cvxopt -> stub + the oracle's pinned LP rule/RNG.
 """
-import os, sys, json, gzip, hashlib, shutil, subprocess
+import os, sys, json, gzip, hashlib, shutil, subprocess, collections
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -162,8 +162,13 @@ def main():
            # find_mate_pairs adds paths (mbgraph.py:151-160); the second one is a K=31 case with a multi-node partition
            ("syn_pe_hairpin", 40, 4000, True, 25, 500), ("syn_pe_hairpin_K31", 41, 4000, True, 31, 500),
            # -s / --ss / --strand_specific (shannon.py:407-411): no strand doubling; of a pair, RC(R2) stands for R2
-           ("syn_se_ss_s53", 53, 2500, False, 25, 500), ("syn_pe_ss_s69", 69, 2500, True, 25, 500), ("syn_pe_ss_s71", 71, 2500, True, 25, 500)]
-    for name, seed, npairs, paired, K, psize in syn:
+           ("syn_se_ss_s53", 53, 2500, False, 25, 500), ("syn_pe_ss_s69", 69, 2500, True, 25, 500), ("syn_pe_ss_s71", 71, 2500, True, 25, 500),
+           # read lengths other than 100 (read_len, frag_len): 2x150 (the sixth word of a read is all padding); 128 bases, the last
+           # k1 = 32 window ending on a word boundary; 2x250 at partition size 1 (many probes per mate, pairs routed to many
+           # partitions); 64 bases, two words and no padding
+           ("syn_pe_L150_K25", 90, 2500, True, 25, 500, 150, 400), ("syn_se_L128_K31", 93, 2500, False, 31, 500, 128, 300),
+           ("syn_pe_L250_K20_part1", 96, 2500, True, 20, 1, 250, 400), ("syn_pe_L64_K24", 99, 2500, True, 24, 500, 64, 300)]
+    for name, seed, npairs, paired, K, psize, *lens in syn:
         ss = "_ss_" in name
         manifest[name] = {"inputs": [name + ".npz"], "K": K, "paired": paired, "sf_seed": seed, "partition_size": psize}
         if ss:
@@ -171,7 +176,11 @@ def main():
         if not want(name):
             continue
         isos = hairpin_transcriptome(seed) if "hairpin" in name else tricky_transcriptome(seed, 3 if psize > 10 else 6)
-        r1, r2 = synth.sample_pairs(isos, npairs, seed, err=[0.005, 0.0, 0.01][seed % 3])
+        kw = {}
+        if lens:
+            kw = {"read_len": lens[0], "frag_len": lens[1]}
+            isos = [t for t in isos if len(t) >= lens[1]]
+        r1, r2 = synth.sample_pairs(isos, npairs, seed, err=[0.005, 0.0, 0.01][seed % 3], **kw)
         np.savez_compressed(os.path.join(OUT, "data", name + ".npz"), r1=r1, r2=r2)
         d = os.path.join(TMP, name + "_in")
         os.makedirs(d)
@@ -184,7 +193,9 @@ def main():
         art = H.run_case(os.path.join(TMP, name), [d + "/r1.fasta", d + "/r2.fasta"] if paired else [d + "/r1.fasta"],
                          K, paired, partition_size=psize, part_hook=hook, run_sf=True, sf_seed=seed, double_stranded=not ss)
         save(name, slim(art, keep_full=(name in ("syn_pe_s0", "syn_se_s7_K20"))))
-        print(name, "done", art["n_k1mers"], {c: p["graph"] and len(p["graph"]["nodes"]) for c, p in art["partitions"].items()})
+        fan = collections.Counter(r for p in art["partitions"].values() for r in set(zip(*p["reads"])))
+        print(name, "done", art["n_k1mers"], {c: p["graph"] and len(p["graph"]["nodes"]) for c, p in art["partitions"].items()},
+              "most partitions of one read (pair):", max(fan.values(), default=0))
     json.dump(manifest, open(os.path.join(OUT, "manifest.json"), "w"), indent=1)
     # --- the two k-mer cutoffs of the CLI (shannon.py:237-247): --kmer_hard_cutoff = the -L of `jellyfish dump` (:441),
     # --kmer_soft_cutoff = hyp_min_weight = run_correction's min_weight (:457), alone and together, on inputs of cases above

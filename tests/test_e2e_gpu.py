@@ -179,16 +179,15 @@ def test_graph_reads_gathered_on_the_device_equal_uploaded_text(ctx, monkeypatch
             assert a.final == b.final and len(a.final) > 10
 
 
-@pytest.mark.parametrize("paired", [False, True])
-def test_distinct_reads_found_on_the_device_equal_the_read_dictionary(ctx, paired):
-    """shn_reads_dedup against Read.reads filled one read (pair) at a time (mbgraph.py:56-70, multibridging.py:185-236): ids in
-    order of first occurrence, copy counts, and for pairs the role and mate of each read's LAST occurrence."""
+def _dedup_vs_read_dictionary(ctx, paired, L, seed):
     import numpy as np
     from shannon_amd import device, mbgraph_native
-    rng = np.random.RandomState(5 + paired)
-    n, L = 3000, 77
+    rng = np.random.RandomState(seed)
+    n = 3000
     pool = rng.randint(0, 4, size=(40, L)).astype(np.uint8)
     pool[7] = (3 - pool[6][::-1])                                   # a read and its reverse complement, and a palindrome-free pool otherwise
+    if L % 2 == 0:                                                  # (even lengths: one read that is its own reverse complement)
+        pool[8][L // 2:] = 3 - pool[8][:L // 2][::-1]
     m1 = pool[rng.randint(0, 40, size=n)].copy()
     m2 = pool[rng.randint(0, 40, size=n)].copy()
     d1 = device.Reads.from_codes(ctx, m1)
@@ -220,6 +219,63 @@ def test_distinct_reads_found_on_the_device_equal_the_read_dictionary(ctx, paire
             roles[a] = 1; roles[b] = 2; mates[a] = b; mates[b] = a
     assert len(ids) < len(didx) and len(slot) == len(ids)
     assert slot.tolist() == first and cnt.tolist() == counts and mate.tolist() == mates and role.tolist() == roles
+    d1.close()
+    if d2 is not None:
+        d2.close()
+
+
+@pytest.mark.parametrize("paired", [False, True])
+def test_distinct_reads_found_on_the_device_equal_the_read_dictionary(ctx, paired):
+    """shn_reads_dedup against Read.reads filled one read (pair) at a time (mbgraph.py:56-70, multibridging.py:185-236): ids in
+    order of first occurrence, copy counts, and for pairs the role and mate of each read's LAST occurrence."""
+    _dedup_vs_read_dictionary(ctx, paired, 77, 5 + paired)
+
+
+@pytest.mark.parametrize("paired", [False, True])
+@pytest.mark.parametrize("L", [31, 32, 64, 96, 128, 129, 150, 250, 512, 513, 600])
+def test_distinct_reads_found_on_the_device_at_read_lengths(ctx, paired, L):
+    """The same at the edges of the word geometry (32 bases per word, 2 * ceil(L / 64) words per read): one word, exact words, a
+    whole padding word; dd_insert<4> up to 128 bases, dd_insert<16> at 129-512, dd_insert_wide beyond (reads of more than 512
+    bases used to be refused, which failed the graph stage of any run on such reads)."""
+    _dedup_vs_read_dictionary(ctx, paired, L, 11 * L + paired)
+
+
+def _lengths_case(case):
+    """inputs of test_end_to_end_at_read_lengths: (reads for the pipeline, reads for the oracle) -- code matrices where the reads
+    have one length per mate file (the graph stage then names them by rows of the resident sets), strings otherwise"""
+    import numpy as np
+    from shannon_amd import synth
+    A = np.frombuffer(b"ACGT", np.uint8)
+    txt = lambda rows: [A[r].tobytes().decode() for r in rows]
+    iso, _ = synth.make_transcriptome(5, seed=61)
+    L = {"L513": 513, "L600": 600}.get(case, 150)
+    iso = [t for t in iso if len(t) >= L + 150]
+    r1, r2 = synth.sample_pairs(iso, 1200, 62, read_len=L, frag_len=L + 150, err=0.003)
+    if case in ("L513", "L600"):
+        return (r1, r2), (txt(r1), txt(r2))
+    if case == "mates_differ":
+        a, b = np.ascontiguousarray(r1[:, :100]), np.ascontiguousarray(r2[:, :80])
+        return (a, b), (txt(a), txt(b))
+    rng = np.random.RandomState(63)                                   # ragged: 30-150 bases, the mates of a pair of different lengths
+    s1 = [t[:rng.randint(30, 151)] for t in txt(r1)]
+    s2 = [t[:rng.randint(30, 151)] for t in txt(r2)]
+    return (s1, s2), (s1, s2)
+
+
+@pytest.mark.parametrize("case", ["L513", "L600", "ragged", "mates_differ"])
+def test_end_to_end_at_read_lengths(ctx, case):
+    """Reads the device duplicate search took no part in before, or must be kept away from: longer than 512 bases (one word
+    more than its register bound), a ragged set, mates of different fixed lengths -- pipeline.assemble against the oracle."""
+    from shannon_amd import pipeline
+    from oracle import pipeline as opipe
+    (p1, p2), (o1, o2) = _lengths_case(case)
+    R = pipeline.assemble(ctx, p1, p2, K=25, sample="s", seed=7)
+    O = opipe.assemble(o1, o2, K=25, sample="s", seed=7)
+    assert R.extension.contigs == O["contigs"]
+    assert list(R.partitions) == list(O["partitions"]) and len(R.partitions) > 0
+    for p in R.partitions:
+        cmp_fasta(R.partitions[p]["reconstructed_fasta"], O["partitions"][p]["reconstructed_fasta"])
+    assert R.final == O["final"] and len(R.final) > 0
 
 
 def test_two_batches_in_flight_give_the_sequential_results(ctx):

@@ -19,3 +19,17 @@ def test_random_input_equals_the_oracle(seed):
         assert ok, text
     finally:
         ctx.close()
+
+
+@pytest.mark.parametrize("seed,read_len", [(3100, 64), (3101, 150), (3102, "mixed")])
+def test_random_input_at_other_read_lengths_equals_the_oracle(seed, read_len):
+    """the same at other read lengths: two words and no padding (64), a whole padding word (150), and a ragged set of 30-150 bases
+    whose mates differ in length"""
+    import random_parity
+    from shannon_amd import device
+    ctx = device.Context(0)
+    try:
+        ok, text = random_parity.run_case(ctx, seed, read_len=read_len)
+        assert ok, text
+    finally:
+        ctx.close()

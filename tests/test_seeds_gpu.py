@@ -6,14 +6,42 @@ from golden_util import *
 pytestmark = pytest.mark.gpu
 
 
+def _device_reads(ctx, reads, fixed):
+    """reads of one length as a fixed-length set (read r at word r * wpr) or, fixed=False, as a ragged one (word offsets)"""
+    from shannon_amd import device
+    if fixed:
+        return device.Reads.from_codes(ctx, np.frombuffer("".join(reads).translate(str.maketrans("ACGT", "\x00\x01\x02\x03")).encode(),
+                                                           np.uint8).reshape(len(reads), -1))
+    return device.Reads.from_strings(ctx, reads)
+
+
 def test_seed_scans_match_host():
-    import ctypes as C
-    from shannon_amd import device, _lib, graph_seeds
-    from shannon_amd.kmers_for_component import make_table
+    from shannon_amd import device
     ctx = device.Context(0)
     rng = np.random.default_rng(3)
-    K = 25
     reads = ["".join("ACGT"[c] for c in rng.integers(0, 4, int(rng.integers(20, 140)))) for _ in range(3000)]
+    _seed_scans(ctx, reads, rng, 25, False)
+    ctx.close()
+
+
+@pytest.mark.parametrize("L", [128, 129, 150, 250])
+def test_seed_scans_match_host_fixed_length(L):
+    """the same on fixed-length read sets, whose reads the kernels address as r * wpr: the last window ending on a word boundary
+    (128), one base into a new pair of words (129), a whole padding word (150), eight words (250)"""
+    from shannon_amd import device
+    ctx = device.Context(0)
+    rng = np.random.default_rng(L)
+    reads = ["".join("ACGT"[c] for c in rng.integers(0, 4, L)) for _ in range(2000)]
+    for i in range(0, len(reads) - 1, 13):                          # (seeds at both ends: a read starting with another's last K-mer)
+        reads[i + 1] = reads[i][-25:] + reads[i + 1][25:]
+    _seed_scans(ctx, reads, rng, 25, True)
+    ctx.close()
+
+
+def _seed_scans(ctx, reads, rng, K, fixed):
+    import ctypes as C
+    from shannon_amd import _lib, graph_seeds
+    from shannon_amd.kmers_for_component import make_table
     pats = {}
     for r in reads[::7]:
         if len(r) >= K + 5:
@@ -21,7 +49,7 @@ def test_seed_scans_match_host():
             pats.setdefault(r[p:p + K], len(pats))
     keys = list(pats)
     tab = make_table(ctx, graph_seeds.pack_strings(keys, K), np.arange(1, len(keys) + 1, dtype=np.uint32), K)
-    rd = device.Reads.from_strings(ctx, reads)
+    rd = _device_reads(ctx, reads, fixed)
     n = C.c_uint64(0)
     _lib.check(_lib.lib().shn_seed_scan(ctx.h, rd.h, K, tab.h, C.byref(n), None, None, None))
     r_ = np.empty(n.value, np.uint32); s_ = np.empty(n.value, np.uint32); i_ = np.empty(n.value, np.uint32)
@@ -33,11 +61,20 @@ def test_seed_scans_match_host():
     assert a.tolist() == [pats.get(rb[:K], -1) + 1 if len(rb) >= K else 0 for rb in reads]
     assert b.tolist() == [pats.get(rb[-K:], -1) + 1 if len(rb) >= K else 0 for rb in reads]
     rd.close(); tab.close()
-    ctx.close()
 
 
 @pytest.mark.parametrize("K,seed", [(25, 1), (31, 2), (12, 3)])
 def test_known_paths_scan_equals_the_index_walk(K, seed):
+    _known_paths_scan(K, seed, 70, False)
+
+
+@pytest.mark.parametrize("L", [64, 128, 150, 250])
+def test_known_paths_scan_at_read_lengths(L):
+    """the same on fixed-length read sets at the edges of the word geometry (two words, four, a padding word, eight)"""
+    _known_paths_scan(31 if L == 128 else 25, 20 + L, L, True)
+
+
+def _known_paths_scan(K, seed, L, fixed):
     """shn_known_paths_scan against the host rule it replaces (mbgraph.py:1355-1388 / search_sequence :114-160, the part every read
     goes through): look the read's first K-mer up in the index of all K-mers of all nodes (occurrences in node order, then offset);
     an occurrence whose node text equals the read's from there on counts -- inside the node if the read ends before the node does
@@ -49,9 +86,8 @@ def test_known_paths_scan_equals_the_index_walk(K, seed):
     base = "".join("ACGT"[i] for i in rng.integers(0, 4, 3000))
     nodes = []
     for _ in range(60):                                              # overlapping pieces of one sequence + repeats of a few
-        a = int(rng.integers(0, len(base) - 200)); nodes.append(base[a:a + int(rng.integers(K, 200))])
+        a = int(rng.integers(0, len(base) - 200)); nodes.append(base[a:a + int(rng.integers(K, max(200, 2 * L)))])
     nodes += nodes[:5] + [nodes[7][3:], nodes[9][:-4]]
-    L = 70
     reads = []
     for _ in range(4000):
         kind = rng.integers(0, 4)
@@ -86,7 +122,7 @@ def test_known_paths_scan_equals_the_index_walk(K, seed):
                     break
             st = 2 if need else 1 if anyin else 0
         want_state.append(st); want_node.append(fn)
-    d = device.Reads.from_strings(ctx, reads)
+    d = _device_reads(ctx, reads, fixed)
     text = np.frombuffer("".join(nodes).encode(), np.uint8)
     off = np.zeros(len(nodes) + 1, np.uint64); off[1:] = np.cumsum([len(n) for n in nodes])
     state = np.empty(len(reads), np.uint8); node = np.empty(len(reads), np.int32)
@@ -109,6 +145,16 @@ def test_known_paths_scan_equals_the_index_walk(K, seed):
 
 @pytest.mark.parametrize("K,seed,cap", [(25, 5, 1 << 16), (31, 6, 1 << 16), (12, 7, 1 << 16), (25, 8, 300)])
 def test_known_paths_search_equals_the_recursion(K, seed, cap):
+    _known_paths_search(K, seed, cap, 100, False)
+
+
+@pytest.mark.parametrize("L", [64, 128, 150, 250])
+def test_known_paths_search_at_read_lengths(L):
+    """the same on fixed-length read sets of other lengths: longer reads cross more nodes"""
+    _known_paths_search(31 if L == 128 else 25, 40 + L, 1 << 18, L, True)
+
+
+def _known_paths_search(K, seed, cap, L, fixed):
     """shn_known_paths_search: the reads that run past the node their first K-mer lies in, searched on the device, against the
     reference's recursion (mbgraph.py:114-160 search_sequence: follow the out-edges in list order while the node texts agree with
     the read; every complete way is a path, in that order) on a graph cut from one sequence with branches, repeats and dead ends;
@@ -137,7 +183,6 @@ def test_known_paths_search_equals_the_recursion(K, seed, cap):
             edges.setdefault(len(nodes) - 1, []).append((i + 1, K - 1))
     for i in range(4, n_main - 2, 7):                                # a second edge to the true successor with a wrong overlap: never agrees
         edges[i].append((i + 1, 3))
-    L = 100
     reads = []
     for _ in range(3000):
         a = int(rng.integers(0, len(base) - L)); r = base[a:a + L]
@@ -156,7 +201,7 @@ def test_known_paths_search_equals_the_recursion(K, seed, cap):
             if ov <= len(nodes[dst]) and seq[so2:so2 + n] == nodes[dst][ov:ov + n]:
                 search(seq, so2, dst, ov, hops - 1, cur, out)
         cur.pop()
-    d = device.Reads.from_strings(ctx, reads)
+    d = _device_reads(ctx, reads, fixed)
     text = np.frombuffer("".join(nodes).encode(), np.uint8)
     off = np.zeros(len(nodes) + 1, np.uint64); off[1:] = np.cumsum([len(n) for n in nodes])
     eoff = np.zeros(len(nodes) + 1, np.uint32)

@@ -13,8 +13,9 @@ from oracle import pipeline as opipe
 A = np.frombuffer(b"ACGT", np.uint8)
 
 
-def run_case(ctx, seed, big=False):
-    """one random case; returns (equal?, description)"""
+def run_case(ctx, seed, big=False, read_len=None):
+    """one random case; returns (equal?, description).  read_len: reads of that length (fragments of at least 300 bases, 100 more
+    than the read), or "mixed": 30-150 bases, the two mates of a pair of different lengths (the reads then go in as strings)"""
     if True:
         rng = np.random.default_rng(seed)
         n_pairs = int(rng.integers(1500, 7000)) * (4 if big else 1)
@@ -23,9 +24,16 @@ def run_case(ctx, seed, big=False):
         paired = bool(rng.integers(0, 2))
         psize = int(rng.choice([4, 8, 500]))
         ss = os.environ.get("PARITY_SS", "") == "1" or (os.environ.get("PARITY_SS", "") == "mix" and seed % 3 == 0)      # -s / --ss (shannon.py:407-411)
-        (r1, r2), _ = synth.make_dataset(n_pairs, n_genes, seed=seed)
+        L = 150 if read_len == "mixed" else read_len
+        kw = {} if L is None else {"read_len": L, "frag_len": max(300, L + 100)}
+        (r1, r2), _ = synth.make_dataset(n_pairs, n_genes, seed=seed, **kw)
         s1 = [A[r].tobytes().decode() for r in r1]
         s2 = [A[r].tobytes().decode() for r in r2]
+        if read_len == "mixed":
+            cut = np.random.default_rng(seed + 1).integers(30, 151, size=(2, len(s1)))
+            s1 = [r[:c] for r, c in zip(s1, cut[0])]
+            s2 = [r[:c] for r, c in zip(s2, cut[1])]
+            r1, r2 = s1, s2
         t = time.time()
         R = pipeline.assemble(ctx, r1, r2 if paired else None, K=K, partition_size=psize, sample="s", seed=seed % 7, double_stranded=not ss)
         tg = time.time() - t
@@ -46,8 +54,8 @@ def run_case(ctx, seed, big=False):
                 a = [l for l in R.partitions[p]["reconstructed_fasta"].splitlines() if not l.startswith(">")]
                 b = [l for l in O["partitions"][p]["reconstructed_fasta"].splitlines() if not l.startswith(">")]
                 ok = ok and a == b
-        return ok, ("seed %d: pairs %d genes %d K %d %s partition %d: contigs %d partitions %d transcripts %d  %s  (product %.2f s, oracle %.1f s)"
-                    % (seed, n_pairs, n_genes, K, ("PE" if paired else "SE") + (" -s" if ss else ""), psize, len(O["contigs"]), len(O["partitions"]), len(O["final"]),
+        return ok, ("seed %d: pairs %d genes %d K %d %s partition %d reads %s: contigs %d partitions %d transcripts %d  %s  (product %.2f s, oracle %.1f s)"
+                    % (seed, n_pairs, n_genes, K, ("PE" if paired else "SE") + (" -s" if ss else ""), psize, read_len or 100, len(O["contigs"]), len(O["partitions"]), len(O["final"]),
                        "equal" if ok else "DIFFERENT", tg, to))
 
 

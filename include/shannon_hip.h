@@ -384,6 +384,15 @@ int shn_unitigs_build(shn_ctx* ctx, const uint8_t* bases, const uint64_t* off, u
 void shn_unitigs_destroy(shn_unitigs* u);
 /* distinct K-mers of partition `part` (the node count after loading: the read cap is 10 x this, multibridging.py:26-30, 385-391) */
 uint64_t shn_unitigs_n_kmers(const shn_unitigs* u, uint32_t part);
+/* Read-only view of partition `part` (what the graph stage is handed; the tests hold it against the sequential code).
+ * sizes[5] = n_kmers, cyclic flag (1: holds a cycle of condensable edges -- the arrays then leave out the cycle's K-mers and the graph
+ * stage builds the partition from its rows), n_nodes, node bases, n_edges.  Export: the final nodes in stored (creation) order --
+ * n_off[n_nodes+1] into n_bases, n_len = K-mers merged into the node, n_tail_out = out-degree of the node's last K-mer; the edges in
+ * stored (edge-id) order -- e_src / e_dst = partition-local node indices, e_out_rank / e_in_rank = the edge's place in the source's
+ * out-list / the destination's in-list.                                                                                            */
+int shn_unitigs_sizes(const shn_unitigs* u, uint32_t part, uint64_t* sizes);
+int shn_unitigs_export(const shn_unitigs* u, uint32_t part, uint64_t* n_off, uint8_t* n_bases, uint32_t* n_len, uint32_t* n_tail_out,
+                       uint32_t* e_src, uint32_t* e_dst, uint32_t* e_out_rank, uint32_t* e_in_rank);
 /* shn_mbgraph_run on partition `part` of `ug`.  rows / n_rows (may be NULL / 0): the partition's k1-mers, needed only for a partition
  * that holds a cycle of condensable edges (built by the sequential code) and for SHN_GRAPH_CHECK=1.                               */
 int shn_mbgraph_run_unitigs(shn_ctx* ctx, const shn_unitigs* ug, uint32_t part, const uint8_t* rows, uint64_t n_rows, const uint8_t* r1,

@@ -84,6 +84,8 @@ SIGNATURES = {
     "shn_unitigs_build": (C.c_int, [vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, vpp]),
     "shn_unitigs_destroy": (None, [vp]),
     "shn_unitigs_n_kmers": (C.c_uint64, [vp, C.c_uint32]),
+    "shn_unitigs_sizes": (C.c_int, [vp, C.c_uint32, u64p]),
+    "shn_unitigs_export": (C.c_int, [vp, C.c_uint32] + [vp] * 8),
     "shn_mbgraph_run_unitigs": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, vp, vp, vpp]),
     "shn_graph_sizes": (C.c_int, [vp, u64p]),
     "shn_graph_export": (C.c_int, [vp] + [vp] * 20),

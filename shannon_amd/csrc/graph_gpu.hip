@@ -162,10 +162,10 @@ __global__ void ug_run_start_kernel(const uint32_t* __restrict__ reset, const ui
   UG_FOR(i, ng) if (reset[i]) starts[rsum[i]] = i;            // rsum = exclusive scan: the index of this run
 }
 // merged[i] = group i is alive when visited and not the chain's last: it merges with what follows.
-// boundary[i] = a new group starts at i.  Records the head / tail merge times of the chain for the edge lists.
+// boundary[i] = a new group starts at i.  Records the head merge time of the chain for the edge lists (the tail's: ug_chain_done_kernel).
 __global__ void ug_alive_kernel(const uint32_t* __restrict__ reset, const uint64_t* __restrict__ rsum, const uint64_t* __restrict__ starts,
                                 const uint32_t* __restrict__ gchain, const uint64_t* __restrict__ gpos, const uint64_t* __restrict__ coff, uint64_t ng,
-                                uint64_t round_tag, uint32_t* __restrict__ merged, uint64_t* __restrict__ t_head, uint64_t* __restrict__ t_tail) {
+                                uint64_t round_tag, uint32_t* __restrict__ merged, uint64_t* __restrict__ t_head) {
   UG_FOR(i, ng) {
     const uint32_t c = gchain[i];
     const uint64_t run = reset[i] ? rsum[i] : rsum[i] - 1;      // exclusive scan counts the resets before i
@@ -174,7 +174,6 @@ __global__ void ug_alive_kernel(const uint32_t* __restrict__ reset, const uint64
     const bool m = alive && !last;
     merged[i] = m ? 1u : 0u;
     if (i == coff[c]) t_head[c] = round_tag | gpos[i];          // (a chain in the array has >= 2 groups: its head merges)
-    if (m && i + 2 == coff[c + 1]) t_tail[c] = round_tag | gpos[i];
   }
 }
 __global__ void ug_boundary_kernel(const uint32_t* __restrict__ merged, const uint32_t* __restrict__ gchain, const uint64_t* __restrict__ coff, uint64_t ng,
@@ -193,14 +192,20 @@ __global__ void ug_newpos_kernel(const uint32_t* __restrict__ merged, const uint
 __global__ void ug_chain_count_kernel(const uint32_t* __restrict__ boundary, const uint32_t* __restrict__ gchain, uint64_t ng, uint32_t* __restrict__ ccount) {
   UG_FOR(i, ng) if (boundary[i]) atomicAdd(&ccount[gchain[i]], 1u);
 }
-// chains left with one group are finished (creation stamp recorded); the others keep their groups for the next round
+// chains left with one group are finished (creation stamp recorded); the others keep their groups for the next round.
+// Tail time: every merge whose second node holds the chain's last K-mer re-creates that K-mer's out-edges, so when the last group is
+// absorbed this round they are re-created last by the latest merge of the run that swallows it -- not by the merge of the group
+// next to it, which comes earlier whenever a group further up the run is visited later (K-mer ids not ascending along the chain).
+// That time is the creation time of the round's last new group.
 __global__ void ug_chain_done_kernel(const uint32_t* __restrict__ ccount, const uint32_t* __restrict__ chain_head_in, const uint64_t* __restrict__ t_head_in,
-                                     const uint64_t* __restrict__ t_tail_in, const uint64_t* __restrict__ coff, const uint32_t* __restrict__ boundary,
+                                     uint64_t* __restrict__ t_tail_in, const uint64_t* __restrict__ coff, const uint32_t* __restrict__ boundary,
                                      const uint64_t* __restrict__ bsum, const unsigned long long* __restrict__ newpos, uint64_t nc, uint64_t round_tag,
                                      uint64_t* __restrict__ fin_stamp, uint64_t* __restrict__ fin_thead, uint64_t* __restrict__ fin_ttail,
                                      uint32_t* __restrict__ keep, uint32_t* __restrict__ keep_groups) {
   UG_FOR(c, nc) {
     const bool done = ccount[c] == 1;
+    const uint64_t last = coff[c + 1] - 1;                           // (a chain in the array has >= 2 groups: last > coff[c])
+    if (!boundary[last]) t_tail_in[c] = round_tag | (uint64_t)newpos[bsum[last] - 1];
     keep[c] = done ? 0u : 1u;
     keep_groups[c] = done ? 0u : ccount[c];
     if (done) {
@@ -310,6 +315,37 @@ __global__ void ug_edge_heads_kernel(uint32_t* __restrict__ e_src, uint32_t* __r
 
 extern "C" void shn_unitigs_destroy(shn_unitigs* u) { delete u; }
 extern "C" uint64_t shn_unitigs_n_kmers(const shn_unitigs* u, uint32_t part) { return (u && part < u->n_parts) ? u->n_kmers[part] : 0; }
+
+// read-only view of one partition (the tests compare it with the sequential code): what load_unitigs is given, copied out
+extern "C" int shn_unitigs_sizes(const shn_unitigs* u, uint32_t part, uint64_t* sizes) {
+  if (!u || !sizes || part >= u->n_parts) return shn_fail(SHN_ERR_ARG, "shn_unitigs_sizes: bad unitigs / partition");
+  const uint64_t n0 = u->node_off[part], n1 = u->node_off[part + 1];
+  sizes[0] = u->n_kmers[part];
+  sizes[1] = u->cyclic[part];
+  sizes[2] = n1 - n0;
+  sizes[3] = n1 > n0 ? u->base_off[n1] - u->base_off[n0] : 0;
+  sizes[4] = u->edge_off[part + 1] - u->edge_off[part];
+  return SHN_OK;
+}
+extern "C" int shn_unitigs_export(const shn_unitigs* u, uint32_t part, uint64_t* n_off, uint8_t* n_bases, uint32_t* n_len, uint32_t* n_tail_out,
+                                  uint32_t* e_src, uint32_t* e_dst, uint32_t* e_out_rank, uint32_t* e_in_rank) {
+  if (!u || part >= u->n_parts || !n_off || !n_bases || !n_len || !n_tail_out || !e_src || !e_dst || !e_out_rank || !e_in_rank)
+    return shn_fail(SHN_ERR_ARG, "shn_unitigs_export: bad unitigs / partition / NULL argument");
+  const uint64_t n0 = u->node_off[part], n1 = u->node_off[part + 1], e0 = u->edge_off[part], e1 = u->edge_off[part + 1];
+  n_off[0] = 0;
+  if (n1 > n0) {
+    const uint64_t b0 = u->base_off[n0];
+    for (uint64_t i = n0; i < n1; i++) n_off[i - n0 + 1] = u->base_off[i + 1] - b0;
+    memcpy(n_bases, u->bases.data() + b0, u->base_off[n1] - b0);
+    memcpy(n_len, u->n_len.data() + n0, (n1 - n0) * 4);
+    memcpy(n_tail_out, u->n_tail_out.data() + n0, (n1 - n0) * 4);
+  }
+  if (e1 > e0) {
+    memcpy(e_src, u->e_src.data() + e0, (e1 - e0) * 4); memcpy(e_dst, u->e_dst.data() + e0, (e1 - e0) * 4);
+    memcpy(e_out_rank, u->e_out_rank.data() + e0, (e1 - e0) * 4); memcpy(e_in_rank, u->e_in_rank.data() + e0, (e1 - e0) * 4);
+  }
+  return SHN_OK;
+}
 
 // bases/off: the contigs of all partitions one after the other (ASCII), part_of[c] = partition of contig c, ascending.
 extern "C" int shn_unitigs_build(shn_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint64_t n_contigs, const uint32_t* part_of, uint32_t n_parts,
@@ -449,7 +485,7 @@ extern "C" int shn_unitigs_build(shn_ctx* ctx, const uint8_t* bases, const uint6
         if ((rc = shn_device_scan_u32(ctx, d_reset, ng, d_rsum, &nruns))) return rc;
         hipLaunchKernelGGL(ug_run_start_kernel, dim3(ug_grid(ng)), dim3(UG_BLK), 0, s, d_reset, d_rsum, ng, d_starts);
         hipLaunchKernelGGL(ug_alive_kernel, dim3(ug_grid(ng)), dim3(UG_BLK), 0, s, d_reset, d_rsum, d_starts, gchain[a], gpos[a], coff[a], ng, tag, d_merged,
-                           thead[a], ttail[a]);
+                           thead[a]);
         hipLaunchKernelGGL(ug_boundary_kernel, dim3(ug_grid(ng)), dim3(UG_BLK), 0, s, d_merged, gchain[a], coff[a], ng, d_boundary);
         if ((rc = shn_device_scan_u32(ctx, d_boundary, ng, d_bsum, &ngn))) return rc;
         HIP_TRY(hipMemsetAsync(d_newpos, 0, (ngn + 1) * 8, s));

@@ -1551,7 +1551,8 @@ static int mbgraph_run_impl(shn_ctx* ctx, int K, const uint8_t* rows, uint64_t n
       }
     }
   } else {
-    if (ug && !rows && ug->node_off[part + 1] != ug->node_off[part]) return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run_unitigs: cyclic partition needs the k1-mer rows");
+    // (asked by the K-mers, not by the stored nodes: a partition that is nothing but cycles stores no node at all)
+    if (ug && !rows && ug->n_kmers[part] != 0) return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run_unitigs: cyclic partition needs the k1-mer rows");
     g.load_k1mers(rows, n_rows);
     n_kmer_nodes = g.order.size();
   }

@@ -42,6 +42,23 @@ class Unitigs(object):
     def n_kmers(self, part):
         return int(_lib.lib().shn_unitigs_n_kmers(self.h, int(part)))
 
+    def partition(self, part):
+        """Read-only view of one partition (shn_unitigs_sizes / shn_unitigs_export): {"n_kmers", "cyclic", "bases": [str] of the final
+        nodes in stored order, "n_len", "n_tail_out" (uint32 per node), "e_src", "e_dst", "e_out_rank", "e_in_rank" (uint32 per edge,
+        stored = edge-id order)}.  For a cyclic partition the arrays leave out the K-mers of the cycle."""
+        L = _lib.lib()
+        sz = np.zeros(5, dtype=np.uint64)
+        _lib.check(L.shn_unitigs_sizes(self.h, int(part), sz.ctypes.data_as(_lib.u64p)))
+        nk, cyc, nn, nb, ne = [int(x) for x in sz]
+        n_off = np.zeros(nn + 1, np.uint64); n_bases = np.zeros(max(nb, 1), np.uint8)
+        n_len = np.zeros(max(nn, 1), np.uint32); n_tail = np.zeros(max(nn, 1), np.uint32)
+        e = [np.zeros(max(ne, 1), np.uint32) for _ in range(4)]
+        _lib.check(L.shn_unitigs_export(self.h, int(part), *[a.ctypes.data for a in [n_off, n_bases, n_len, n_tail] + e]))
+        txt = n_bases[:nb].tobytes().decode()
+        off = n_off.tolist()
+        return {"n_kmers": nk, "cyclic": bool(cyc), "bases": [txt[off[i]:off[i + 1]] for i in range(nn)], "n_len": n_len[:nn], "n_tail_out": n_tail[:nn],
+                "e_src": e[0][:ne], "e_dst": e[1][:ne], "e_out_rank": e[2][:ne], "e_in_rank": e[3][:ne]}
+
     def close(self):
         if self.h:
             _lib.lib().shn_unitigs_destroy(self.h)

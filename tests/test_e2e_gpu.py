@@ -68,6 +68,15 @@ def test_end_to_end_vs_oracle(ctx, name):
         assert post.finalize_texts([g["all_reconstructed"]], d2, ctx=ctx) == g["final"][k2]
 
 
+@pytest.mark.parametrize("name", ["se_K24", "syn_part_s33", "syn_pe_hairpin_K31"])
+def test_end_to_end_vs_oracle_under_the_unitig_check(ctx, name, monkeypatch):
+    """the same once more with SHN_GRAPH_CHECK=1 (a single-end case, a paired one that goes through the gpmetis branch, one at
+    K = 31): every real partition's GPU unitigs are held against load_k1mers + condense_all by the graph stage's own
+    order-sensitive comparison, in rows mode, where the byte rows are made on demand; a difference is an error return"""
+    monkeypatch.setenv("SHN_GRAPH_CHECK", "1")
+    test_end_to_end_vs_oracle(ctx, name)
+
+
 def test_cli_config1_samples_se(tmp_path):
     """BASELINE configs[0]: Samples/SE_read.fasta, single-end, -K 25, through the shannon.py CLI."""
     import gzip, subprocess, sys, os

@@ -343,6 +343,27 @@ int shn_routes_download(shn_ctx* ctx, const shn_routes* r, uint32_t* pid, uint32
 int shn_routes_bounds(shn_ctx* ctx, const shn_routes* r, uint32_t n_parts, uint32_t split, uint64_t* start, uint64_t* below);
 int shn_routes_download_range(shn_ctx* ctx, const shn_routes* r, uint64_t lo, uint64_t n, uint32_t* ridx);
 
+/* ---- --filter_FP: coverage of the transcripts by the read pairs routed to their partition --------------
+ * Replaces filter_FP.filter_FP (filter_FP.py:29-55: hisat-build, hisat --no-discordant, samtools view -f 0x2 / sort / depth) as
+ * run_MB_SF_fn.py:272-277 calls it once per partition, for ALL partitions in one call.  hisat and samtools are replaced by a
+ * stated rule ("filter_FP"): ungapped placements of both mates on the forward strand of one transcript of the pair's
+ * own partition, at most len / 30 mismatches per mate (a non-ACGT base of a read is one), first mate not behind the second,
+ * fragment no longer than max_span; every placement of a fragment's minimum total cost covers the bases under both mates.
+ *   text / t_off / t_part  the transcripts one after the other (ASCII, ACGT only: SHN_ERR_ARG otherwise), t_off[n_tr + 1],
+ *                          t_part[j] = partition of transcript j (< n_parts)
+ *   r1 / r2                the run's read sets as the user gave them (fixed-length or ragged)
+ *   routes                 the routing's result where it lies on the device, or NULL: then h_pid / h_frag, n_host routes on the host
+ *   strand_specific        != 0: a route's index is the fragment i, oriented pair (r1[i], RC(r2[i])); 0: fragment = index mod
+ *                          #pairs (the strand-doubled numbering of shn_route_reads), oriented pairs (r1[i], RC(r2[i])) and
+ *                          (r2[i], RC(r1[i]))
+ *   hits[n_tr]             covered bases of every transcript (the depth file's line count per transcript, filter_FP.py:7-13)
+ *   stats                  NULL or [2]: routes looked at, routes whose fragment found a concordant placement                    */
+#define SHN_FILTER_FP_MAX_SPAN 500 /* hisat's default -X: the longest fragment a concordant pair may span */
+#define SHN_FILTER_FP_SEED 15      /* seed length of the mapping; a read shorter than this is never placed  */
+int shn_filter_fp_hits(shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off, const uint32_t* t_part, uint64_t n_tr, uint32_t n_parts,
+                       const shn_reads* r1, const shn_reads* r2, const shn_routes* routes, const uint32_t* h_pid, const uint32_t* h_frag,
+                       uint64_t n_host, int strand_specific, uint32_t max_span, uint32_t* hits, uint64_t* stats);
+
 /* ---- K-mer seed scans of reads against graph nodes -----------------------------------------------
  * Replace the per-read Python loops of Read.find_bridging_reads (mbgraph.py:88-111) and known_paths
  * (mbgraph.py:1355-1388).  `patterns`: plain K-mer keys -> value = id+1 (shn_table_create).

@@ -3,13 +3,17 @@
 
 Keeps the reference CLI (sreeramkannan/Shannon shannon.py:145-321) for the flags that drive the
 hot path and produces the same products: OUT/shannon.fasta, OUT/log.txt, OUT/TEMP/ (shannon.py:
-634-638).  Flags that only select external tools outside the path (quorum, kallisto, --compare,
---filter_FP) are accepted and reported as not built.
+634-638).  Flags that only select external tools outside the path (quorum, kallisto, --compare)
+are accepted and reported as not built.
 
     python shannon.py -o OUT --single reads.fasta            [-K 25] [--partition 500]
     python shannon.py -o OUT --left r1.fasta --right r2.fasta [-s / --ss / --strand_specific]
     ... [--kmer_hard_cutoff N]   k1-mers counted fewer than N times are dropped (`jellyfish dump -L N`, shannon.py:237-241, 441; default 1)
     ... [--kmer_soft_cutoff N]   hyp_min_weight: seed threshold + hyperbola of the contig stage (shannon.py:243-247, 457; default 3)
+    ... [--filter_FP]            paired-end runs: after a partition's sparse flow its read pairs are mapped back onto its transcripts and a
+                                 transcript stays only if the pairs cover 90 % of its bases (shannon.py:170-195, filter_FP.py; the aligner is
+                                 the rule of DESIGN.md "filter_FP", run on the GPU); per partition TEMP/<sample>_<name>algo_output/ then holds
+                                 reconstructed.fasta (filtered), reconstructed_org.fasta and rec.log
     python shannon.py -o OUT --left r1.fasta --right r2.fasta -p 8        # one rank per GPU (the reference's -p nJobs, shannon.py:527-566)
 
 -p N / --gpus N: the reference fans its partitions out over nJobs processes (GNU parallel, shannon.py:527-566); here the N jobs
@@ -73,7 +77,7 @@ def launch_ranks(n, args):
     return subprocess.call(cmd, env=env, cwd=os.getcwd())
 
 
-def rank_main(out_dir, reads, K, partition_size, min_weight, min_length, double_stranded, ignored, noted, kmer_hard_cutoff=1):
+def rank_main(out_dir, reads, K, partition_size, min_weight, min_length, double_stranded, ignored, noted, kmer_hard_cutoff=1, filter_fp=False):
     """one rank of an N-rank run: its slice of the reads (by index, contiguous), shannon_amd.distributed.assemble_distributed,
     rank 0 writes OUT/ (shannon.fasta, log.txt, TEMP/<sample>_allalgo_output/all_reconstructed.fasta and the contig files; the
     per-partition graph files stay with the ranks that owned the partitions)"""
@@ -122,6 +126,9 @@ def rank_main(out_dir, reads, K, partition_size, min_weight, min_length, double_
         say("WARNING: flags outside the hot path ignored: " + " ".join(ignored))
     for msg in noted:
         say("NOTE: " + msg)
+    if filter_fp:
+        say("WARNING: --filter_FP is not applied on the N-rank path (-p N / --gpus N): the transcripts are NOT filtered; run with one "
+            "process for the filter")
     ctx = device.Context(dev_index)
     T = {}
     t0 = time.time()
@@ -210,7 +217,13 @@ def rank_main(out_dir, reads, K, partition_size, min_weight, min_length, double_
     return rc
 
 
-def main(argv):
+class Options(object):
+    """what the command line asked for (parse_args)"""
+
+
+def parse_args(argv):
+    """the flags of argv (argv[0] = the program) -> Options, or the exit code of a run that ends with the parsing (--help,
+    --version, a flag without its value).  Prints the reference's OPTIONS lines; touches neither the GPU nor the file system."""
     K, partition_size, nJobs = 24, 500, 1                     # shannon.py:58,65,67
     out_dir, reads, double_stranded = None, [], True
     min_weight, min_length = 3, 75                            # hyp_min_weight, hyp_min_length: shannon.py:56-57
@@ -219,6 +232,7 @@ def main(argv):
     ignored, noted = [], []
     takes_value = ("-o", "--single", "--left", "--right", "-K", "-p", "--gpus", "--partition", "--kmer_hard_cutoff", "--kmer_soft_cutoff")
     n_gpus = 0
+    filter_fp = False
     while i < len(argv):
         a = argv[i]
         if a in takes_value and i + 1 >= len(argv):
@@ -258,6 +272,11 @@ def main(argv):
             double_stranded = False; i += 1; continue
         if a in ("--inMem", "--fasta", "--fastq"):
             i += 1; continue
+        if a == "--filter_FP":
+            # shannon.py:170-174 (the reference refuses it with --inMem, :195, because it needs the read files; here the reads are resident)
+            if not filter_fp:
+                print("OPTIONS --filter_FP: False-positive filtering enabled")
+            filter_fp = True; i += 1; continue
         if a in ("--inDisk", "--only_reads"):
             noted.append("%s: the stages hand their data over in memory (the reference's --inMem contract); TEMP/ holds the per-stage "
                          "products but not reads{comp}.fasta / component*k1mers_allowed.dict (shannon_amd/reference_api.py writes those "
@@ -266,6 +285,27 @@ def main(argv):
         if a in ("--compare", "--kallisto_cutoff"):
             ignored.append(a); i += 2; continue
         ignored.append(a); i += 1
+    if filter_fp and len(reads) != 2:
+        # run_MB_SF_fn.py:110: `if '--filter_FP' in n_inp and paired_end`
+        noted.append("--filter_FP: single-end input -- the reference applies the filter to paired-end runs only (run_MB_SF_fn.py:110); "
+                     "nothing is filtered")
+        filter_fp = False
+    o = Options()
+    o.K, o.partition_size, o.nJobs, o.n_gpus = K, partition_size, nJobs, n_gpus
+    o.out_dir, o.reads, o.double_stranded = out_dir, reads, double_stranded
+    o.min_weight, o.min_length, o.kmer_hard_cutoff = min_weight, min_length, kmer_hard_cutoff
+    o.ignored, o.noted, o.filter_fp = ignored, noted, filter_fp
+    return o
+
+
+def main(argv):
+    o = parse_args(argv)
+    if isinstance(o, int):
+        return o
+    K, partition_size, nJobs, n_gpus = o.K, o.partition_size, o.nJobs, o.n_gpus
+    out_dir, reads, double_stranded = o.out_dir, o.reads, o.double_stranded
+    min_weight, min_length, kmer_hard_cutoff = o.min_weight, o.min_length, o.kmer_hard_cutoff
+    ignored, noted, filter_fp = o.ignored, o.noted, o.filter_fp
     if out_dir is None or not reads:
         print("ERROR: need -o OUT and --single F or --left F1 --right F2")
         print("Try running python shannon.py --help for a short manual")
@@ -290,7 +330,7 @@ def main(argv):
             if n_gpus > 1:
                 print("NOTE: --gpus %d asked for, the node shows %d GPU(s): one process" % (n_gpus, have))
     if in_rank:
-        return rank_main(out_dir, reads, K, partition_size, min_weight, min_length, double_stranded, ignored, noted, kmer_hard_cutoff)
+        return rank_main(out_dir, reads, K, partition_size, min_weight, min_length, double_stranded, ignored, noted, kmer_hard_cutoff, filter_fp)
     os.makedirs(out_dir, exist_ok=True)
     sample = os.path.basename(os.path.normpath(out_dir))
     temp = os.path.join(out_dir, "TEMP")
@@ -346,11 +386,12 @@ def main(argv):
         from shannon_amd import kmers_for_component as kfc
         R = pipeline.assemble_resident(ctx, sets[0], sets[1] if paired else None, kfc.ReadStore(r[0], r[1] if paired else None), K=K,
                                        partition_size=partition_size, min_weight=min_weight, min_length=min_length, sample=sample, seed=0,
-                                       double_stranded=double_stranded, timings=T, kmer_hard_cutoff=kmer_hard_cutoff)
+                                       double_stranded=double_stranded, timings=T, kmer_hard_cutoff=kmer_hard_cutoff,
+                                       filter_fp=filter_fp)
     else:
         R = pipeline.assemble(ctx, r[0], r[1] if paired else None, K=K, partition_size=partition_size, min_weight=min_weight,
                               min_length=min_length, sample=sample, seed=0, double_stranded=double_stranded, timings=T,
-                              kmer_hard_cutoff=kmer_hard_cutoff)
+                              kmer_hard_cutoff=kmer_hard_cutoff, filter_fp=filter_fp)
     say("%d K-mers loaded; %d contigs; %d partitions" % (R.n_k1mers, len(R.extension.contigs), len(R.partitions)))
     # TEMP tree: the per-stage products of the reference (shannon.py:496-513, 584-595)
     from shannon_amd import extension_correction as ec, mbgraph
@@ -363,7 +404,18 @@ def main(argv):
             os.makedirs(base + sub)
         mbgraph.write_files(p["singles"], p["components"], base + "intermediate")
         open(os.path.join(base + "algo_output", "reconstructed.fasta"), "w").write(p["reconstructed_fasta"])
+        if "filter_log" in p:
+            # filter_FP.py:52-55: the filtered transcripts take the place of reconstructed.fasta, the sparse flow's stay beside them
+            open(os.path.join(base + "algo_output", "reconstructed_org.fasta"), "w").write(p["reconstructed_org_fasta"])
+            open(os.path.join(base + "algo_output", "rec.log"), "w").write(p["filter_log"])
+            say("%s has completed: %d transcripts, %d after --filter_FP" % (base, p["reconstructed_org_fasta"].count(">"),
+                                                                           p["reconstructed_fasta"].count(">")))
+            continue
         say("%s has completed: %d transcripts" % (base, p["reconstructed_fasta"].count(">")))
+    if filter_fp:
+        st = getattr(R, "filter_fp_stats", {})
+        say("--filter_FP: %d of %d routed fragments placed as concordant pairs; %d of %d transcripts kept"
+            % (st.get("placed", 0), st.get("routes", 0), st.get("kept", 0), st.get("transcripts", 0)))
     alld = os.path.join(temp, sample + "_allalgo_output")
     os.makedirs(alld)
     open(os.path.join(alld, "all_reconstructed.fasta"), "w").write("".join(R.all_reconstructed))

@@ -1,0 +1,458 @@
+// --filter_FP on the device: how many bases of every transcript the read pairs routed to its partition cover
+// (filter_FP.py:29-55 as run_MB_SF_fn.py:272-277 runs it per partition; here all partitions in one call).  hisat + samtools
+// are replaced by the rule of DESIGN.md ("filter_FP"); the kernels below state the part of it they implement.
+//
+//   index   all transcripts packed 2 bits a base into one text; one record per 15-mer position that lies inside a transcript,
+//           key = partition << 30 | 15-mer, value = position in the text, sorted by key (shn_sort_pairs, stable: equal keys
+//           stay in text order).  A partition's pairs only ever meet the 15-mers of their own partition.
+//   map     one thread per route.  A mate of L >= 15 bases may carry L / 30 mismatches and holds L / 30 + 1 disjoint 15-base
+//           seeds (at 0, 15, 30, ...): one of them is free of mismatches (pigeonhole), so the exact hits of the seeds name
+//           every start the rule admits.  A start reached through seed s is taken up only if no earlier seed matches there
+//           too (de-duplication without a candidate store); verification is XOR + popcount of 64-bit words against the text.
+//           Two passes over the same enumeration: the fragment's minimum cost, then every placement that attains it is marked.
+//           Nothing is stored per fragment, so nothing is capped.
+//   mark    one bit per base of the text.  The word is loaded first and the atomic OR is issued only when it would set a new
+//           bit: a highly expressed transcript is covered within its first few thousand fragments and every later one then
+//           costs loads only.  (The rate of scattered 64-bit integer ORs on this chip is not measured anywhere in this
+//           repository; the load-first form is what keeps the kernel from depending on it.)
+//   count   bits set inside every transcript's range.
+//
+// The thread-per-route shape trades lane divergence (mates differ in how many candidates their seeds name) for having no
+// intermediate candidate lists at all; DESIGN.md gives the measured time next to the byte models below.
+#include "common.h"
+
+#define FFP_SEED SHN_FILTER_FP_SEED
+#define FFP_NONE 0xFFFFFFFFu
+#define FFP_BLOCK 256
+#define FFP_YSEEDS 9
+
+struct shn_routes;
+int shn_routes_device_arrays(const shn_routes* r, const uint32_t** pid, const uint32_t** ridx, uint64_t* n);   // route.hip
+
+// a read set as the mapping sees it: the set as packed by shn_reads_create / shn_reads_ingest and its reverse complement in the
+// same geometry (every read in its own words, so RC(read i) lies where read i lies)
+struct FfpSet {
+  const uint64_t *words, *mask, *words_rc, *mask_rc, *woff;
+  const uint32_t* len;
+  const uint8_t* bad;          // NULL: no read of the set holds a non-ACGT base
+  uint32_t fixed_len, wpr;
+};
+struct FfpRead { const uint64_t* w; const uint64_t* m; uint32_t L; bool bad; };
+
+struct FfpIndex {
+  const uint64_t* keys; const uint32_t* vals; uint64_t n_rec;
+  const uint64_t* tw;          // the text, 32 bases a word, first base in the top bits; two zero words behind the end
+  const uint64_t* t_off; uint64_t n_tr;
+};
+
+__device__ __forceinline__ FfpRead ffp_read(const FfpSet& S, uint64_t i, bool rc) {
+  FfpRead r;
+  const uint64_t wb = S.woff ? S.woff[i] : i * (uint64_t)S.wpr;
+  r.L = S.len ? S.len[i] : S.fixed_len;
+  r.w = (rc ? S.words_rc : S.words) + wb;
+  r.bad = S.bad != nullptr && S.bad[i] != 0;
+  r.m = r.bad ? (rc ? S.mask_rc : S.mask) + wb / 2 : nullptr;
+  return r;
+}
+
+// 32 bases of the text from base g on (the words behind the text's end are zero)
+__device__ __forceinline__ uint64_t ffp_text32(const uint64_t* __restrict__ tw, uint64_t g) {
+  const uint64_t wi = g >> 5;
+  const uint32_t sh = (uint32_t)(g & 31) * 2;
+  uint64_t v = tw[wi] << sh;
+  if (sh) v |= tw[wi + 1] >> (64 - sh);
+  return v;
+}
+__device__ __forceinline__ uint64_t ffp_text_seed(const uint64_t* __restrict__ tw, uint64_t g) {
+  return ffp_text32(tw, g) >> (64 - 2 * FFP_SEED);
+}
+
+// bit i of a 32-bit word -> bit 2 i (the N mask of 32 bases onto the low bits of their 2-bit fields)
+__device__ __forceinline__ uint64_t ffp_spread(uint32_t n) {
+  uint64_t x = n;
+  x = (x | (x << 16)) & 0x0000FFFF0000FFFFULL;
+  x = (x | (x << 8)) & 0x00FF00FF00FF00FFULL;
+  x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0FULL;
+  x = (x | (x << 2)) & 0x3333333333333333ULL;
+  x = (x | (x << 1)) & 0x5555555555555555ULL;
+  return x;
+}
+
+// Hamming distance between the read and the text at u (a non-ACGT base of the read is a mismatch); gives up above thr
+__device__ __forceinline__ uint32_t ffp_hamming(const FfpRead& x, const uint64_t* __restrict__ tw, uint64_t u, uint32_t thr) {
+  uint32_t mm = 0;
+  const uint32_t nw = (x.L + 31) >> 5;
+  for (uint32_t k = 0; k < nw; k++) {
+    uint64_t d = x.w[k] ^ ffp_text32(tw, u + 32ull * k);
+    d = (d | (d >> 1)) & 0x5555555555555555ULL;
+    if (x.bad) {
+      const uint64_t m = x.m[k >> 1];
+      d |= ffp_spread((k & 1) ? (uint32_t)m : (uint32_t)(m >> 32));
+    }
+    const uint32_t rem = x.L - 32 * k;
+    if (rem < 32) d &= ~0ULL << (64 - 2 * rem);
+    mm += (uint32_t)__popcll(d);
+    if (mm > thr) return mm;
+  }
+  return mm;
+}
+
+__device__ __forceinline__ bool ffp_seed_of(const FfpRead& x, uint32_t s, uint64_t* seed) {
+  if (x.bad && shn_extract_mask(x.m, s * FFP_SEED, FFP_SEED)) return false;
+  *seed = shn_extract(x.w, s * FFP_SEED, FFP_SEED);
+  return true;
+}
+
+// does a seed before s match the text exactly when the read starts at u?  (then that seed has named this start already)
+__device__ __forceinline__ bool ffp_named_before(const FfpRead& x, const uint64_t* __restrict__ tw, uint64_t u, uint32_t s) {
+  for (uint32_t e = 0; e < s; e++) {
+    uint64_t seed;
+    if (ffp_seed_of(x, e, &seed) && ffp_text_seed(tw, u + (uint64_t)e * FFP_SEED) == seed) return true;
+  }
+  return false;
+}
+
+__device__ __forceinline__ uint64_t ffp_lower(const FfpIndex& I, uint64_t key) {
+  uint64_t lo = 0, hi = I.n_rec;
+  while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (I.keys[mid] < key) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+// transcript that holds base g of the text (empty transcripts hold none)
+__device__ __forceinline__ uint64_t ffp_transcript_of(const FfpIndex& I, uint64_t g) {
+  uint64_t lo = 0, hi = I.n_tr;               // largest j with t_off[j] <= g
+  while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (I.t_off[mid] <= g) lo = mid; else hi = mid; }
+  return lo;
+}
+
+__device__ __forceinline__ void ffp_mark(unsigned long long* __restrict__ cov, uint64_t g0, uint32_t len) {
+  const uint64_t g1 = g0 + len;
+  for (uint64_t w = g0 >> 6; w <= (g1 - 1) >> 6; w++) {
+    const uint64_t b0 = w << 6;
+    const uint32_t lo = (uint32_t)((g0 > b0 ? g0 : b0) - b0), hi = (uint32_t)((g1 < b0 + 64 ? g1 : b0 + 64) - b0);
+    const unsigned long long m = (hi - lo == 64 ? ~0ULL : ((1ULL << (hi - lo)) - 1ULL)) << lo;
+    if (~cov[w] & m) atomicOr(&cov[w], m);
+  }
+}
+
+// Every concordant placement of the oriented pair (x, y) in the partition whose key prefix is pkey: x at u, y at v on the same
+// transcript, u <= v, u + |x| <= v + |y|, v + |y| - u <= max_span, each mate within its mismatch bound.  MARK == false: *best
+// becomes the smallest cost seen; MARK == true: the placements of cost *best are marked.
+template <bool MARK>
+__device__ void ffp_pairs(const FfpIndex& I, uint64_t pkey, const FfpRead& x, const FfpRead& y, uint32_t max_span, uint32_t* best,
+                          unsigned long long* __restrict__ cov) {
+  if (x.L < FFP_SEED || y.L < FFP_SEED) return;
+  const uint32_t thrx = x.L / 30, thry = y.L / 30;
+  uint32_t ylo[FFP_YSEEDS];                              // first index record of the second mate's seeds (reads up to 269 bases: all of them)
+  bool have_y = false;
+  for (uint32_t s = 0; s <= thrx; s++) {
+    uint64_t seed;
+    if (!ffp_seed_of(x, s, &seed)) continue;
+    const uint64_t key = pkey | seed;
+    for (uint64_t r = ffp_lower(I, key); r < I.n_rec && I.keys[r] == key; r++) {
+      const uint64_t g = I.vals[r];
+      const uint64_t j = ffp_transcript_of(I, g);
+      const uint64_t a = I.t_off[j], b = I.t_off[j + 1];
+      if (g < a + (uint64_t)s * FFP_SEED) continue;
+      const uint64_t u = g - (uint64_t)s * FFP_SEED;
+      if (u + x.L > b || ffp_named_before(x, I.tw, u, s)) continue;
+      const uint32_t cx = ffp_hamming(x, I.tw, u, thrx);
+      if (cx > thrx || (MARK ? cx > *best : cx >= *best)) continue;
+      if (!have_y) {                                     // (the first verified first mate: where the second mate's seeds start in the index)
+        for (uint32_t t = 0; t <= thry && t < FFP_YSEEDS; t++) {
+          uint64_t seed_y;
+          ylo[t] = ffp_seed_of(y, t, &seed_y) ? (uint32_t)ffp_lower(I, pkey | seed_y) : FFP_NONE;
+        }
+        have_y = true;
+      }
+      for (uint32_t t = 0; t <= thry; t++) {
+        uint64_t seed_y;
+        if (!ffp_seed_of(y, t, &seed_y)) continue;
+        const uint64_t key_y = pkey | seed_y;
+        for (uint64_t q = t < FFP_YSEEDS ? ylo[t] : ffp_lower(I, key_y); q < I.n_rec && I.keys[q] == key_y; q++) {
+          const uint64_t gy = I.vals[q];
+          if (gy < a + (uint64_t)t * FFP_SEED || gy >= b) continue;                 // (another transcript, or y would start before this one)
+          const uint64_t v = gy - (uint64_t)t * FFP_SEED;
+          if (v + y.L > b || v < u || u + x.L > v + y.L || v + y.L - u > max_span) continue;
+          if (ffp_named_before(y, I.tw, v, t)) continue;
+          const uint32_t cy = ffp_hamming(y, I.tw, v, thry);
+          if (cy > thry) continue;
+          const uint32_t c = cx + cy;
+          if (!MARK) { if (c < *best) *best = c; }
+          else if (c == *best) { ffp_mark(cov, u, x.L); ffp_mark(cov, v, y.L); }
+        }
+      }
+    }
+  }
+}
+
+// One route a thread: fragment i = the route's read index (strand-specific) or index mod n_pairs (strand-doubled numbering);
+// oriented pairs (r1[i], RC(r2[i])) and -- not strand-specific -- (r2[i], RC(r1[i])).
+__global__ __launch_bounds__(FFP_BLOCK) void ffp_map_kernel(FfpIndex I, FfpSet A, FfpSet B, uint64_t n_pairs, const uint32_t* __restrict__ pid,
+                                                            const uint32_t* __restrict__ ridx, uint64_t n_routes, uint32_t n_parts, int ss,
+                                                            uint32_t max_span, unsigned long long* __restrict__ cov,
+                                                            unsigned long long* __restrict__ n_placed) {
+  const uint64_t r = (uint64_t)blockIdx.x * FFP_BLOCK + threadIdx.x;
+  bool placed = false;
+  if (r < n_routes) {
+    const uint32_t p = pid[r];
+    uint64_t i = ridx[r];
+    if (!ss && i >= n_pairs) i -= n_pairs;
+    if (p < n_parts && i < n_pairs) {
+      const uint64_t pkey = (uint64_t)p << (2 * FFP_SEED);
+      const FfpRead a = ffp_read(A, i, false), b_rc = ffp_read(B, i, true);
+      uint32_t best = FFP_NONE;
+      ffp_pairs<false>(I, pkey, a, b_rc, max_span, &best, cov);
+      if (!ss) {
+        const FfpRead b = ffp_read(B, i, false), a_rc = ffp_read(A, i, true);
+        ffp_pairs<false>(I, pkey, b, a_rc, max_span, &best, cov);
+        if (best != FFP_NONE) {
+          ffp_pairs<true>(I, pkey, a, b_rc, max_span, &best, cov);
+          ffp_pairs<true>(I, pkey, b, a_rc, max_span, &best, cov);
+        }
+      } else if (best != FFP_NONE) {
+        ffp_pairs<true>(I, pkey, a, b_rc, max_span, &best, cov);
+      }
+      placed = best != FFP_NONE;
+    }
+  }
+  const unsigned long long vote = __ballot(placed);
+  if ((threadIdx.x & 63) == 0 && vote) atomicAdd(n_placed, (unsigned long long)__popcll(vote));
+}
+
+// ASCII -> 2 bits a base, one word a thread; a base outside ACGT raises *bad
+__global__ void ffp_pack_text_kernel(const uint8_t* __restrict__ text, uint64_t n, uint64_t* __restrict__ tw, uint32_t* __restrict__ bad) {
+  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w * 32 >= n) return;
+  uint64_t v = 0;
+  bool any_bad = false;
+  for (uint32_t j = 0; j < 32; j++) {
+    const uint64_t g = w * 32 + j;
+    uint64_t c = 0;
+    if (g < n) {
+      switch (text[g]) {
+        case 'A': case 'a': c = 0; break;
+        case 'C': case 'c': c = 1; break;
+        case 'G': case 'g': c = 2; break;
+        case 'T': case 't': c = 3; break;
+        default: any_bad = true;
+      }
+    }
+    v |= c << (62 - 2 * j);
+  }
+  tw[w] = v;
+  if (any_bad) atomicOr(bad, 1u);
+}
+
+// record r = the r-th 15-mer position inside a transcript (rec_off[j] = records of the transcripts before j)
+__global__ void ffp_records_kernel(const uint64_t* __restrict__ tw, const uint64_t* __restrict__ t_off, const uint64_t* __restrict__ rec_off,
+                                   const uint32_t* __restrict__ t_part, uint64_t n_tr, uint64_t n_rec, uint64_t* __restrict__ keys,
+                                   uint32_t* __restrict__ vals) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rec) return;
+  uint64_t lo = 0, hi = n_tr;                 // largest j with rec_off[j] <= r: the transcript that holds record r
+  while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (rec_off[mid] <= r) lo = mid; else hi = mid; }
+  const uint64_t g = t_off[lo] + (r - rec_off[lo]);
+  keys[r] = ((uint64_t)t_part[lo] << (2 * FFP_SEED)) | ffp_text_seed(tw, g);
+  vals[r] = (uint32_t)g;
+}
+
+// the reverse complement of every read of a set in the set's own geometry: one thread per 64-base group (two words + one mask word)
+__global__ void ffp_revcomp_kernel(const uint64_t* __restrict__ words, const uint64_t* __restrict__ mask, const uint64_t* __restrict__ woff,
+                                   const uint32_t* __restrict__ lens, uint64_t n_reads, uint32_t fixed_len, uint32_t wpr, uint64_t n_groups,
+                                   uint64_t* __restrict__ words_rc, uint64_t* __restrict__ mask_rc) {
+  const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= n_groups) return;
+  uint64_t r, g, wbase;
+  uint32_t len;
+  if (!woff) {
+    const uint32_t gpr = wpr / 2;
+    r = gid / gpr; g = gid % gpr; wbase = r * wpr; len = fixed_len;
+  } else {
+    uint64_t lo = 0, hi = n_reads;            // largest r with woff[r] <= 2 gid
+    while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (woff[mid] <= gid * 2) lo = mid; else hi = mid; }
+    r = lo; wbase = woff[r]; g = (gid * 2 - wbase) / 2; len = lens[r];
+  }
+  const uint64_t* w = words + wbase;
+  const uint64_t* m = mask ? mask + wbase / 2 : nullptr;
+  uint64_t w0 = 0, w1 = 0, mo = 0;
+  for (uint32_t j = 0; j < 64; j++) {
+    const uint64_t p = g * 64 + j;
+    uint64_t c = 0;
+    if (p < len) {
+      const uint32_t q = len - 1 - (uint32_t)p;
+      c = 3 - ((w[q >> 5] >> (62 - 2 * (q & 31))) & 3);
+      if (m && ((m[q >> 6] >> (63 - (q & 63))) & 1)) { mo |= 1ULL << (63 - j); c = 0; }
+    }
+    if (j < 32) w0 |= c << (62 - 2 * j); else w1 |= c << (62 - 2 * (j - 32));
+  }
+  words_rc[wbase + 2 * g] = w0;
+  words_rc[wbase + 2 * g + 1] = w1;
+  if (mask_rc) mask_rc[wbase / 2 + g] = mo;
+}
+
+__global__ void ffp_count_kernel(const unsigned long long* __restrict__ cov, const uint64_t* __restrict__ t_off, uint64_t n_tr,
+                                 uint32_t* __restrict__ hits) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_tr) return;
+  const uint64_t g0 = t_off[j], g1 = t_off[j + 1];
+  uint32_t n = 0;
+  if (g1 > g0) {
+    for (uint64_t w = g0 >> 6; w <= (g1 - 1) >> 6; w++) {
+      const uint64_t b0 = w << 6;
+      const uint32_t lo = (uint32_t)((g0 > b0 ? g0 : b0) - b0), hi = (uint32_t)((g1 < b0 + 64 ? g1 : b0 + 64) - b0);
+      const unsigned long long m = (hi - lo == 64 ? ~0ULL : ((1ULL << (hi - lo)) - 1ULL)) << lo;
+      n += (uint32_t)__popcll(cov[w] & m);
+    }
+  }
+  hits[j] = n;
+}
+
+static int ffp_set(shn_ctx* ctx, ShnDevBufs& bufs, const shn_reads* r, bool want_rc, FfpSet* out, uint64_t* rc_bytes) {
+  hipStream_t s = ctx->stream;
+  const bool use_mask = r->n_invalid != 0 && r->d_mask && r->d_bad;
+  FfpSet S;
+  S.words = r->d_words; S.mask = use_mask ? r->d_mask : nullptr; S.words_rc = nullptr; S.mask_rc = nullptr;
+  S.woff = r->fixed_len ? nullptr : r->d_woff; S.len = r->fixed_len ? nullptr : r->d_len; S.bad = use_mask ? r->d_bad : nullptr;
+  S.fixed_len = r->fixed_len; S.wpr = r->wpr;
+  if (want_rc && r->n_words) {
+    uint64_t *wrc = nullptr, *mrc = nullptr;
+    HIP_TRY(bufs.get(&wrc, (r->n_words + 2) * 8));
+    HIP_TRY(hipMemsetAsync(wrc + r->n_words, 0, 16, s));
+    if (use_mask) {
+      HIP_TRY(bufs.get(&mrc, (r->n_words / 2 + 2) * 8));
+      HIP_TRY(hipMemsetAsync(mrc + r->n_words / 2, 0, 16, s));
+    }
+    const uint64_t n_groups = r->n_words / 2;
+    hipLaunchKernelGGL(ffp_revcomp_kernel, dim3((uint32_t)cdiv(n_groups, 256)), dim3(256), 0, s, S.words, S.mask, S.woff, S.len, r->n_reads,
+                       r->fixed_len, r->wpr, n_groups, wrc, mrc);
+    S.words_rc = wrc; S.mask_rc = mrc;
+    *rc_bytes += r->n_words * 16 + (use_mask ? r->n_words * 8 : 0);          // the set read once, its reverse complement written once
+  }
+  *out = S;
+  return SHN_OK;
+}
+
+extern "C" int shn_filter_fp_hits(shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off, const uint32_t* t_part, uint64_t n_tr,
+                                  uint32_t n_parts, const shn_reads* r1, const shn_reads* r2, const shn_routes* routes, const uint32_t* h_pid,
+                                  const uint32_t* h_frag, uint64_t n_host, int strand_specific, uint32_t max_span, uint32_t* hits,
+                                  uint64_t* stats) {
+  if (!ctx || !r1 || !r2 || !t_off || (n_tr && (!text || !t_part || !hits)))
+    return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: NULL argument");
+  if (!routes && n_host && (!h_pid || !h_frag)) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: routes neither on the device nor on the host");
+  if (r1->n_reads != r2->n_reads) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: the two read sets are not mates of each other (different sizes)");
+  if (n_parts >= (1u << 31)) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: too many partitions");
+  const uint64_t n_pairs = r1->n_reads;
+  const uint64_t total = t_off[n_tr];
+  if (t_off[0] != 0) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: t_off[0] is not 0");
+  if (total >= 0xFFFFFF00ULL) return shn_fail(SHN_ERR_OVERFLOW, "shn_filter_fp_hits: more than 2^32 transcript bases in one call");
+  std::vector<uint64_t> rec_off(n_tr + 1, 0);
+  for (uint64_t j = 0; j < n_tr; j++) {
+    if (t_off[j + 1] < t_off[j]) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: t_off not monotone");
+    if (t_part[j] >= n_parts) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: partition of a transcript out of range");
+    const uint64_t len = t_off[j + 1] - t_off[j];
+    rec_off[j + 1] = rec_off[j] + (len >= FFP_SEED ? len - FFP_SEED + 1 : 0);
+  }
+  const uint64_t n_rec = rec_off[n_tr];
+  if (!routes)
+    for (uint64_t i = 0; i < n_host; i++)
+      if (h_pid[i] >= n_parts || h_frag[i] >= (strand_specific ? n_pairs : 2 * n_pairs))
+        return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: a route names a partition or a fragment that does not exist");
+  SHN_ENTER(ctx);
+  shn_stage_begin(ctx);
+  hipStream_t s = ctx->stream;
+  ShnDevBufs bufs(s);
+
+  const uint32_t *d_pid = nullptr, *d_ridx = nullptr;
+  uint64_t n_routes = 0;
+  if (routes) {
+    int rc = shn_routes_device_arrays(routes, &d_pid, &d_ridx, &n_routes);
+    if (rc) return rc;
+  } else if (n_host) {
+    uint32_t *p = nullptr, *f = nullptr;
+    HIP_TRY(bufs.get(&p, n_host * 4));
+    HIP_TRY(bufs.get(&f, n_host * 4));
+    HIP_TRY(hipMemcpyAsync(p, h_pid, n_host * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(f, h_frag, n_host * 4, hipMemcpyHostToDevice, s));
+    d_pid = p; d_ridx = f; n_routes = n_host;
+  }
+  if (stats) { stats[0] = n_routes; stats[1] = 0; }
+  if (n_tr == 0) { HIP_TRY(hipStreamSynchronize(s)); return SHN_OK; }
+
+  // ---- index
+  const uint64_t n_tw = cdiv(total, 32);
+  uint8_t* d_text = nullptr;
+  uint64_t *d_tw = nullptr, *d_toff = nullptr, *d_roff = nullptr, *d_keys = nullptr, *d_keys_tmp = nullptr;
+  uint32_t *d_tpart = nullptr, *d_vals = nullptr, *d_vals_tmp = nullptr, *d_flag = nullptr, *d_hits = nullptr;
+  unsigned long long *d_cov = nullptr, *d_placed = nullptr;
+  HIP_TRY(bufs.get(&d_text, total + 1));
+  HIP_TRY(bufs.get(&d_tw, (n_tw + 2) * 8));
+  HIP_TRY(bufs.get(&d_toff, (n_tr + 1) * 8));
+  HIP_TRY(bufs.get(&d_roff, (n_tr + 1) * 8));
+  HIP_TRY(bufs.get(&d_tpart, n_tr * 4));
+  HIP_TRY(bufs.get(&d_flag, 4));
+  HIP_TRY(bufs.get(&d_keys, (n_rec + 1) * 8));
+  HIP_TRY(bufs.get(&d_keys_tmp, (n_rec + 1) * 8));
+  HIP_TRY(bufs.get(&d_vals, (n_rec + 1) * 4));
+  HIP_TRY(bufs.get(&d_vals_tmp, (n_rec + 1) * 4));
+  HIP_TRY(hipMemcpyAsync(d_text, text, total, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_toff, t_off, (n_tr + 1) * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_roff, rec_off.data(), (n_tr + 1) * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_tpart, t_part, n_tr * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(d_flag, 0, 4, s));
+  HIP_TRY(hipMemsetAsync(d_tw + n_tw, 0, 16, s));
+  {
+    int key_bits = 2 * FFP_SEED;
+    while (key_bits < 62 && ((uint64_t)n_parts >> (key_bits - 2 * FFP_SEED))) key_bits++;
+    const uint64_t passes = (uint64_t)(key_bits + 7) / 8;
+    TimerRegion treg(ctx, T_FFP_INDEX);
+    // bytes: the text read and written packed (1.25 B a base), a record written (12 B), every sort pass reads and writes the records
+    treg.bytes(total + total / 4 + n_rec * 12 + passes * n_rec * 24);
+    if (n_tw) hipLaunchKernelGGL(ffp_pack_text_kernel, dim3((uint32_t)cdiv(n_tw, 256)), dim3(256), 0, s, d_text, total, d_tw, d_flag);
+    if (n_rec) {
+      hipLaunchKernelGGL(ffp_records_kernel, dim3((uint32_t)cdiv(n_rec, 256)), dim3(256), 0, s, d_tw, d_toff, d_roff, d_tpart, n_tr, n_rec, d_keys, d_vals);
+      int rc = shn_sort_pairs(ctx, d_keys, d_vals, d_keys_tmp, d_vals_tmp, n_rec, 0, key_bits);
+      if (rc) return rc;
+    }
+  }
+  uint32_t flag = 0;
+  HIP_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (flag) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: a transcript holds a base outside ACGT");
+
+  // ---- map + mark
+  const uint64_t n_cov = cdiv(total, 64) + 1;
+  HIP_TRY(bufs.get(&d_cov, n_cov * 8));
+  HIP_TRY(bufs.get(&d_placed, 8));
+  HIP_TRY(bufs.get(&d_hits, n_tr * 4));
+  HIP_TRY(hipMemsetAsync(d_cov, 0, n_cov * 8, s));
+  HIP_TRY(hipMemsetAsync(d_placed, 0, 8, s));
+  if (n_routes && n_rec) {
+    FfpSet A, B;
+    uint64_t rc_bytes = 0;
+    TimerRegion treg(ctx, T_FFP_MAP);
+    int rc = ffp_set(ctx, bufs, r1, !strand_specific, &A, &rc_bytes);
+    if (!rc) rc = ffp_set(ctx, bufs, r2, true, &B, &rc_bytes);
+    if (rc) return rc;
+    FfpIndex I;
+    I.keys = d_keys; I.vals = d_vals; I.n_rec = n_rec; I.tw = d_tw; I.t_off = d_toff; I.n_tr = n_tr;
+    // bytes: a route (8 B) and both mates of its fragment in each orientation used (2 bits a base); the index, the text and the
+    // bitmap are re-read from the caches and priced once; what the reverse complements cost is added above
+    const uint64_t per_pair = n_pairs ? (r1->n_words + r2->n_words) * 8 / n_pairs : 0;
+    treg.bytes(rc_bytes + n_routes * (8 + per_pair * (strand_specific ? 1 : 2)) + n_rec * 12 + n_tw * 8 + n_cov * 8);
+    hipLaunchKernelGGL(ffp_map_kernel, dim3((uint32_t)cdiv(n_routes, FFP_BLOCK)), dim3(FFP_BLOCK), 0, s, I, A, B, n_pairs, d_pid, d_ridx, n_routes,
+                       n_parts, strand_specific ? 1 : 0, max_span, d_cov, d_placed);
+  }
+  // ---- count
+  {
+    TimerRegion treg(ctx, T_FFP_COUNT);
+    treg.bytes(n_cov * 8 + n_tr * 20);          // the bitmap, two offsets read and a count written per transcript
+    hipLaunchKernelGGL(ffp_count_kernel, dim3((uint32_t)cdiv(n_tr, 256)), dim3(256), 0, s, d_cov, d_toff, n_tr, d_hits);
+  }
+  unsigned long long placed = 0;
+  HIP_TRY(hipMemcpyAsync(hits, d_hits, n_tr * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&placed, d_placed, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipGetLastError());
+  if (stats) stats[1] = placed;
+  return SHN_OK;
+}

@@ -236,6 +236,13 @@ int shn_routes_device_slice(const shn_routes* r, uint64_t lo, uint64_t n, const 
   return SHN_OK;
 }
 
+// (internal, filter_fp.hip) both columns of the routes where they lie on the device
+int shn_routes_device_arrays(const shn_routes* r, const uint32_t** pid, const uint32_t** ridx, uint64_t* n) {
+  if (!r || !pid || !ridx || !n) return shn_fail(SHN_ERR_ARG, "shn_routes_device_arrays: NULL argument");
+  *pid = r->d_pid; *ridx = r->d_ridx; *n = r->n;
+  return SHN_OK;
+}
+
 extern "C" void shn_routes_destroy(shn_routes* r) {
   if (!r) return;
   hipSetDevice(r->device);

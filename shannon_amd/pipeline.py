@@ -71,10 +71,11 @@ def n_kmer_nodes(rows, K):
 
 def assemble(ctx, reads1, reads2=None, K=25, partition_size=500, min_weight=3, min_length=75, overload=2, penalty=5,
              sample="shannon", seed=0, double_stranded=True, part_vectors=None, timings=None, hits_factory=None,
-             native_graph=True, kmer_hard_cutoff=1):
+             native_graph=True, kmer_hard_cutoff=1, filter_fp=False):
     """reads1/reads2: lists of strings or uint8 code matrices (reads2 None = single-end).
     min_weight = the reference's hyp_min_weight (--kmer_soft_cutoff, shannon.py:243-247, 457); kmer_hard_cutoff = its
-    jellyfish_kmer_cutoff (--kmer_hard_cutoff, `jellyfish dump -L`, shannon.py:237-241, 441).
+    jellyfish_kmer_cutoff (--kmer_hard_cutoff, `jellyfish dump -L`, shannon.py:237-241, 441).  filter_fp: --filter_FP, see
+    assemble_resident.
     Returns Result with .partitions {name: dict}, .all_reconstructed (lines), .final {name: seq}."""
     T = timings if timings is not None else {}
     paired = reads2 is not None
@@ -89,17 +90,21 @@ def assemble(ctx, reads1, reads2=None, K=25, partition_size=500, min_weight=3, m
     store = kfc.ReadStore(reads1, reads2)
     tick("upload+pack", t0)
     return assemble_resident(ctx, d1, d2, store, K, partition_size, min_weight, min_length, overload, penalty, sample, seed,
-                             double_stranded, part_vectors, T, hits_factory, native_graph, kmer_hard_cutoff=kmer_hard_cutoff)
+                             double_stranded, part_vectors, T, hits_factory, native_graph, kmer_hard_cutoff=kmer_hard_cutoff, filter_fp=filter_fp)
 
 
 def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3, min_length=75, overload=2, penalty=5,
                       sample="shannon", seed=0, double_stranded=True, part_vectors=None, timings=None, hits_factory=None,
-                      native_graph=True, graph_threads=None, keep_partitioning=False, defer_back=False, kmer_hard_cutoff=1):
+                      native_graph=True, graph_threads=None, keep_partitioning=False, defer_back=False, kmer_hard_cutoff=1, filter_fp=False):
     """Same as assemble() with the reads already packed in HBM (d1/d2: device.Reads).  graph_threads: partitions whose
     graph stage may run concurrently on host threads.  keep_partitioning: leave the partition stage's tables (partition ->
     contigs, routed read indices) on the result as `.partitioning` (tests/test_fullsize_gpu.py reads them).  defer_back: run count,
     extension, partitioning / routing and the unitig batch now and return a function that does the rest (see `back`);
-    defer_back="early": only count and extension now, partitioning / routing / unitigs with the rest (see `middle`)."""
+    defer_back="early": only count and extension now, partitioning / routing / unitigs with the rest (see `middle`).
+    filter_fp: --filter_FP (shannon.py:170-195, run_MB_SF_fn.py:110, 272-277) -- once the last sparse flow is done, every partition's
+    transcripts are held against the read pairs routed to it in one device call (filter_fp.filter_texts) and the merge gets the
+    texts without the transcripts the pairs do not cover; a record then holds reconstructed_fasta (filtered), reconstructed_org_fasta
+    and filter_log.  Paired-end input only, as in the reference (single-end: R.filter_fp_note says so, nothing is filtered)."""
     # double_stranded=False: -s / --ss / --strand_specific.  shannon.py:394-424 then leaves single-end reads as they are and
     # reverse-complements the second mates, without doubling; from :427 on double_stranded is False in BOTH modes, so only the read
     # set differs: forward counting (d2: its reverse complements), routes of plain read indices, pairs (R1[i], RC(R2[i])) in the
@@ -224,8 +229,9 @@ def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3
         # ... and the merge takes every text as a piece the moment it exists (post.PostStream: lines, upload, fingerprints beside the
         # graph stage; the order-dependent rules at the end).  Piece 0 = the single contigs, piece 1 + i = partition i.
         pstream, ps_failed, post_futs = None, [], []
+        # (--filter_FP: the merge must not see a text before the filter has; the texts go to it in one piece at the end)
         if (sflow_beside and os.environ.get("SHN_POST_NATIVE", "1") != "0" and os.environ.get("SHN_POST_GPU", "1") != "0" and
-                os.environ.get("SHN_POST_STREAM", "1") != "0"):
+                os.environ.get("SHN_POST_STREAM", "1") != "0" and not filter_fp):
             try:
                 # room for the merge's text on the device: the transcripts are paths through the contigs' graph -- a few times the
                 # accepted contigs' text (both strands, isoforms sharing exons); a text that outgrows it falls back to the one-piece merge
@@ -371,6 +377,37 @@ def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3
             return {"n_reads_routed": len(part["routes"][name]), "n_k1mers": n_rows, "singles": singles, "components": comps,
                     "log": glog}, tt
 
+        def apply_filter_fp(fctx, texts):
+            """--filter_FP over the partitions' texts (in the order of `names` = the partition ids of the routes); sets the three
+            entries of every record and returns the filtered texts"""
+            t0 = time.time()
+            if not paired or d1 is None or d2 is None:
+                R.filter_fp_note = ("--filter_FP: single-end input -- the reference sets the flag only for paired-end runs "
+                                    "(run_MB_SF_fn.py:110); nothing filtered")
+                return texts
+            from . import filter_fp as ffp
+            stats = {}
+            rdev = part.get("routes_dev")
+            if rdev is not None:
+                routes = rdev[0]
+            else:                                   # (routes on the host only: one list of (partition, index) pairs)
+                per = [np.asarray(part["routes"][nm], dtype=np.uint32) for nm in names]
+                routes = (np.repeat(np.arange(len(names), dtype=np.uint32), [len(x) for x in per]),
+                          np.concatenate(per) if per else np.zeros(0, np.uint32))
+            out = ffp.filter_texts(fctx, texts, d1, d2, routes, ss, stats=stats)
+            kept = []
+            for name, org, (txt, log_) in zip(names, texts, out):
+                rec = R.partitions[name]
+                dict.__setitem__(rec, "reconstructed_org_fasta", org if isinstance(org, str) else bytes(org).decode())
+                dict.__setitem__(rec, "reconstructed_fasta", txt)
+                dict.__setitem__(rec, "filter_log", log_)
+                if getattr(rec, "fasta_raw", None) is not None:
+                    rec.fasta_raw = txt.encode()
+                kept.append(txt.encode())
+            R.filter_fp_stats = stats
+            tick("filter_FP", t0)
+            return kept
+
         t_graph = time.time()
         results, futs = [], {}
         try:
@@ -432,6 +469,8 @@ def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3
                 for name, txt in zip(names, texts):
                     R.partitions[name].fasta_raw = txt                 # decoded when somebody reads ["reconstructed_fasta"]
             tick("sparse flow", t0)
+            if filter_fp:
+                texts = apply_filter_fp(ctx_b, texts)
             t0 = time.time()
             R._texts = [single_text] + texts                           # all_reconstructed.fasta: single contigs, then the partitions
             streamed = pstream is not None and not ps_failed and len(pstream.keep) == len(names) + 1
@@ -479,6 +518,11 @@ def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3
             R.partitions[name]["reconstructed_fasta"] = txt
             lines.extend(txt.splitlines(True))
         tick("sparse flow", t0)
+        if filter_fp:
+            apply_filter_fp(ctx_b, [R.partitions[name]["reconstructed_fasta"] for name in names])
+            lines = (single_text if isinstance(single_text, str) else bytes(single_text).decode()).splitlines(True)
+            for name in names:
+                lines.extend(R.partitions[name]["reconstructed_fasta"].splitlines(True))
         t0 = time.time()
         R.all_reconstructed = lines
         R.final = post.finalize(lines, double_stranded)

@@ -7,6 +7,7 @@ modules of the same names:
     multibridging_main(arguments, inMem, contigs, weights, rps)  multibridging.py:327 (`main`)
     algorithm_sf(comp, prefix)                                   algorithm_SF.py:39-63, 858-934 (the script)
     path_decompose(a, b, a_true, b_true, overwrite_norm, P, use_GLPK, sparsity)   path_decompose_sparse.py:15
+    filter_FP(rec_fasta, read_1, read_2, out_dir, flags)         filter_FP.py:29
 
 They read and write the reference's files (k1mer.dict_org / *_contig / component*.txt / remaining_contigs*.txt /
 reads{comp}.fasta / component{comp}k1mers_allowed.dict / nodes, edges, paths{c}.txt / reconstructed*.fasta).  The pipeline
@@ -245,3 +246,56 @@ def path_decompose(a, b, a_true, b_true, overwrite_norm, P, use_GLPK=False, spar
     xs = sparse_flow.solve_batch(ctx, [q], seed)[0]
     ans, non_unique = sparse_flow.finish(q, xs)
     return [np.array(ans, dtype=float).reshape(m, n), non_unique]
+
+
+def _read_records(path):
+    """the sequences of a read file: 2-line / multi-line FASTA or 4-line FASTQ"""
+    with open(path) as f:
+        first = f.readline()
+    if first.startswith("@"):
+        with open(path) as f:
+            lines = f.read().splitlines()
+        return [lines[i + 1].strip() for i in range(0, len(lines) - 1, 4)]
+    return _read_fasta(path)
+
+
+_RC = str.maketrans("ACGTacgt", "TGCAtgca")
+
+
+def filter_FP(rec_fasta, read_1, read_2, out_dir, flags="-f --ff", ctx=None):
+    """filter_FP.py:29-55 for one partition: the pairs of read_1 / read_2 as the files hold them are placed on the transcripts
+    of rec_fasta by the rule of DESIGN.md ("filter_FP"; it stands where hisat-build / hisat --no-spliced-alignment
+    --no-discordant / samtools view -f 0x2 | sort | depth stand in the reference) and write_filtered_tr's products are written:
+    out_dir/reconstructed.fasta (the transcripts with >= 90 % of their bases covered), out_dir/reconstructed_org.fasta (a copy of
+    rec_fasta), out_dir/rec.log (name, hits, length).  No rec.hisat*, .sam, .bam or .depth files.
+    flags: '--ff' (the default, what run_MB_SF_fn.py:277 uses: its read files already hold RC(reads_2), shannon.py:407-411) --
+    both mates are given on the transcript's strand, oriented pair (read_1[i], read_2[i]); '--fr' -- the second mate is given on
+    the other strand, oriented pair (read_1[i], RC(read_2[i])).  '-f' / '-q': the file format is recognised from the files."""
+    from . import filter_fp as ffp
+    ctx = ctx or default_context()
+    with open(rec_fasta) as f:
+        text = f.read()
+    r1, r2 = _read_records(read_1), _read_records(read_2)
+    if len(r1) != len(r2):
+        raise ValueError("filter_FP: %s and %s hold different numbers of reads" % (read_1, read_2))
+    if "--fr" not in flags.split():
+        # the device call takes the second mates as sequenced and reverse-complements them: hand it RC(read_2)
+        r2 = [x[::-1].translate(_RC) for x in r2]
+    names, seqs = ffp.records(text)
+    if r1:
+        d1, d2 = device.Reads.from_strings(ctx, r1), device.Reads.from_strings(ctx, r2)
+        try:
+            routes = (np.zeros(len(r1), np.uint32), np.arange(len(r1), dtype=np.uint32))
+            hits = ffp.coverage_hits(ctx, seqs, [0] * len(seqs), 1, d1, d2, routes, True).tolist()
+        finally:
+            d1.close()
+            d2.close()
+    else:
+        hits = [0] * len(seqs)
+    kept, log = ffp.filter_text(text, hits)
+    with open(os.path.join(out_dir, "reconstructed_org.fasta"), "w") as f:
+        f.write(text)
+    with open(os.path.join(out_dir, "rec.log"), "w") as f:
+        f.write(log)
+    with open(os.path.join(out_dir, "reconstructed.fasta"), "w") as f:
+        f.write(kept)

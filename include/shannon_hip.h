@@ -167,8 +167,6 @@ uint64_t shn_ext_total_steps(const shn_ext* e);   /* walk steps executed over al
 uint64_t shn_ext_wave_steps(const shn_ext* e);    /* ... of which by the wavefront (long-walk) kernel */
 uint64_t shn_ext_fresh_steps(const shn_ext* e);   /* ... of which by the thread walker in the first round of a rank block (the bulk launches) */
 int shn_ext_dense_rounds(const shn_ext* e);       /* rounds whose begin / mark passes streamed every claim (the others followed line flags) */
-uint64_t shn_ext_settled_walks(const shn_ext* e); /* seeds never launched: a lower-ranked k1-mer on a chain of forced links takes them first
-                                                    * (extension_correction.py:223-245, 346: such a seed is always `in traversed`) */
 /* Diagnostics (no counterpart in the reference, whose loop extension_correction.py:334-354 is sequential and deterministic): with
  * SHN_EXT_DIGEST=1 in the environment shn_extend keeps checksums of the arrays of its stages -- out[stage * 64 + chunk], 8 stages
  * (table keys, counts, bucket offsets, weights + flags, adjacency records, seed order, converged claims, walk records) x 64 chunks
@@ -228,8 +226,6 @@ int shn_ext_seed_info(shn_ctx* ctx, const shn_ext* e, const uint32_t* ranks, uin
  *   shn_cc_owners        owner rank of every k1-mer (1 byte each): hash of its label mod world, except the n_big labels listed
  *                        (ascending) with their ranks -- the components the caller balances by size
  *   shn_cc_shard         the shard's (key, count) pairs grouped by owner rank (per_rank[r] each)                               */
-/* diagnostics of the labelling kernel (SHN_CC_DEBUG=1): out4[0] = look-ups that found their key since the last reset                */
-int shn_debug_cc_counters(uint64_t* out4, int reset);
 typedef struct shn_cc shn_cc;
 int shn_cc_create(shn_ctx* ctx, const shn_table* t, int world, int rank, shn_cc** out);
 void shn_cc_destroy(shn_cc* c);

@@ -47,7 +47,6 @@ SIGNATURES = {
     "shn_table_merge_rc": (C.c_int, [vp, vp, vp, vpp]),
     "shn_table_shard": (C.c_int, [vp, vp, C.c_int, u64p, vp, vp]),
     "shn_table_shard_mode": (C.c_int, [vp, vp, C.c_int, C.c_int, u64p, vp, vp]),
-    "shn_debug_cc_counters": (C.c_int, [u64p, C.c_int]),
     "shn_cc_create": (C.c_int, [vp, vp, C.c_int, C.c_int, vpp]),
     "shn_cc_destroy": (None, [vp]),
     "shn_cc_query_counts": (C.c_int, [vp, u64p]),
@@ -131,7 +130,6 @@ SIGNATURES = {
     "shn_ext_total_steps": (C.c_uint64, [vp]),
     "shn_ext_wave_steps": (C.c_uint64, [vp]),
     "shn_ext_dense_rounds": (C.c_int, [vp]),
-    "shn_ext_settled_walks": (C.c_uint64, [vp]),
     "shn_ext_fresh_steps": (C.c_uint64, [vp]),
     "shn_ext_digests": (C.c_int, [vp, vp]),
     "shn_debug_counter": (C.c_uint64, [C.c_int]),

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string>
 #include <vector>
 #include <mutex>
@@ -15,6 +16,24 @@ hipError_t shn_counted_memset(const char* file, int line, void* dst, int value, 
 #define hipMemsetAsync(...) shn_counted_memset(__FILE__, __LINE__, __VA_ARGS__)
 
 #define SHN_WAVE 64
+
+// The one reader of the SHN_* environment switches (README.md has the table; tests/test_switch_table.py checks it against the
+// code).  A call site that must read its switch once per process keeps the result in a function-local static.
+static inline const char* shn_env_str(const char* name) { return getenv(name); }                 // NULL: not set
+static inline bool shn_env_set(const char* name) { return shn_env_str(name) != nullptr; }         // any value, even empty
+// on / off: a switch that is on by default goes off with a value that starts with 0, one that is off goes on with one that starts with 1
+static inline bool shn_env_flag(const char* name, bool dflt) {
+  const char* v = shn_env_str(name);
+  return !v ? dflt : dflt ? v[0] != '0' : v[0] == '1';
+}
+// unsigned decimal number; dflt (as it is) when the switch is not set, else the value held inside [lo, hi]
+static inline uint64_t shn_env_u64(const char* name, uint64_t dflt, uint64_t lo = 0, uint64_t hi = ~0ULL) {
+  const char* v = shn_env_str(name);
+  if (!v) return dflt;
+  const uint64_t x = strtoull(v, nullptr, 10);
+  return x < lo ? lo : x > hi ? hi : x;
+}
+static inline double shn_env_double(const char* name, double dflt) { const char* v = shn_env_str(name); return v ? atof(v) : dflt; }
 
 void shn_set_error(const std::string& msg);
 int shn_fail(int code, const std::string& msg);

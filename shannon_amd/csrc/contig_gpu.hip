@@ -421,7 +421,7 @@ static int contig_stage_impl(shn_ctx* ctx, const uint8_t* bases, const uint8_t* 
   if (!ctx || !out || k1 < 2 || k1 > 33 || r < 1 || r > 32 || (n_cand && ((!bases && !dev_text) || !off || !accepted_out)))
     return shn_fail(SHN_ERR_ARG, "shn_contig_stage: bad argument");
   *out = nullptr;
-  const bool dbg = getenv("SHN_DEBUG") != nullptr;
+  const bool dbg = shn_env_set("SHN_DEBUG");
   auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t0 = now();
   auto lap = [&](const char* what) { if (dbg) { double t = now(); fprintf(stderr, "[contig_stage] %-34s %8.3f s\n", what, t - t0); t0 = t; } };
@@ -470,9 +470,9 @@ static int contig_stage_impl(shn_ctx* ctx, const uint8_t* bases, const uint8_t* 
     ShnDevBufs tmp(s);
     uint64_t* keys = nullptr; uint32_t* vals = nullptr; uint64_t* words = nullptr; uint64_t nv = 0;
     int rc;
-    const bool shared_only = !(getenv("SHN_CONTIG_SHARED") && getenv("SHN_CONTIG_SHARED")[0] == '0');
+    const bool shared_only = shn_env_flag("SHN_CONTIG_SHARED", true);
     // (r <= 16: the r-mer and the 32-bit base index of its window share one word through the sort; SHN_CONTIG_PACKED=0: pairs)
-    const bool packed = r <= 16 && shared_only && !(getenv("SHN_CONTIG_PACKED") && getenv("SHN_CONTIG_PACKED")[0] == '0');
+    const bool packed = r <= 16 && shared_only && shn_env_flag("SHN_CONTIG_PACKED", true);
     { TimerRegion ts(ctx, T_CG_SORT);
       rc = packed ? sorted_windows_packed(ctx, tmp, d_bases, d_off, d_cid, total, r, &words, &nv)
                   : shn_sorted_windows(ctx, tmp, d_bases, d_off, d_cid, nullptr, total, r, &keys, &vals, &nv);
@@ -516,12 +516,12 @@ static int contig_stage_impl(shn_ctx* ctx, const uint8_t* bases, const uint8_t* 
     HIP_TRY(tmp.get(&d_aval, (nv + 1) * 4));
     HIP_TRY(tmp.get(&d_aff, n_cand + 1)); HIP_TRY(tmp.get(&d_chgf, n_cand + 1));
     HIP_TRY(hipMemsetAsync(d_chgf, 0, n_cand + 1, s));
-    const bool incremental = !getenv("SHN_CONTIG_INCREMENTAL") || atoi(getenv("SHN_CONTIG_INCREMENTAL")) != 0;
+    const bool incremental = shn_env_u64("SHN_CONTIG_INCREMENTAL", 1) != 0;
     HIP_TRY(hipMemsetAsync(d_acc, 0, n_cand + 1, s));
     HIP_TRY(hipMemsetAsync(d_bestc, 0, (n_cand + 1) * 4, s));
     if (nv) hipLaunchKernelGGL(cg_scid_kernel, dim3(grid_for(nv)), dim3(CG_BLK), 0, s, vals, d_cid, nv, d_scid);
     // rounds that re-evaluate few candidates go candidate by candidate (cg_*_list_kernel): base of a window -> its sorted entry
-    const uint64_t list_max = getenv("SHN_CONTIG_LIST_MAX") ? strtoull(getenv("SHN_CONTIG_LIST_MAX"), nullptr, 10) : 20000;      // decisions changed in the round before (0: never)
+    const uint64_t list_max = shn_env_u64("SHN_CONTIG_LIST_MAX", 20000);      // decisions changed in the round before (0: never)
     uint32_t *d_pos_of = nullptr, *d_clist = nullptr, *d_alist = nullptr, *d_nlist = nullptr;
     if (list_max && nv && nv < 0xFFFFFFF0ULL) {
       HIP_TRY(tmp.get(&d_pos_of, (total + 1) * 4)); HIP_TRY(tmp.get(&d_clist, (n_cand + 1) * 4)); HIP_TRY(tmp.get(&d_alist, (n_cand + 1) * 4)); HIP_TRY(tmp.get(&d_nlist, 64));
@@ -530,13 +530,13 @@ static int contig_stage_impl(shn_ctx* ctx, const uint8_t* bases, const uint8_t* 
     }
     int lg_slots = 22;
     while (lg_slots < 28 && (1ULL << lg_slots) < nv / 4) lg_slots++;
-    if (getenv("SHN_CONTIG_PAIR_LOG2")) lg_slots = atoi(getenv("SHN_CONTIG_PAIR_LOG2"));     // (tests: start too small, grow)
+    lg_slots = (int)shn_env_u64("SHN_CONTIG_PAIR_LOG2", (uint64_t)lg_slots);     // (tests: start too small, grow)
     PairSlot* d_tab = nullptr;
     HIP_TRY(tmp.get(&d_tab, sizeof(PairSlot) << lg_slots));
-    const int lg_small = getenv("SHN_CONTIG_PAIR_SMALL_LOG2") ? atoi(getenv("SHN_CONTIG_PAIR_SMALL_LOG2")) : 20;   // pair table of the rounds after a block's first
+    const int lg_small = (int)shn_env_u64("SHN_CONTIG_PAIR_SMALL_LOG2", 20);   // pair table of the rounds after a block's first
     uint64_t blk0 = std::max<uint64_t>(1024, n_cand / 16);          // (n / 256: 23 rounds, 0.75 s at 731 k candidates; n / 16: 0.66 s; one block: 0.68 s)
-    if (getenv("SHN_CONTIG_BLOCK0")) blk0 = std::max<uint64_t>(1, strtoull(getenv("SHN_CONTIG_BLOCK0"), nullptr, 10));
-    const int max_rounds = getenv("SHN_CONTIG_MAX_ROUNDS") ? std::max(1, atoi(getenv("SHN_CONTIG_MAX_ROUNDS"))) : 64;   // (tests: halve blocks early)
+    blk0 = shn_env_u64("SHN_CONTIG_BLOCK0", blk0, 1);
+    const int max_rounds = (int)shn_env_u64("SHN_CONTIG_MAX_ROUNDS", 64, 1, 1u << 30);   // (tests: halve blocks early)
     uint64_t lo = 0, bsize = blk0;
     while (lo < n_cand) {
       uint64_t hi = std::min<uint64_t>(n_cand, lo + bsize);

@@ -49,7 +49,7 @@ struct shn_cgraph {
   // accepted[i] = 1-based accepted index of candidate i or 0; bestcnt[i] = hit count of its `best` contig
   void add(const uint8_t* bases, const uint64_t* off, uint64_t n_cand, int32_t* accepted, int32_t* bestcnt) {
     const int C = k1 - 1;
-    const bool dbg = getenv("SHN_DEBUG") != nullptr;
+    const bool dbg = shn_env_set("SHN_DEBUG");
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     for (uint64_t i = 0; i < n_cand; i++) { accepted[i] = 0; bestcnt[i] = 0; }
     n_cand_total += n_cand;

@@ -39,7 +39,7 @@ extern "C" int shn_cgraph_export(const shn_cgraph* g, uint64_t* conn_off, int32_
     for (size_t j = 0; j < g->conns[i].nb.size(); j++) { conn_nb[p] = g->conns[i].nb[j]; conn_w[p] = g->conns[i].w[j]; p++; }
   }
   conn_off[n_acc] = p;
-  if (getenv("SHN_DEBUG"))
+  if (shn_env_set("SHN_DEBUG"))
     fprintf(stderr, "[contig_graph] %llu candidates: %llu evaluations in %llu batches, %.3f s, inserts %.3f s\n",
             (unsigned long long)g->n_cand_total, (unsigned long long)g->n_evals, (unsigned long long)g->n_batches, g->t_eval, g->t_accept);
   return SHN_OK;

@@ -91,10 +91,9 @@ std::deque<hipEvent_t> g_ev_free;                // events of frees, given back 
 std::vector<hipStream_t> g_fork_streams;         // (g_blocks_mu) streams of forked contexts: short queues, ordered at the reuse
 std::atomic<uint64_t> g_dbg[8];
 thread_local hipStream_t t_stream = nullptr;
-int poison_byte() { static const int v = getenv("SHN_DEV_POISON") ? (atoi(getenv("SHN_DEV_POISON")) & 255) : -1; return v; }
-bool legacy_reuse() { static const bool v = getenv("SHN_DEV_LEGACY") && getenv("SHN_DEV_LEGACY")[0] == '1'; return v; }   // (A/B: the allocator of rounds 1-4 -- a freed block goes to the next caller at once)
-bool no_cache() { static const bool v = getenv("SHN_DEV_NOCACHE") && getenv("SHN_DEV_NOCACHE")[0] == '1'; return v; }
-bool free_events() { static const bool v = !(getenv("SHN_DEV_FREE_EVENTS") && getenv("SHN_DEV_FREE_EVENTS")[0] == '0'); return v; }   // (A/B: 0 = every hand-over ordered at the reuse, as in round 5)
+int poison_byte() { static const int v = shn_env_set("SHN_DEV_POISON") ? (int)(shn_env_u64("SHN_DEV_POISON", 0) & 255) : -1; return v; }
+bool legacy_reuse() { static const bool v = shn_env_flag("SHN_DEV_LEGACY", false); return v; }   // (A/B: the allocator of rounds 1-4 -- a freed block goes to the next caller at once)
+bool no_cache() { static const bool v = shn_env_flag("SHN_DEV_NOCACHE", false); return v; }
 bool is_fork_stream(hipStream_t s) { for (hipStream_t f : g_fork_streams) if (f == s) return true; return false; }
 hipEvent_t take_event() {
   hipEvent_t e = nullptr;
@@ -136,7 +135,7 @@ bool order_behind(DevBlock& b, hipStream_t asker) {
 void shn_fork_stream_added(hipStream_t s) { std::lock_guard<std::mutex> lk(g_blocks_mu); g_fork_streams.push_back(s); }
 namespace {
 struct CopyCensus {
-  const bool on = getenv("SHN_COPY_CENSUS") != nullptr;
+  const bool on = shn_env_set("SHN_COPY_CENSUS");
   std::mutex mu;
   std::map<std::pair<std::string, int>, std::pair<uint64_t, uint64_t>> sites;      // (file, line) -> calls, bytes
   void add(const char* file, int line, size_t n) {
@@ -273,7 +272,7 @@ void shn_dev_free_on(void* p, hipStream_t stream) {
     for (int j = 0; j < n_on; j++) {
       b.pend[j] = on[j];
       b.ev[j] = nullptr;
-      if (free_events() && !legacy_reuse() && !is_fork_stream(on[j])) {          // an owner's stream: what is queued on it NOW is all the block has to wait for
+      if (!legacy_reuse() && !is_fork_stream(on[j])) {          // an owner's stream: what is queued on it NOW is all the block has to wait for
         hipEvent_t e = take_event();
         if (e && hipEventRecord(e, on[j]) == hipSuccess) { b.ev[j] = e; g_dbg[6].fetch_add(1); }
         else { (void)hipGetLastError(); give_event(e); }
@@ -344,7 +343,7 @@ extern "C" int shn_ctx_create(int device, void* stream, shn_ctx** out) {
   c->sk_pool_ratio = 0;
   c->owns_stream = false;
   for (int i = 0; i < T_N; i++) { c->ms[i] = 0; c->regions[i] = 0; c->abytes[i] = 0; }
-  const char* rule = getenv("SHN_LP_RULE");
+  const char* rule = shn_env_str("SHN_LP_RULE");
   c->lp_rule = (rule && !strcmp(rule, "vertex")) ? SHN_LP_RULE_VERTEX : SHN_LP_RULE_CENTER;
   for (auto& v : c->lp_stats) v = 0;
   c->wsset = shn_default_wsset();
@@ -430,10 +429,9 @@ extern "C" int shn_ctx_fork(const shn_ctx* parent, shn_ctx** out) {
   // A fork's kernels are the short, latency-bound passes of one partition (seed scans, distinct reads, path searches, LP batches)
   // whose host thread waits for each: on a stream of the highest priority their workgroups are placed ahead of those of a long
   // kernel queued on the owner's stream -- which matters when another batch's counting / extension runs beside the graph stage
-  // (bench.py's two batches in flight) and costs nothing otherwise.  SHN_FORK_PRIORITY=0: default priority, as until round 6.
-  static const bool fork_high = !(getenv("SHN_FORK_PRIORITY") && getenv("SHN_FORK_PRIORITY")[0] == '0');
+  // (bench.py's two batches in flight) and costs nothing otherwise.
   int pr_least = 0, pr_greatest = 0;
-  if (fork_high && hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest) == hipSuccess && pr_greatest != pr_least)
+  if (hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest) == hipSuccess && pr_greatest != pr_least)
     HIP_TRY(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, pr_greatest));
   else
     HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -462,7 +460,7 @@ struct ShnThreadCtx {
 static thread_local ShnThreadCtx t_thread_ctx;
 static shn_ctx* thread_ctx_impl(shn_ctx* p) {
   if (!p) return nullptr;
-  static const bool no_fork = getenv("SHN_GRAPH_FORK") && getenv("SHN_GRAPH_FORK")[0] == '0';
+  static const bool no_fork = !shn_env_flag("SHN_GRAPH_FORK", true);
   if (no_fork) return p;
   ShnThreadCtx& t = t_thread_ctx;
   if (t.c && t.parent == p && t.c->parent == p) { t.c->lp_rule = p->lp_rule; t.c->timing = p->timing; return t.c; }      // (rule / timing may have been set on the parent since the fork; a parent that went away orphaned the fork: a new one)
@@ -799,9 +797,7 @@ extern "C" uint64_t shn_reads_n_invalid(const shn_reads* r) { return r ? r->n_in
 #include <climits>
 static void shn_malloc_tune_apply();
 __attribute__((constructor)) static void shn_malloc_tune() {
-  const char* v = getenv("SHN_MALLOC_TUNE");
-  if (!v || v[0] != '1') return;
-  shn_malloc_tune_apply();
+  if (shn_env_flag("SHN_MALLOC_TUNE", false)) shn_malloc_tune_apply();
 }
 extern "C" void shn_malloc_tune_now(void) { shn_malloc_tune_apply(); }
 static void shn_malloc_tune_apply() {
@@ -840,8 +836,8 @@ extern "C" int shn_host_cpus(void) {
   // one process per GPU: the ranks of a node share the allowance (LOCAL_WORLD_SIZE is torchrun's count of them; SHN_LOCAL_RANKS
   // for other launchers) -- eight ranks each sizing its pools for the whole quota is the oversubscription described above
   for (const char* name : {"SHN_LOCAL_RANKS", "LOCAL_WORLD_SIZE"})
-    if (const char* e = getenv(name)) { const int v = atoi(e); if (v > 1) { n = std::max(1, n / v); break; } }
-  if (const char* e = getenv("SHN_HOST_CPUS")) { const int v = atoi(e); if (v > 0) n = v; }
+    if (const char* e = shn_env_str(name)) { const int v = atoi(e); if (v > 1) { n = std::max(1, n / v); break; } }
+  { const int v = (int)shn_env_u64("SHN_HOST_CPUS", 0, 0, 1u << 20); if (v > 0) n = v; }
   cached = std::max(1, n);
   return cached;
 }

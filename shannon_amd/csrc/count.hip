@@ -545,7 +545,7 @@ int ShnWs::get(size_t bytes, void** out) {
     // SHN_DEV_POISON: a slot that has just grown is filled with the poison byte; SHN_DEV_POISON_WS=1: on EVERY request (finds reads of
     // what an earlier call left behind: no call may rely on a slot's content across calls -- the seed scan's count / fetch pair,
     // which did until round 5, owns its offsets now, seeds.hip)
-    static const bool every = getenv("SHN_DEV_POISON_WS") && getenv("SHN_DEV_POISON_WS")[0] == '1';
+    static const bool every = shn_env_flag("SHN_DEV_POISON_WS", false);
     if (every || grew) shn_poison(p, bytes, shn_current_stream());
   }
   return SHN_OK;
@@ -616,7 +616,7 @@ extern "C" int shn_count_k1mers(shn_ctx* ctx, shn_reads* const* sets, int n_sets
   // back).  Beyond 2^31 windows the reads are counted in chunks of at most that many windows, each chunk to its own table, and
   // the tables' (key, count) pairs are reduced by key (the pairs path of the exchange step) -- a few GB of extra traffic.
   uint64_t chunk_windows = 1ULL << 31;
-  if (getenv("SHN_COUNT_CHUNK")) chunk_windows = std::max<uint64_t>(1, strtoull(getenv("SHN_COUNT_CHUNK"), nullptr, 10));   // (tests)
+  chunk_windows = shn_env_u64("SHN_COUNT_CHUNK", chunk_windows, 1);   // (tests)
   if (upper <= chunk_windows) return count_views(ctx, views, upper, k1, both_strands, out);
   {
     // inputs of this size go through the super-k-mer path in one piece (its records are a quarter of the windows' keys); what it
@@ -685,13 +685,13 @@ static int count_views(shn_ctx* ctx, const std::vector<ReadsView>& views, uint64
   {
     int& learned_log2 = ctx->count_direct_log2;            // slots that sufficed last time on this context (0: none yet; -1: the
                                                            // one-pass path gave up on this context's input -- do not try again)
-    const int mode = getenv("SHN_COUNT_DIRECT") ? atoi(getenv("SHN_COUNT_DIRECT")) : 1;      // 0 off, 1 large inputs, 2 always (tests)
+    const int mode = (int)shn_env_u64("SHN_COUNT_DIRECT", 1);      // 0 off, 1 large inputs, 2 always (tests)
     // (stored key + 1: k1 = 32 is fine for canonical counting -- the one key that would wrap, all-T, is never the canonical form of
     // a pair, its reverse complement all-A is)
     const bool want = mode != 0 && (upper >= (1ULL << 22) || mode == 2) && (k1 < 32 || both_strands) && upper > 0 && (learned_log2 >= 0 || mode == 2);
     int lg = learned_log2 > 0 ? learned_log2 : 0;
     if (!lg) { lg = 20; while (lg < 24 && (1ULL << lg) < upper / 32) lg++; }
-    if (getenv("SHN_COUNT_DIRECT_LOG2")) lg = atoi(getenv("SHN_COUNT_DIRECT_LOG2"));          // (tests: start too small, grow)
+    lg = (int)shn_env_u64("SHN_COUNT_DIRECT_LOG2", (uint64_t)lg);          // (tests: start too small, grow)
     for (int attempt = 0; want && attempt < 8 && lg <= 27; attempt++) {
       const uint64_t slots = 1ULL << lg;
       unsigned long long* gk = nullptr; uint32_t* gc = nullptr; uint32_t* flag = nullptr; uint64_t* pos = nullptr; uint32_t* d_ov = nullptr;
@@ -732,7 +732,7 @@ static int count_views(shn_ctx* ctx, const std::vector<ReadsView>& views, uint64
       freeall();
 #undef TRYD
       if (rcp) return rcp;
-      if (!getenv("SHN_COUNT_DIRECT_LOG2")) learned_log2 = lg;
+      if (!shn_env_set("SHN_COUNT_DIRECT_LOG2")) learned_log2 = lg;
       *out = tb;
       return SHN_OK;
     }

@@ -518,7 +518,7 @@ __global__ void sk_sum_counts_kernel(const uint32_t* __restrict__ c, uint64_t n,
 // ================================================================ host side
 int shn_count_superkmers(shn_ctx* ctx, const std::vector<ReadsView>& views, uint64_t upper, int k1, int both_strands, shn_table** out, int* handled) {
   *handled = 0;
-  const int mode = getenv("SHN_COUNT_SK") ? atoi(getenv("SHN_COUNT_SK")) : 1;          // 0 off, 1 large inputs, 2 always (tests)
+  const int mode = (int)shn_env_u64("SHN_COUNT_SK", 1);          // 0 off, 1 large inputs, 2 always (tests)
   if (mode == 0 || k1 < SK_MIN_K || (k1 == 32 && !both_strands) || upper == 0) return SHN_OK;
   if (mode != 2 && upper < (1ULL << 22)) return SHN_OK;
   hipStream_t s = ctx->stream; shn_use_stream(s);
@@ -528,7 +528,7 @@ int shn_count_superkmers(shn_ctx* ctx, const std::vector<ReadsView>& views, uint
   P.w = k1 - P.m + 1;
   int bits = 6;
   while (bits < 22 && (upper >> bits) > 3500) bits++;
-  if (getenv("SHN_COUNT_SK_BITS")) bits = std::max(4, std::min(22, atoi(getenv("SHN_COUNT_SK_BITS"))));      // (tests / experiments: any grid gives the same table)
+  bits = (int)shn_env_u64("SHN_COUNT_SK_BITS", (uint64_t)bits, 4, 22);      // (tests / experiments: any grid gives the same table)
   P.bits = bits;
   P.b1 = (bits + 1) / 2;
   P.b2 = bits - P.b1;
@@ -543,7 +543,7 @@ int shn_count_superkmers(shn_ctx* ctx, const std::vector<ReadsView>& views, uint
     const double expect = 2.0 * v.wmax / (P.w + 1) + 1.0;
     uint32_t S = ((uint32_t)(expect * 1.35 + 1.999) + 3u) & ~3u;
     S = std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(S, 252), std::max<uint32_t>(v.wmax, 1)));
-    if (getenv("SHN_COUNT_SK_SLOTS")) S = (uint32_t)std::max(1, std::min(252, atoi(getenv("SHN_COUNT_SK_SLOTS"))));     // (tests: reads that overflow their slots)
+    S = (uint32_t)shn_env_u64("SHN_COUNT_SK_SLOTS", S, 1, 252);     // (tests: reads that overflow their slots)
     plan[i] = ViewPlan{n_slots, n_reads, S, v.wmax ? v.wmax + (uint32_t)k1 - 1 : 0u};
     if (v.wmax && v.n_reads) { n_slots += v.n_reads * S; n_reads += v.n_reads; }
   }
@@ -644,13 +644,13 @@ int shn_count_superkmers(shn_ctx* ctx, const std::vector<ReadsView>& views, uint
   // the pool of (key, count) pairs: sized from what the buckets emitted per window last time on this context (an eighth of the
   // windows to begin with); a pool that turns out too small is made as large as the cursor says and the bucket kernels run again
   double ratio = ctx->sk_pool_ratio > 0 ? ctx->sk_pool_ratio * 1.05 : 0.125;
-  if (getenv("SHN_COUNT_SK_POOL")) ratio = atof(getenv("SHN_COUNT_SK_POOL"));                                  // (tests: start too small)
+  ratio = shn_env_double("SHN_COUNT_SK_POOL", ratio);                                  // (tests: start too small)
   uint64_t cap = std::min<uint64_t>(upper, (uint64_t)((double)upper * ratio) + 4096);
   uint64_t np = 0;
   void *pk = nullptr, *pc = nullptr;
   // layout 1 (default): the buckets' sorted runs ARE the table; SHN_COUNT_SK_LAYOUT=0 (and the fallback of a bucket that 65,536 key
   // ranges do not split): unsorted pairs, reduced and re-partitioned by key through the pairs path
-  bool sorted = !(getenv("SHN_COUNT_SK_LAYOUT") && atoi(getenv("SHN_COUNT_SK_LAYOUT")) == 0);
+  bool sorted = shn_env_u64("SHN_COUNT_SK_LAYOUT", 1) != 0;
   if (sorted) {
     void* pr;
     if ((rc = shn_ws(ctx)[24].get(nbk * 20 + 64, &pr))) return rc;
@@ -696,7 +696,7 @@ int shn_count_superkmers(shn_ctx* ctx, const std::vector<ReadsView>& views, uint
           HIP_TRY(hipMemcpyAsync(cur, d_cursors, 64, hipMemcpyDeviceToHost, s));
           HIP_TRY(hipStreamSynchronize(s));
         }
-        if (getenv("SHN_COUNT_SK_DEBUG")) fprintf(stderr, "[sk] buckets %llu, %llu of them to 2,048 slots, %llu to 8,192; pool of %llu pairs in %d stretches\n", (unsigned long long)nbk, n_t2, cur[6], (unsigned long long)cap, SK_REGIONS);
+        if (shn_env_set("SHN_COUNT_SK_DEBUG")) fprintf(stderr, "[sk] buckets %llu, %llu of them to 2,048 slots, %llu to 8,192; pool of %llu pairs in %d stretches\n", (unsigned long long)nbk, n_t2, cur[6], (unsigned long long)cap, SK_REGIONS);
         if (cur[6]) {
           TimerRegion tb(ctx, T_SK_BIG);
           if (both_strands) SK_LAUNCH(true, BIG_T, BIG_CAP, 2, cur[6], lds_big, d_defer2, nullptr, 2);
@@ -718,7 +718,7 @@ int shn_count_superkmers(shn_ctx* ctx, const std::vector<ReadsView>& views, uint
       cap = std::max<uint64_t>(np + np / 64 + 4096, (fullest + fullest / 64 + 64) * SK_REGIONS);          // (every stretch as large as the fullest asked for)
     }
     if (sorted) {
-      if (!getenv("SHN_COUNT_SK_POOL")) ctx->sk_pool_ratio = (double)np / (double)upper;
+      if (!shn_env_set("SHN_COUNT_SK_POOL")) ctx->sk_pool_ratio = (double)np / (double)upper;
       shn_table* t = new shn_table();
       memset(t, 0, sizeof(*t));
       t->ctx = ctx; t->device = ctx->device; t->k = k1; t->canonical = both_strands ? 1 : 0; t->bits = bits; t->n_buckets = nbk;

@@ -113,7 +113,6 @@ struct shn_ext {
   uint64_t wave_steps;   // ... of which by the wavefront kernel
   uint64_t fresh_steps;  // ... of which by the thread walker in the first round of a rank block
   int dense_rounds;      // rounds whose begin / mark passes streamed all claims
-  uint64_t settled_walks; // walks that were never launched: a lower rank on a forced chain of their seed (ext_chain_has_lower)
   uint32_t* d_nr;        // [n_seeds] right steps (UNCLAIMED = void walk)
   uint32_t* d_nl;        // [n_seeds]
   uint64_t* d_totw;      // [n_seeds] sum of weights incl. the seed
@@ -181,22 +180,10 @@ __device__ __forceinline__ uint64_t fd_line_in_bucket(const TabIdx& T, uint32_t 
   const uint64_t lo = T.boff[b], hi = T.boff[b + 1];
   return lo / FD_PER_LINE + b + __umul64hi(shn_mix64(key), (hi - lo) / FD_PER_LINE + 1);
 }
-// Workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8 share one; each XCD has its own 4 MB L2).  A kernel that
-// goes through the table in order -- consecutive blocks on consecutive k1-mers, whose dictionary look-ups fall into the same few
-// lines -- therefore spreads every stretch of lines over eight L2s.  With this block number instead of blockIdx.x the blocks that
-// share an XCD are consecutive: each XCD works through one contiguous eighth of the launch.  (Speed only; any mapping is correct.)
-// MEASURED at BASELINE configs[2] (round 5, two boxes-worth of A/B on one box): ext_records_kernel 110 -> 119-120 ms WITH the
-// mapping -- the spread over all eight L2s (and the shared infinity cache behind them) serves the look-ups better than one L2 per
-// stretch; SHN_XCD_MAP=1 switches it on, the default is the plain order.
-__device__ __forceinline__ uint64_t xcd_block(int on) {
-  const uint32_t g8 = gridDim.x & ~7u;
-  if (!on || blockIdx.x >= g8) return blockIdx.x;
-  return (uint64_t)(blockIdx.x & 7u) * (g8 >> 3) + (blockIdx.x >> 3);
-}
 __global__ void fd_build_kernel(const TabIdx T, const uint8_t* __restrict__ flags, uint64_t n,
-                                unsigned long long* __restrict__ lines, uint64_t n_lines, int xcd) {
+                                unsigned long long* __restrict__ lines, uint64_t n_lines) {
   const uint64_t* __restrict__ tkeys = T.keys;
-  const uint64_t i = xcd_block(xcd) * blockDim.x + threadIdx.x;
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint8_t f = flags[i];
   if (f & 2) return;
@@ -244,38 +231,21 @@ __device__ __forceinline__ uint32_t fd_match(ulonglong2 v, const unsigned long l
 // 128-byte request of the eight lanes, all eight requests in flight before the first is looked at), and then write the two
 // records -- 128 contiguous bytes -- 16 bytes each.
 struct __attribute__((aligned(16))) Quad { uint32_t a, b, c, d; };
-#ifndef SHN_REC_PIPE
-#define SHN_REC_PIPE 0      // 1: the next trip's key / flag / weight fetched at the top of the trip.  Measured (round 5, configs[2]): 128 ms against 119.5 -- the
-#endif                      // eight look-ups of a trip are already all in flight together and the extra live registers cost a wavefront or spills; left off
-
-#if SHN_REC_PIPE
-#define REC_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(5, 5)))      // (the pipelined form needs 105 registers: held at 96 = 5 wavefronts per SIMD, ten words spill)
-#else
-#define REC_KERNEL_ATTR
-#endif
-__global__ REC_KERNEL_ATTR void ext_records_kernel(const TabIdx T, const uint8_t* __restrict__ flags, const uint32_t* __restrict__ weight, uint64_t n, int k, int canonical,
-                                   Rec* __restrict__ rec, const unsigned long long* __restrict__ lines, uint64_t n_lines, int xcd) {
+__global__ void ext_records_kernel(const TabIdx T, const uint8_t* __restrict__ flags, const uint32_t* __restrict__ weight, uint64_t n, int k, int canonical,
+                                   Rec* __restrict__ rec, const unsigned long long* __restrict__ lines, uint64_t n_lines) {
   const uint64_t* __restrict__ tkeys = T.keys;
   const uint64_t total = n * 8;
   const uint64_t rounded = (total + 63) & ~63ULL;                       // whole wavefronts take part in the ballots and shuffles
   const uint64_t mask = (k == 32) ? ~0ULL : ((1ULL << (2 * k)) - 1);
   const int lane = threadIdx.x & 63, g0 = lane & ~7, p = lane & 7;
-  // (software-pipelined: the k1-mer, its flags and its weight of the NEXT trip are asked for at the top of this one -- a k1-mer is a
-  // chain of dependent round trips (its key -> its neighbours' bucket offsets -> their dictionary lines), the kernel runs at 5
-  // wavefronts per SIMD, and the first link of the chain need not be one)
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  uint64_t gid = xcd_block(xcd) * blockDim.x + threadIdx.x;
+  uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   bool in = gid < total;
   uint64_t i = in ? gid >> 3 : 0;
   uint8_t f = (gid < rounded && in) ? flags[i] : (uint8_t)2;
   uint64_t str = gid < rounded ? tkeys[i] : 0ULL;
   uint32_t wt = (gid < rounded && in && (p == 2 || p == 6)) ? weight[i] : 0u;
   for (; gid < rounded;) {
-    const uint64_t gid_n = gid + stride;
-    const bool in_n = gid_n < total;
-    const uint64_t i_n = in_n ? gid_n >> 3 : 0;
-    uint8_t f_n = 2; uint64_t str_n = 0; uint32_t wt_n = 0;
-    if (SHN_REC_PIPE && gid_n < rounded) { str_n = tkeys[i_n]; if (in_n) { f_n = flags[i_n]; if (p == 2 || p == 6) wt_n = weight[i_n]; } }
     const bool dead0 = (f & 2) != 0;                                    // forward orientation
     const bool dead1 = dead0 || (f & 1) || !canonical;                  // reverse-complement orientation (absent for palindromes)
     // look-up q: q = 0..3 append base q, q = 4..7 prepend base q - 4; lane q prepares it (key, strand, line), the group shares
@@ -350,145 +320,8 @@ __global__ REC_KERNEL_ATTR void ext_records_kernel(const TabIdx T, const uint8_t
       }
       ((Quad*)(rec + 2 * i))[p] = out;
     }
-    gid = gid_n; in = in_n; i = i_n;
-    if (SHN_REC_PIPE) { f = f_n; str = str_n; wt = wt_n; }
-    else if (gid < rounded) { str = tkeys[i]; f = in ? flags[i] : (uint8_t)2; wt = (in && (p == 2 || p == 6)) ? weight[i] : 0u; }
-  }
-}
-
-// The same records for a table of layout 1 with most look-ups answered from LDS (round 5).  A k1-mer's neighbour has the k1-mer's
-// own minimizer seven times out of eight, i.e. lies in the k1-mer's own bucket -- and the kernel above already knows every
-// neighbour's bucket (it needs it for the dictionary line).  A block takes REC_G consecutive buckets (~170 keys each at BASELINE
-// configs[2]), stages their keys and flags in LDS, and a neighbour whose bucket is one of them is looked up there by bisection:
-// found = its id, not found = it does not exist (a key has one bucket).  Only the neighbours of other buckets (one in eight) go to
-// the dictionary in HBM; the eight lanes of a k1-mer make those look-ups together as before, a wavefront skips the look-up
-// numbers none of its eight k1-mers needs.  Blocks whose buckets hold more than REC_CAP keys take the dictionary for everything.
-#define REC_G 4
-#define REC_CAP 2048
-#ifndef REC_FLY
-#define REC_FLY 2
-#endif
-__global__ __launch_bounds__(256) void ext_records_lds_kernel(const TabIdx T, const uint8_t* __restrict__ flags, const uint32_t* __restrict__ weight,
-                                                              uint64_t n_buckets, int k, int canonical, Rec* __restrict__ rec,
-                                                              const unsigned long long* __restrict__ lines, int ablate) {
-  // ablate (timing experiments only, wrong records): 1 = no dictionary look-ups, 2 = no LDS bisection either, 3 = no neighbour minimizers
-  __shared__ uint64_t skeys[REC_CAP];
-  __shared__ uint8_t sflags[REC_CAP];
-  __shared__ uint64_t sboff[REC_G + 1];
-  const uint64_t* __restrict__ tkeys = T.keys;
-  const uint64_t B0 = (uint64_t)blockIdx.x * REC_G;
-  const uint32_t G = (uint32_t)(n_buckets - B0 < REC_G ? n_buckets - B0 : REC_G);
-  if (threadIdx.x <= G) sboff[threadIdx.x] = T.boff[B0 + threadIdx.x];
-  __syncthreads();
-  const uint64_t lo = sboff[0];
-  const uint64_t nk64 = sboff[G] - lo;
-  if (nk64 == 0) return;
-  const bool staged = nk64 <= REC_CAP;
-  const uint32_t nk = (uint32_t)nk64;                                   // (a bucket range of 2^32 keys does not occur: the table holds fewer)
-  if (staged) for (uint32_t t = threadIdx.x; t < nk; t += blockDim.x) { skeys[t] = tkeys[lo + t]; sflags[t] = flags[lo + t]; }
-  __syncthreads();
-  const uint64_t mask = (k == 32) ? ~0ULL : ((1ULL << (2 * k)) - 1);
-  const int lane = threadIdx.x & 63, g0 = lane & ~7, p = lane & 7;
-  const int m = T.m, w = k - m + 1;
-  const uint32_t mmask = m == 16 ? 0xFFFFFFFFu : ((1u << (2 * m)) - 1u);
-  for (uint64_t base = 0; base < nk64; base += blockDim.x >> 3) {
-    const uint64_t t = base + (threadIdx.x >> 3);
-    const bool in = t < nk64;
-    const uint64_t i = lo + (in ? t : 0);
-    const uint64_t str = in ? (staged ? skeys[t] : tkeys[i]) : 0ULL;
-    const uint8_t f = in ? (staged ? sflags[t] : flags[i]) : (uint8_t)2;
-    const uint32_t wt = (in && (p == 2 || p == 6)) ? weight[i] : 0u;
-    const bool dead0 = (f & 2) != 0;
-    const bool dead1 = dead0 || (f & 1) || !canonical;
-    uint64_t mykey; uint32_t mystrand = 0;
-    {
-      const uint64_t b = (uint64_t)(p & 3);
-      mykey = p < 4 ? (((str << 2) | b) & mask) : ((str >> 2) | (b << (2 * (k - 1))));
-      if (canonical) { const uint64_t rc = shn_revcomp(mykey, k); if (rc < mykey) { mykey = rc; mystrand = 1; } }
-      if (dead0) mykey = 0;
-    }
-    // the neighbour's bucket from the k1-mer's own m-mers (see ext_records_kernel)
-    uint32_t nbkt = (uint32_t)B0;
-    if (ablate < 3) {
-      uint32_t smin = 0xFFFFFFFFu, pmin = 0xFFFFFFFFu;
-      for (int pos = p; pos < w; pos += 8) {
-        const uint32_t fm = (uint32_t)(str >> (2 * (k - m - pos))) & mmask;
-        uint32_t c = fm;
-        if (canonical) { const uint32_t r = shn_revcomp32(fm, m); c = r < fm ? r : fm; }
-        const uint32_t o = shn_sk_order(c);
-        if (pos >= 1) smin = o < smin ? o : smin;
-        if (pos <= w - 2) pmin = o < pmin ? o : pmin;
-      }
-#pragma unroll
-      for (int d = 1; d < 8; d <<= 1) {
-        const uint32_t a = (uint32_t)__shfl_xor((int)smin, d, 64), b2 = (uint32_t)__shfl_xor((int)pmin, d, 64);
-        smin = a < smin ? a : smin; pmin = b2 < pmin ? b2 : pmin;
-      }
-      const uint32_t nb = (uint32_t)(p & 3);
-      const uint32_t fm = p < 4 ? ((((uint32_t)str & (mmask >> 2)) << 2) | nb)
-                                : ((nb << (2 * (m - 1))) | ((uint32_t)(str >> (2 * (k - m + 1))) & (mmask >> 2)));
-      uint32_t c = fm;
-      if (canonical) { const uint32_t r = shn_revcomp32(fm, m); c = r < fm ? r : fm; }
-      uint32_t o = shn_sk_order(c);
-      const uint32_t shared = p < 4 ? smin : pmin;
-      o = shared < o ? shared : o;
-      nbkt = shn_sk_bucket(o, T.bits);
-    }
-    bool cross = !dead0;                                                // this lane's look-up goes to the dictionary
-    uint32_t w_own = 0xFFFFFFFFu;
-    if (ablate >= 2) { cross = false; w_own = (uint32_t)mykey & 0x7FFFFFFu; }
-    else if (!dead0 && staged && (uint64_t)nbkt >= B0 && (uint64_t)nbkt < B0 + G) {
-      cross = false;
-      uint32_t a = (uint32_t)(sboff[nbkt - B0] - lo), b = (uint32_t)(sboff[nbkt - B0 + 1] - lo);
-      while (a < b) {
-        const uint32_t mid = (a + b) >> 1;
-        const uint64_t v = skeys[mid];
-        if (v == mykey) { const uint8_t fj = sflags[mid]; if (!(fj & 2)) w_own = (uint32_t)(lo + mid) | ((fj & 1) ? FD_PAL : 0u); break; }
-        if (v < mykey) a = mid + 1; else b = mid;
-      }
-    }
-    if (ablate == 1) cross = false;
-    const uint64_t myline = cross ? fd_line_in_bucket(T, nbkt, mykey) : 0ULL;
-    const uint32_t strands = (uint32_t)((__ballot(mystrand != 0) >> g0) & 0xFFULL);
-    uint32_t need = 0;                                                  // look-up numbers some k1-mer of this wavefront sends to the dictionary
-#pragma unroll
-    for (int q = 0; q < 8; q++) if (__ballot(cross && p == q)) need |= 1u << q;
-    const uint64_t ckey = cross ? mykey : 0ULL;
-    uint32_t r8[8], d8[8];
-#pragma unroll
-    for (int h = 0; h < 8; h += REC_FLY) {                              // (REC_FLY dictionary look-ups in flight at a time: one in eight is a real one)
-      ulonglong2 v[REC_FLY];
-#pragma unroll
-      for (int q = 0; q < REC_FLY; q++)
-        if ((need >> (h + q)) & 1) v[q] = ((const ulonglong2*)(lines + shfl_u64(myline, g0 + h + q) * 16))[p];
-#pragma unroll
-      for (int q = 0; q < REC_FLY; q++) {
-        uint32_t wq = (uint32_t)__shfl((int)w_own, g0 + h + q, 64);
-        if ((need >> (h + q)) & 1) {
-          const uint64_t kq = shfl_u64(ckey, g0 + h + q);
-          const uint32_t wd = fd_match(v[q], lines, shfl_u64(myline, g0 + h + q), kq, p, g0, T, flags);
-          if (kq != 0) wq = wd;                                         // (this group's look-up was one for the dictionary)
-        }
-        if (wq == 0xFFFFFFFFu) { r8[h + q] = d8[h + q] = 0xFFFFFFFFu; continue; }
-        const uint32_t j = wq & ~FD_PAL;
-        const uint32_t st = (strands >> (h + q)) & 1u;
-        r8[h + q] = 2 * j + st;
-        d8[h + q] = (wq & FD_PAL) ? r8[h + q] : 2 * j + (1 - st);
-      }
-    }
-    if (in) {
-      Quad out;
-      const Quad none = Quad{~0u, ~0u, ~0u, ~0u};
-      switch (p) {
-        case 0: out = Quad{r8[0], r8[1], r8[2], r8[3]}; break;
-        case 1: out = Quad{r8[4], r8[5], r8[6], r8[7]}; break;
-        case 4: out = dead1 ? none : Quad{d8[7], d8[6], d8[5], d8[4]}; break;
-        case 5: out = dead1 ? none : Quad{d8[3], d8[2], d8[1], d8[0]}; break;
-        case 2: case 6: out = Quad{wt, NOHINT_WORD, 0xFFFFFFFFu, 0u}; break;
-        default: out = Quad{0u, 0u, 0u, 0u}; break;
-      }
-      ((Quad*)(rec + 2 * i))[p] = out;
-    }
+    gid += stride; in = gid < total; i = in ? gid >> 3 : 0;
+    if (gid < rounded) { str = tkeys[i]; f = in ? flags[i] : (uint8_t)2; wt = (in && (p == 2 || p == 6)) ? weight[i] : 0u; }
   }
 }
 
@@ -524,18 +357,8 @@ __device__ __forceinline__ void cc_unite(uint32_t* lab, uint32_t u, uint32_t v) 
 // and only joined through a common neighbour if that neighbour exists and is not low-complexity (a transcript's last K-mer before
 // a poly-A tail is the typical exception).  So the labelling also unites every k1-mer with its (up to six) siblings.
 // Look-ups as in the records kernel: eight lanes per canonical k1-mer, through the one-line dictionary.
-// diagnostics (round 5): look-ups of the labelling kernel that found their key / unions made / unions that found both ends united already
-__device__ unsigned long long g_cc_dbg[4];
-extern "C" int shn_debug_cc_counters(uint64_t* out4, int reset) {
-  unsigned long long h[4] = {0, 0, 0, 0};
-  if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_cc_dbg), sizeof(h)) != hipSuccess) return shn_fail(SHN_ERR_HIP, "shn_debug_cc_counters");
-  for (int i = 0; i < 4; i++) out4[i] = h[i];
-  if (reset) { unsigned long long z[4] = {0, 0, 0, 0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_cc_dbg), z, sizeof(z)) != hipSuccess) return shn_fail(SHN_ERR_HIP, "shn_debug_cc_counters"); }
-  return SHN_OK;
-}
-static int cc_half_mode() { return ((getenv("SHN_CC_HALF") && getenv("SHN_CC_HALF")[0] == '0') ? 0 : 1) | (getenv("SHN_CC_DEBUG") ? 2 : 0); }
 __global__ void cc_edges_kernel(const TabIdx T, const uint8_t* __restrict__ flags,
-                                uint64_t n, int k, int canonical, uint32_t* lab, const unsigned long long* __restrict__ lines, uint64_t n_lines, int half_mode) {
+                                uint64_t n, int k, int canonical, uint32_t* lab, const unsigned long long* __restrict__ lines, uint64_t n_lines) {
   const uint64_t* __restrict__ tkeys = T.keys;
   const uint64_t mask = (k == 32) ? ~0ULL : ((1ULL << (2 * k)) - 1);
   const uint64_t total = n * 8, rounded = (total + 63) & ~63ULL;
@@ -558,7 +381,7 @@ __global__ void cc_edges_kernel(const TabIdx T, const uint8_t* __restrict__ flag
         // (every edge is seen from both of its ends -- the neighbour and sibling relations are symmetric, and so is "both not
         // low-complexity" -- so an end asks only for the larger keys: half the look-ups; what is not asked goes to line 0, which the
         // caches hold)
-        if (skip || ((half_mode & 1) && mykey <= str)) mykey = 0;
+        if (skip || mykey <= str) mykey = 0;
       }
       const uint64_t myline = mykey ? fd_bucket(T, mykey, n_lines) : 0ULL;
       uint64_t key[8];
@@ -572,10 +395,7 @@ __global__ void cc_edges_kernel(const TabIdx T, const uint8_t* __restrict__ flag
       for (int q = 0; q < 8; q++) {
         const uint32_t w = fd_match(v[q], lines, shfl_u64(myline, g0 + q), key[q], p, g0, T, flags);
         // (lane q of the group does the union: eight independent ones side by side)
-        if (w != 0xFFFFFFFFu && p == q && (uint64_t)(w & ~FD_PAL) != i) {
-          if (half_mode & 2) atomicAdd(&g_cc_dbg[0], 1ULL);
-          cc_unite(lab, (uint32_t)i, w & ~FD_PAL);
-        }
+        if (w != 0xFFFFFFFFu && p == q && (uint64_t)(w & ~FD_PAL) != i) cc_unite(lab, (uint32_t)i, w & ~FD_PAL);
       }
     }
   }
@@ -682,7 +502,6 @@ struct WalkArgs {
   uint32_t promote_steps;
   uint8_t* chunk;        // per 2^CHUNK_SHIFT oriented k1-mers: "a claim in here was written this round" (the mark pass visits only those)
   uint8_t* robbed;       // per walk: a claim of its record is not (or no longer) its own -- see note_claim
-  int seed_check;        // thread walkers: look at the own seed's claim on every step and stop when a lower rank has taken it
   int first_look;        // thread walkers: a direction starts with a look at the candidates' claims alone
   // claim logs (round 6): in a bulk round -- no memos are made there -- the thread walker writes the k1-mers it claims into a chain of
   // 8-word chunks of its own ([0] = the chunk before, [1..7] = k1-mers; the seed is not logged: it is order[r]); a walk that re-runs
@@ -840,9 +659,7 @@ __global__ __launch_bounds__(WBLK) void ext_walk_kernel(WalkArgs A, uint64_t n_w
           // the walk's own seed (one line, in the L2 from the second step on): once a lower rank has taken it this walk is void in
           // the end -- 98.6 % of the walks of BASELINE configs[2] are -- and whatever it goes on to claim is wasted; it stops, is
           // flagged like any robbed walk and looks again next round
-          // (seed_check 2 -- experiment: the walk's robbed flag instead, set by whoever took ANY of its k1-mers)
-          const u64 cseed = A.seed_check == 1 ? __hip_atomic_load(&A.claim[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                            : A.seed_check == 2 ? (*(volatile const uint8_t*)&A.robbed[r] ? 0ULL : CLAIM(r, 0)) : CLAIM(r, 0);
+          const u64 cseed = __hip_atomic_load(&A.claim[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           // the claim of the step just taken goes out BEHIND the loads of this step: vector memory operations of a wavefront
           // return in issue order (one counter for loads, stores and atomics), so a claim issued in front of the loads would put
           // the latency of a memory-side atomic on every step of the walk -- and a bulk round lasts as long as its longest walk
@@ -978,8 +795,7 @@ __global__ __launch_bounds__(WBLK) void ext_walk_resume_kernel(WalkArgs A, const
       w[b] = A.weight[idx];
       nxt[b] = adj[idx];
     }
-    const u64 cseed = A.seed_check == 1 ? __hip_atomic_load(&A.claim[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                      : A.seed_check == 2 ? (*(volatile const uint8_t*)&A.robbed[r] ? 0ULL : CLAIM(r, 0)) : CLAIM(r, 0);
+    const u64 cseed = __hip_atomic_load(&A.claim[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     u64 found = UNCLAIMED64;
     if (pend != NONE32) { found = claim_node(A, pend, r, pos); pend = NONE32; }
     int best = -1;
@@ -1305,45 +1121,6 @@ __global__ void ext_audit_kernel(WalkArgs A, uint64_t ns, unsigned long long* __
   if (bad) { atomicAdd(&counters[0], 1ULL); atomicMin(&counters[1], (unsigned long long)r); }
 }
 
-// ---- Seeds that cannot survive, decided from the graph alone (round 6).  Let p be a left neighbour of the seed s whose ONLY right
-// neighbour is s (a forced link p -> s), and let some walk of rank below rank(s) traverse p -- p's own, if p is a seed of lower rank.
-// Whatever walk W gets to p first (extension_correction.py:223-245): it is seeded on p and extends right first -- its one candidate
-// is s; or it arrives at p extending right -- the same; or it arrives at p extending left, which it can only do from p's one right
-// neighbour, s.  In every case s is traversed by W or by an earlier walk, W's rank is at most rank(p) < rank(s), and the walk seeded
-// on s is void (:346).  By induction along a chain of forced links p_d -> ... -> p_1 -> s a lower rank ANYWHERE on the chain is
-// enough (whoever traverses p_i traverses p_{i-1} or came from it), and the mirror image holds on the right (q's only left
-// neighbour is s).  So of the seeds of a stretch without branches only the local rank minima can start a surviving walk: at
-// BASELINE configs[2] 98.6 % of the 186 M walks end void, most of them swallowed by a neighbour on their own unitig after a few
-// steps -- each cost its seed claim and the lines of its first candidates, and robbed whoever it met.  Here such a seed costs the
-// records of its chain neighbours (one 64-byte line per hop) and is never launched.  `hops` links are followed on each side; from
-// the second hop on only through k1-mers with a single neighbour on that side.
-__device__ __forceinline__ int adj_count(const Adj4& a) { return (a.v[0] >= 0) + (a.v[1] >= 0) + (a.v[2] >= 0) + (a.v[3] >= 0); }
-__device__ __forceinline__ bool ext_chain_has_lower(const Rec* __restrict__ rec, uint32_t o, uint32_t r, uint32_t hops) {
-  const Adj4 L0 = *(const Adj4*)((const char*)&rec[o] + 16), R0 = *(const Adj4*)((const char*)&rec[o]);
-#pragma unroll
-  for (int side = 0; side < 2; side++) {                       // 0: left neighbours (forced = their right row has one entry), 1: right
-    Adj4 nb = side == 0 ? L0 : R0;
-    for (uint32_t h = 0; h < hops; h++) {
-      const int cnt = adj_count(nb);
-      if (cnt == 0 || (h > 0 && cnt != 1)) break;
-      Adj4 next; next.v[0] = next.v[1] = next.v[2] = next.v[3] = -1;
-      bool forced_one = false;
-#pragma unroll
-      for (int b = 0; b < 4; b++) {
-        if (nb.v[b] < 0) continue;
-        const Rec* q = &rec[(uint32_t)nb.v[b]];
-        const Adj4 toward = side == 0 ? *(const Adj4*)((const char*)q) : *(const Adj4*)((const char*)q + 16);     // the row that points back at us
-        if (adj_count(toward) != 1) continue;                  // not forced: a walk may pass it without coming our way
-        if (q->seed_rank < r) return true;
-        if (cnt == 1) { next = side == 0 ? *(const Adj4*)((const char*)q + 16) : *(const Adj4*)((const char*)q); forced_one = true; }
-      }
-      if (!forced_one) break;
-      nb = next;
-    }
-  }
-  return false;
-}
-
 // classify the dirty walks of the open block: long ones (memo or recorded length) go to the wavefront kernel,
 // the others to the thread kernel.  counters: [0] long [1] dirty walks that hold claims and have no current memo [2] short [3] dirty walks
 __global__ __launch_bounds__(1024) void ext_plan_kernel(uint32_t* nr, uint32_t* nl, uint64_t ns, uint32_t frozen,
@@ -1351,8 +1128,7 @@ __global__ __launch_bounds__(1024) void ext_plan_kernel(uint32_t* nr, uint32_t* 
                                 const uint8_t* __restrict__ dirty, uint32_t* __restrict__ long_list, uint32_t* __restrict__ short_list,
                                 unsigned long long* __restrict__ counters, uint32_t long_walk, uint8_t* __restrict__ coarse,
                                 const u64* __restrict__ fresh_claim, const uint32_t* __restrict__ order, uint64_t* __restrict__ totw,
-                                const Rec* __restrict__ rec, uint32_t settle_hops, uint8_t* __restrict__ settled,
-                                unsigned long long* __restrict__ n_settled, uint8_t* __restrict__ robsat = nullptr,
+                                uint8_t* __restrict__ robsat = nullptr,
                                 unsigned long long* __restrict__ n_robsat = nullptr, const uint32_t* __restrict__ log_head = nullptr,
                                 unsigned long long* __restrict__ rel_steps = nullptr) {
   // ns here = current rank limit (walks >= limit have not started yet); walks < frozen are final and never run
@@ -1367,12 +1143,7 @@ __global__ __launch_bounds__(1024) void ext_plan_kernel(uint32_t* nr, uint32_t* 
   // the second and third block then runs over the survivors, packed -- not one live walk among 63 lanes that look at their seed and
   // idle until the wavefront's longest walk ends.
   bool isd = isd_all;
-  if (isd && settled[r]) { nr[r] = UNCLAIMED; nl[r] = 0; totw[r] = 0; isd = false; }           // void for good (below): it never runs
-  else if (isd && fresh_claim && RANK(fresh_claim[order[r]]) < r) { nr[r] = UNCLAIMED; nl[r] = 0; totw[r] = 0; isd = false; }
-  else if (isd && settle_hops && ext_chain_has_lower(rec, order[r], (uint32_t)r, settle_hops)) {
-    settled[r] = 1; nr[r] = UNCLAIMED; nl[r] = 0; totw[r] = 0; isd = false;
-    atomicAdd(n_settled, 1ULL);
-  }
+  if (isd && fresh_claim && RANK(fresh_claim[order[r]]) < r) { nr[r] = UNCLAIMED; nl[r] = 0; totw[r] = 0; isd = false; }
   bool lg = false;
   if (isd) {
     uint32_t a = nr[r];
@@ -1396,7 +1167,7 @@ __global__ __launch_bounds__(1024) void ext_plan_kernel(uint32_t* nr, uint32_t* 
     bl = tl ? atomicAdd(&counters[0], (unsigned long long)tl) : 0ULL;
     bs = ts ? atomicAdd(&counters[2], (unsigned long long)ts) : 0ULL;
   }
-  {                                                                // dirty walks, the ones settled above included (they "ran")
+  {                                                                // dirty walks, the ones found void above included (they "ran")
     const unsigned long long dm = __ballot(isd_all);
     if (lane == 0 && dm) atomicAdd(&bd, (unsigned long long)__popcll(dm));
     // ... of them the ones that hold claims (a record of a live walk): with none, the round's begin pass has nothing to release
@@ -1755,7 +1526,7 @@ static int component_shard(shn_ctx* ctx, const shn_table* t, int world, int rank
   hipLaunchKernelGGL(cc_init_kernel, dim3((uint32_t)cdiv(n, 256)), dim3(256), 0, s, d_lab, n);
   { TimerRegion t1(ctx, T_EXT_PREP);
     hipLaunchKernelGGL(cc_edges_kernel, dim3((uint32_t)std::min<uint64_t>(cdiv(n * 8, 256), 1u << 22)), dim3(256), 0, s, shn_tab_idx(t),
-                       d_flags, n, t->k, t->canonical, d_lab, (const unsigned long long*)lines, n_lines, cc_half_mode()); }
+                       d_flags, n, t->k, t->canonical, d_lab, (const unsigned long long*)lines, n_lines); }
   hipLaunchKernelGGL(cc_flatten_kernel, dim3((uint32_t)cdiv(n, 256)), dim3(256), 0, s, d_lab, n);
   TRYS(hipMemsetAsync(d_size, 0, (n + 1) * 4, s));
   hipLaunchKernelGGL(cc_sample_kernel, dim3((uint32_t)cdiv(cdiv(n, 64), 256)), dim3(256), 0, s, d_lab, n, d_size);
@@ -1821,8 +1592,7 @@ static int build_fine_dict(shn_ctx* ctx, const shn_table* t, const uint8_t* d_fl
   hipError_t e = lines ? hipSuccess : shn_dev_malloc(&lines, n_lines * 128);
   if (e == hipSuccess) e = hipMemsetAsync(lines, 0, n_lines * 128, s);
   if (e != hipSuccess) { if (lines && !room) shn_dev_free(lines); return shn_fail(SHN_ERR_HIP, std::string("build_fine_dict: ") + hipGetErrorString(e)); }
-  static const int xcd_map = getenv("SHN_XCD_MAP") && getenv("SHN_XCD_MAP")[0] == '1';      // (off: measured below)
-  if (n) hipLaunchKernelGGL(fd_build_kernel, dim3((uint32_t)cdiv(n, 256)), dim3(256), 0, s, shn_tab_idx(t), d_flags, n, lines, n_lines - FD_HOPS, xcd_map);
+  if (n) hipLaunchKernelGGL(fd_build_kernel, dim3((uint32_t)cdiv(n, 256)), dim3(256), 0, s, shn_tab_idx(t), d_flags, n, lines, n_lines - FD_HOPS);
   *lines_out = lines; *n_lines_out = n_lines - FD_HOPS;          // (the look-ups hash into all but the spare lines at the end)
   return SHN_OK;
 }
@@ -2008,7 +1778,7 @@ extern "C" int shn_cc_create(shn_ctx* ctx, const shn_table* t, int world, int ra
     { int rc = build_fine_dict(ctx, t, c->d_flags, &lines, &n_lines); if (rc) return fail(rc); }
     hipLaunchKernelGGL(cc_init_kernel, dim3((uint32_t)cdiv(n, 256)), dim3(256), 0, s, c->d_lab, n);
     hipLaunchKernelGGL(cc_edges_kernel, dim3((uint32_t)std::min<uint64_t>(cdiv(n * 8, 256), 1u << 22)), dim3(256), 0, s, shn_tab_idx(t),
-                       c->d_flags, n, t->k, t->canonical, c->d_lab, (const unsigned long long*)lines, n_lines, cc_half_mode());
+                       c->d_flags, n, t->k, t->canonical, c->d_lab, (const unsigned long long*)lines, n_lines);
     hipLaunchKernelGGL(cc_flatten_kernel, dim3((uint32_t)cdiv(n, 256)), dim3(256), 0, s, c->d_lab, n);
     hipLaunchKernelGGL((cc_query_kernel<false>), dim3(c->q_grid), dim3(256), 0, s, t->d_keys, c->d_flags, n, t->k, t->canonical, world, rank, c->d_lab,
                        c->d_cnt, c->d_bc, (const uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr);
@@ -2344,21 +2114,9 @@ extern "C" int shn_extend_sharded(shn_ctx* ctx, const shn_table* t, uint32_t min
       unsigned long long* lines = nullptr;
       uint64_t n_lines = 0;
       { int rca = build_fine_dict(ctx, t, e->d_flags, &lines, &n_lines, e->d_claim); if (rca) { shn_ext_destroy(e); return rca; } }
-      // (off by default -- MEASURED at BASELINE configs[2], one box: 144 ms with two dictionary look-ups in flight, 170 ms with four
-      // (one wavefront per SIMD fewer), against 119.5 ms for the dictionary-only kernel, same records.  The look-ups that are left
-      // come one or two at a time behind their bucket offsets where the kernel above has eight in flight, and a trip's chain of
-      // bisection, ballots and shuffles is longer than the one fetch it replaces: fewer bytes, more latency.  HISTORY.md, round 5.)
-      static const bool rec_lds = getenv("SHN_REC_LDS") && getenv("SHN_REC_LDS")[0] == '1';
-      if (t->layout == 1 && rec_lds && t->n_buckets / REC_G + 1 < 0x7FFFFFFFULL) {
-        TimerRegion ta(ctx, T_EXT_ADJ);
-        hipLaunchKernelGGL(ext_records_lds_kernel, dim3((uint32_t)cdiv(t->n_buckets, REC_G)), dim3(256), 0, s, shn_tab_idx(t), e->d_flags, e->d_weight,
-                           (uint64_t)t->n_buckets, t->k, t->canonical, e->d_rec, (const unsigned long long*)lines,
-                           getenv("SHN_REC_ABLATE") ? atoi(getenv("SHN_REC_ABLATE")) : 0);
-      } else
       { TimerRegion ta(ctx, T_EXT_ADJ);                  // (one launch: bench.py's roofline entry for this kernel)
         hipLaunchKernelGGL(ext_records_kernel, dim3((uint32_t)std::min<uint64_t>(cdiv(n * 8, 256), 1u << 22)), dim3(256), 0, s, shn_tab_idx(t),
-                           e->d_flags, e->d_weight, n, t->k, t->canonical, e->d_rec, (const unsigned long long*)lines, n_lines,
-                           (getenv("SHN_XCD_MAP") && getenv("SHN_XCD_MAP")[0] == '1') ? 1 : 0); }
+                           e->d_flags, e->d_weight, n, t->k, t->canonical, e->d_rec, (const unsigned long long*)lines, n_lines); }
       (void)lines;                                       // (lives in the claims' block: overwritten when the claims are initialised below)
     }
     TRYE(hipGetLastError());
@@ -2401,7 +2159,7 @@ extern "C" int shn_extend_sharded(shn_ctx* ctx, const shn_table* t, uint32_t min
   // memo slots are never recycled within a call (a word per step ever walked by a memo-bearing walk); pool
   // indices live in 30 bits of a hint
   uint64_t pool_cap = std::min<uint64_t>(24 * n + (1ULL << 20), (1ULL << 30) - 1);
-  if (getenv("SHN_EXT_POOL_WORDS")) pool_cap = std::max<uint64_t>(256, std::min<uint64_t>(pool_cap, strtoull(getenv("SHN_EXT_POOL_WORDS"), nullptr, 10)));   // (tests: a full pool only costs time)
+  pool_cap = shn_env_u64("SHN_EXT_POOL_WORDS", pool_cap, 256, pool_cap);   // (tests: a full pool only costs time)
   TRYE(hipMemcpyAsync(e->d_order, svals, ns * 4, hipMemcpyDeviceToDevice, s));
   TRYE(hipMemsetAsync(e->d_nr, 0xFF, (ns + 1) * 4, s));
   TRYE(hipMemsetAsync(e->d_nl, 0, (ns + 1) * 4, s));
@@ -2410,7 +2168,7 @@ extern "C" int shn_extend_sharded(shn_ctx* ctx, const shn_table* t, uint32_t min
   // scratch: claim snapshot (d_claim2), memo pool + per-k1-mer hints, per-walk plan arrays
   void *ppool, *pplan;
   if ((rc = shn_ws(ctx)[27].get(pool_cap * 4, &ppool)) ||
-      (rc = shn_ws(ctx)[28].get((ns + 1) * (8 + 4 * 10 + 1 + 1 + 1 + 1 + 1 + 1 + 1) + 64, &pplan))) { shn_ext_destroy(e); return rc; }
+      (rc = shn_ws(ctx)[28].get((ns + 1) * (8 + 4 * 10 + 1 + 1 + 1 + 1 + 1 + 1) + 64, &pplan))) { shn_ext_destroy(e); return rc; }
   u64 *claim = e->d_claim, *snap = e->d_claim2;
   uint32_t* pool = (uint32_t*)ppool;
   uint64_t* moff = (uint64_t*)pplan;
@@ -2429,18 +2187,17 @@ extern "C" int shn_extend_sharded(shn_ctx* ctx, const shn_table* t, uint32_t min
   uint8_t* dirty = fill + ns + 1;
   uint8_t* ran = dirty + ns + 1;
   uint8_t* robbed = ran + ns + 1;
-  uint8_t* settled = robbed + ns + 1;     // walks that can never survive (ext_chain_has_lower): void for good, never launched
-  uint8_t* log_cnt = settled + ns + 1;    // claim logs: entries of a walk's last chunk
-  TRYE(hipMemsetAsync(robbed, 0, 2 * (ns + 1), s));
+  uint8_t* log_cnt = robbed + ns + 1;     // claim logs: entries of a walk's last chunk
+  TRYE(hipMemsetAsync(robbed, 0, ns + 1, s));
   TRYE(hipMemsetAsync(log_head, 0xFE, (ns + 1) * 4, s));
   uint8_t* robsat = nullptr;              // (development, SHN_EXT_XTIME: walks robbed while they sat out, until they run again)
   struct RobsatFree { uint8_t** p; ~RobsatFree() { if (*p) shn_dev_free(*p); } } robsat_free{&robsat};
-  if (getenv("SHN_EXT_XTIME")) { TRYE(shn_dev_malloc(&robsat, ns + 1)); TRYE(hipMemsetAsync(robsat, 0, ns + 1, s)); }
+  if (shn_env_set("SHN_EXT_XTIME")) { TRYE(shn_dev_malloc(&robsat, ns + 1)); TRYE(hipMemsetAsync(robsat, 0, ns + 1, s)); }
   TRYE(hipMemsetAsync(mvalid, 0, 2 * (ns + 1), s));
   TRYE(hipMemsetAsync(pool, 0xFF, pool_cap * 4, s));            // NONE32: "no entry"
   // (hints and seed ranks live in the records: ext_records_kernel wrote "none" into both)
   if (ns) hipLaunchKernelGGL(ext_seed_rank_kernel, dim3((uint32_t)cdiv(ns, 256)), dim3(256), 0, s, e->d_order, (uint64_t)ns, e->d_rec);
-  const bool want_dig = getenv("SHN_EXT_DIGEST") && getenv("SHN_EXT_DIGEST")[0] == '1';
+  const bool want_dig = shn_env_flag("SHN_EXT_DIGEST", false);
   if (want_dig) {
     int rd;
     if ((rd = ext_digest(ctx, e, 0, t->d_keys, n * 8, 1)) || (rd = ext_digest(ctx, e, 1, t->d_counts, n * 4, 2)) ||
@@ -2476,43 +2233,32 @@ extern "C" int shn_extend_sharded(shn_ctx* ctx, const shn_table* t, uint32_t min
   // passes over all claims whatever it re-runs.  tools/ext_blocks_probe.py: 51 rounds / 2.27 s -> 32 rounds / 2.15 s)
   const bool many = ns >= (1ULL << 24);
   unsigned long long lim0 = std::max<unsigned long long>(ns / (many ? 8 : 32), 4096), grow = 4;
-  if (getenv("SHN_EXT_LIMIT0")) lim0 = strtoull(getenv("SHN_EXT_LIMIT0"), nullptr, 10);
-  if (getenv("SHN_EXT_GROW")) grow = strtoull(getenv("SHN_EXT_GROW"), nullptr, 10);
-  const unsigned long long tail_div = getenv("SHN_EXT_TAIL") ? strtoull(getenv("SHN_EXT_TAIL"), nullptr, 10) : (many ? 0 : 8);   // last blocks = ns / 8 walks (0: off)
+  lim0 = shn_env_u64("SHN_EXT_LIMIT0", lim0);
+  grow = shn_env_u64("SHN_EXT_GROW", grow);
+  const unsigned long long tail_div = shn_env_u64("SHN_EXT_TAIL", many ? 0 : 8);   // last blocks = ns / 8 walks (0: off)
   uint32_t frozen = 0, limit = (uint32_t)std::min<unsigned long long>(ns, lim0);
   TRYE(hipMemsetAsync(dirty, 0, 2 * (ns + 1), s));               // dirty + ran
   TRYE(hipMemsetAsync(dirty, 1, limit, s));
   TRYE(hipMemsetAsync(owned, 0, (ns + 1) * 4, s));
   plan[6] = 64;                                                  // memo pool cursor: 64 words of NONE32 padding in front
   TRYE(hipMemcpyAsync(d_cnt + 10, plan + 6, 8, hipMemcpyHostToDevice, s));   // (from the pinned block, on the context's stream like everything else here)
-  auto tune = [](const char* name, uint32_t dflt) { const char* v = getenv(name); return v ? (uint32_t)strtoul(v, nullptr, 10) : dflt; };
-  const int precise_marks = (int)tune("SHN_EXT_PRECISE", 1);       // 0: the conservative rule (every walk standing next to a freed k1-mer)
-  const uint32_t long_walk = tune("SHN_EXT_LONG_WALK", LONG_WALK), memo_min = tune("SHN_EXT_MEMO_MIN", MEMO_MIN),
-                 promote_steps = tune("SHN_EXT_PROMOTE", PROMOTE_STEPS);
+  const int precise_marks = (int)shn_env_u64("SHN_EXT_PRECISE", 1);       // 0: the conservative rule (every walk standing next to a freed k1-mer)
+  const uint32_t long_walk = (uint32_t)shn_env_u64("SHN_EXT_LONG_WALK", LONG_WALK), memo_min = (uint32_t)shn_env_u64("SHN_EXT_MEMO_MIN", MEMO_MIN),
+                 promote_steps = (uint32_t)shn_env_u64("SHN_EXT_PROMOTE", PROMOTE_STEPS);
   // Bulk rounds: with hundreds of thousands of dirty walks the GPU is throughput-bound, not latency-bound, and one thread
   // per walk (one memory round trip per step, every lane busy) beats a wavefront per walk by an order of magnitude; memos
   // (which serve the latency-bound re-runs of a few long walks) are not made in such a round.  The expected number of
   // dirty walks is the block size when a block opens, else the count of the round before.
-  const unsigned long long bulk_min = getenv("SHN_EXT_BULK") ? strtoull(getenv("SHN_EXT_BULK"), nullptr, 10) : 262144ULL;
-  const unsigned long long dense_min = getenv("SHN_EXT_DENSE") ? strtoull(getenv("SHN_EXT_DENSE"), nullptr, 10) : (4ULL << 20);   // (BASELINE configs[2]: 262144 -> 954 ms, 2 M or 16 M -> 900 ms per extension)
-  const int seed_check = (int)tune("SHN_EXT_SEEDCHECK", 1);
-  const int first_look = (int)tune("SHN_EXT_FIRST_LOOK", 0);      // (measured at configs[2]: first-round launches 172-174 ms with it, 163-170 without: off)
+  const unsigned long long bulk_min = shn_env_u64("SHN_EXT_BULK", 262144);
+  const unsigned long long dense_min = shn_env_u64("SHN_EXT_DENSE", 4ULL << 20);   // (BASELINE configs[2]: 262144 -> 954 ms, 2 M or 16 M -> 900 ms per extension)
+  const int first_look = (int)shn_env_u64("SHN_EXT_FIRST_LOOK", 0);      // (measured at configs[2]: first-round launches 172-174 ms with it, 163-170 without: off)
   // bulk rounds: a thread walker that gets this far hands its walk to the packed second launch (0: it walks to the end itself, as until round 4)
-  const uint32_t bulk_promote = tune("SHN_EXT_PROMOTE_BULK", 0);      // (measured at BASELINE configs[2], round 5: 8 / 24 / 64 -> walk kernels 273 / 267 / 268 ms per step against 224 without -- the bulk rounds are bound by the random fetches of their steps, not by idle lanes; off)
-  const unsigned long long resume_waves = tune("SHN_EXT_RESUME_WAVES", 8192);
-  const bool skip_idle_begin = tune("SHN_EXT_MEMO_RELEASE", 1) != 0;          // rounds whose dirty walks all have a current memo release through it (ext_release_memo_kernel)
-  const unsigned long long memo_release_max = tune("SHN_EXT_MEMO_RELEASE_MAX", 65536);
+  const uint32_t bulk_promote = (uint32_t)shn_env_u64("SHN_EXT_PROMOTE_BULK", 0);      // (measured at BASELINE configs[2], round 5: 8 / 24 / 64 -> walk kernels 273 / 267 / 268 ms per step against 224 without -- the bulk rounds are bound by the random fetches of their steps, not by idle lanes; off)
+  const unsigned long long resume_waves = shn_env_u64("SHN_EXT_RESUME_WAVES", 8192);
+  const bool skip_idle_begin = shn_env_u64("SHN_EXT_MEMO_RELEASE", 1) != 0;          // rounds whose dirty walks all have a current memo release through it (ext_release_memo_kernel)
+  const unsigned long long memo_release_max = shn_env_u64("SHN_EXT_MEMO_RELEASE_MAX", 65536);
   int n_begin_skipped = 0;
-  const bool prepass = tune("SHN_EXT_PREPASS", 1) != 0;
-  // forced links followed on each side of a seed when its block opens (ext_chain_has_lower).  MEASURED at BASELINE configs[2] (round 6, one
-  // box, 4 steps each): hops 0 / 1 / 2 / 4 / 8 / 16 / 64 -> 0 / 78 / 88 / 96 / 99 / 100 / 100.5 M of the 186 M walks never launched, same
-  // digest, first-round walker 164 / 208 / 193 / 163 / 158 / 159 / 152 ms, walk steps 627 / 957 / 891 / 738 / 702 / 696 / 664 M, the walks'
-  // host time 0.608 / 0.687 / 0.671 / 0.638 / 0.629 / 0.632 / 0.631 s: the rule is exact and removes half of the walks -- the cheap half
-  // (seeds on clean chains: weakly covered transcripts; a well covered one has an error branch at every position, so no link is
-  // forced) -- and the survivors, started earlier than they would have been behind the void ones, walk further before a lower rank
-  // stops them.  A launch's time follows its steps' random lines (~5.5 per step at ~20 G lines/s; 623 M steps for the 422 M k1-mers finally claimed:
-  // tools/walk_waste_r06.py), not its walks.  Off by default.
-  const uint32_t settle_hops = tune("SHN_EXT_SETTLE_HOPS", 0);
+  const bool prepass = shn_env_u64("SHN_EXT_PREPASS", 1) != 0;
   // Claim logs (round 6; SHN_EXT_LOGS=0: off).  The begin pass streams every claim (11.6 GB at BASELINE configs[2], 2.7 ms) to find
   // those of the walks that re-run; 22 of a step's 25 rounds re-run walks that hold fewer than ten million claims between them, and
   // what kept them on the stream was a handful of claim holders per round WITHOUT a memo: walks that last ran in a bulk round (no
@@ -2521,15 +2267,15 @@ extern "C" int shn_extend_sharded(shn_ctx* ctx, const shn_table* t, uint32_t min
   // bulk walker writes the k1-mers it claims into a log of its own as it goes (a 4-byte store per step into a 32-byte chunk; a
   // wavefront reserves 64 chunks with one atomic), and a round whose claim holders all have a current memo or a log, and few
   // enough claims to give back, releases through those (ext_release_memo_kernel) instead of the stream.
-  const bool use_logs = tune("SHN_EXT_LOGS", 1) != 0 && bulk_promote == 0 && ns > 0;
-  const unsigned long long targeted_max_steps = getenv("SHN_EXT_TARGETED_MAX") ? strtoull(getenv("SHN_EXT_TARGETED_MAX"), nullptr, 10) : (12ULL << 20);
+  const bool use_logs = shn_env_u64("SHN_EXT_LOGS", 1) != 0 && bulk_promote == 0 && ns > 0;
+  const unsigned long long targeted_max_steps = shn_env_u64("SHN_EXT_TARGETED_MAX", 12ULL << 20);
   uint32_t* logpool = nullptr;
   struct LogFree { uint32_t** p; ~LogFree() { if (*p) shn_dev_free(*p); } } log_free{&logpool};
   uint64_t log_cap = use_logs ? std::min<uint64_t>(2 * n / 4 + (1u << 16), 0x7FFFFFF0ULL) : 0;
-  if (use_logs && getenv("SHN_EXT_LOG_CHUNKS")) log_cap = std::max<uint64_t>(LOG_SLAB, std::min<uint64_t>(log_cap, strtoull(getenv("SHN_EXT_LOG_CHUNKS"), nullptr, 10)));   // (tests: a pool that runs out -- the walks' logs are void and their rounds fall back to the begin pass)
+  if (use_logs) log_cap = shn_env_u64("SHN_EXT_LOG_CHUNKS", log_cap, LOG_SLAB, log_cap);   // (tests: a pool that runs out -- the walks' logs are void and their rounds fall back to the begin pass)
   if (use_logs) { TRYE(shn_dev_malloc(&logpool, log_cap * LOG_WORDS * 4)); TRYE(hipMemsetAsync(d_cnt + 26, 0, 8, s)); }
-  const uint32_t fresh_split = std::max<uint32_t>(1, std::min<uint32_t>(16, tune("SHN_EXT_FRESH_SPLIT", 1)));   // sub-launches of a block's first (bulk) round (measured at configs[2]: 1 / 4 / 7 / 10 -> 184 / 176 / 209 / 248 ms: every sub-launch waits for its longest walk; off)
-  const uint32_t fresh_split_min = tune("SHN_EXT_FRESH_SPLIT_MIN", 65536);                                       // ... of blocks of at least this many walks            // a block's first round settles the walks whose seed an earlier block holds (ext_plan_kernel)
+  const uint32_t fresh_split = (uint32_t)shn_env_u64("SHN_EXT_FRESH_SPLIT", 1, 1, 16);   // sub-launches of a block's first (bulk) round (measured at configs[2]: 1 / 4 / 7 / 10 -> 184 / 176 / 209 / 248 ms: every sub-launch waits for its longest walk; off)
+  const uint32_t fresh_split_min = (uint32_t)shn_env_u64("SHN_EXT_FRESH_SPLIT_MIN", 65536);                                       // ... of blocks of at least this many walks            // a block's first round settles the walks whose seed an earlier block holds (ext_plan_kernel)
   unsigned long long expect_dirty = limit;
   while (!converged && it < max_iterations) {
     const bool bulk = bulk_min && expect_dirty >= bulk_min;
@@ -2544,7 +2290,7 @@ extern "C" int shn_extend_sharded(shn_ctx* ctx, const shn_table* t, uint32_t min
       hipLaunchKernelGGL(ext_plan_kernel, dim3((uint32_t)cdiv(limit - frozen, 1024)), dim3(1024), 0, s, e->d_nr, e->d_nl, (uint64_t)limit, frozen,
                          mvalid, mR, mL, dirty, long_list, short_list, d_cnt + 2, bulk ? 0xFFFFFFFFu : long_walk, coarse,
                          (fresh_block && frozen > 0 && prepass) ? (const u64*)claim : (const u64*)nullptr, e->d_order, e->d_totw,
-                         (const Rec*)e->d_rec, fresh_block ? settle_hops : 0u, settled, d_cnt + 20, robsat, d_cnt + 21,
+                         robsat, d_cnt + 21,
                          use_logs ? (const uint32_t*)log_head : (const uint32_t*)nullptr, d_cnt + 24);
     // (pinned host memory: a pageable destination costs a staging copy kernel per round)
     TRYE(hipMemcpyAsync(plan, d_cnt + 2, 32, hipMemcpyDeviceToHost, s));
@@ -2625,10 +2371,9 @@ extern "C" int shn_extend_sharded(shn_ctx* ctx, const shn_table* t, uint32_t min
     A.promo_list = promo_list; A.promo_count = d_cnt + 13; A.res_cur = res_cur; A.res_info = res_info;
     A.chunk = dense ? nullptr : chunk;         // (dense rounds write nearly everywhere: their mark pass is dense, the walkers do not flag)
     A.robbed = robbed;
-    A.seed_check = seed_check;
     A.first_look = first_look;
     A.logpool = (use_logs && bulk) ? logpool : nullptr; A.log_head = log_head; A.log_cnt = log_cnt; A.log_cursor = d_cnt + 26; A.log_cap = log_cap;
-    A.steps_counter = d_cnt + 1; A.fresh_steps_counter = d_cnt + 16; A.wave_steps_counter = d_cnt + 64; A.dbg = (getenv("SHN_DEBUG") || getenv("SHN_EXT_XTIME")) ? d_cnt + 32 : nullptr;
+    A.steps_counter = d_cnt + 1; A.fresh_steps_counter = d_cnt + 16; A.wave_steps_counter = d_cnt + 64; A.dbg = (shn_env_set("SHN_DEBUG") || shn_env_set("SHN_EXT_XTIME")) ? d_cnt + 32 : nullptr;
     // long (wave per walk) and short (thread per walk) kernels are independent: overlap them on two streams
     if (plan[0]) {
       TRYE(hipEventRecord(ev_fork, s));
@@ -2638,7 +2383,7 @@ extern "C" int shn_extend_sharded(shn_ctx* ctx, const shn_table* t, uint32_t min
       TRYE(hipEventRecord(ev_join, aux));
     }
     double x_t0 = 0;
-    if (getenv("SHN_EXT_XTIME")) {   // (development: time of every thread-walker launch)
+    if (shn_env_set("SHN_EXT_XTIME")) {   // (development: time of every thread-walker launch)
        TRYE(hipStreamSynchronize(s)); timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); x_t0 = ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
     const bool was_fresh = fresh_block;
     if (fresh_block && bulk && fresh_split > 1 && plan[0] == 0 && limit - frozen >= fresh_split_min && !x_t0) {
@@ -2657,8 +2402,7 @@ extern "C" int shn_extend_sharded(shn_ctx* ctx, const shn_table* t, uint32_t min
         TRYE(hipMemsetAsync(d_cnt + 2, 0, 32, s));
         hipLaunchKernelGGL(ext_plan_kernel, dim3((uint32_t)cdiv(b - a, 1024)), dim3(1024), 0, s, e->d_nr, e->d_nl, (uint64_t)b, a,
                            mvalid, mR, mL, dirty, long_list, short_list, d_cnt + 2, 0xFFFFFFFFu, coarse,
-                           ((a > 0) && prepass) ? (const u64*)claim : (const u64*)nullptr, e->d_order, e->d_totw,
-                           (const Rec*)e->d_rec, settle_hops, settled, d_cnt + 20);
+                           ((a > 0) && prepass) ? (const u64*)claim : (const u64*)nullptr, e->d_order, e->d_totw);
         TRYE(hipMemcpyAsync(plan, d_cnt + 2, 32, hipMemcpyDeviceToHost, s));
         TRYE(hipStreamSynchronize(s));
         if (plan[2]) {
@@ -2718,11 +2462,10 @@ extern "C" int shn_extend_sharded(shn_ctx* ctx, const shn_table* t, uint32_t min
                          dense ? (const uint8_t*)nullptr : chunk, robsat);
       if (!dense) TRYE(hipMemsetAsync(chunk, 0, n_chunks, s)); }
     hipLaunchKernelGGL(ext_verify_kernel, dim3((uint32_t)cdiv(ns, 256)), dim3(256), 0, s, ran, robbed, (uint64_t)ns, dirty);
-    if (getenv("SHN_EXT_FAULT") && it + 1 == atoi(getenv("SHN_EXT_FAULT"))) TRYE(hipMemsetAsync(dirty, 0, ns + 1, s));   // (tests: lose every mark of this round)
-    if (getenv("SHN_EXT_ALLDIRTY")) { TRYE(hipMemsetAsync(dirty, 0, ns + 1, s)); TRYE(hipMemsetAsync(dirty + frozen, 1, limit - frozen, s)); }
+    if ((uint64_t)(it + 1) == shn_env_u64("SHN_EXT_FAULT", 0)) TRYE(hipMemsetAsync(dirty, 0, ns + 1, s));   // (tests: lose every mark of this round)
     it++;
 
-    if (getenv("SHN_DEBUG")) {
+    if (shn_env_set("SHN_DEBUG")) {
       unsigned long long chg = 0, cur = 0, mx[2] = {0, 0}, st_tr[2] = {0, 0};
       TRYE(hipMemcpyAsync(&st_tr[0], d_cnt + 1, 8, hipMemcpyDeviceToHost, s));
       TRYE(hipMemcpyAsync(&st_tr[1], d_cnt + 15, 8, hipMemcpyDeviceToHost, s));
@@ -2747,7 +2490,7 @@ extern "C" int shn_extend_sharded(shn_ctx* ctx, const shn_table* t, uint32_t min
   hipStreamDestroy(aux);
   hipEventDestroy(ev_fork);
   hipEventDestroy(ev_join);
-  if (converged && ns && getenv("SHN_EXT_AUDIT")) {
+  if (converged && ns && shn_env_set("SHN_EXT_AUDIT")) {
     WalkArgs A;
     memset(&A, 0, sizeof(A));
     A.order = e->d_order; A.adjR = rows_R(e->d_rec); A.adjL = rows_L(e->d_rec); A.weight = words_weight(e->d_rec);
@@ -2761,7 +2504,7 @@ extern "C" int shn_extend_sharded(shn_ctx* ctx, const shn_table* t, uint32_t min
     au[0] = plan[4]; au[1] = plan[5];
     if (au[0]) {
       fprintf(stderr, "[shn_extend] AUDIT: %llu walks are not at their fixpoint, lowest rank %llu of %llu (rounds %d)\n", au[0], au[1], ns, it);
-      if (atoi(getenv("SHN_EXT_AUDIT")) > 1) { shn_ext_destroy(e); return shn_fail(SHN_ERR_INTERNAL, "shn_extend: audit failed"); }
+      if (shn_env_u64("SHN_EXT_AUDIT", 0) > 1) { shn_ext_destroy(e); return shn_fail(SHN_ERR_INTERNAL, "shn_extend: audit failed"); }
     }
   }
   e->iterations = it;
@@ -2779,12 +2522,11 @@ extern "C" int shn_extend_sharded(shn_ctx* ctx, const shn_table* t, uint32_t min
   unsigned long long steps = 0, wsteps = 0, fsteps = 0, wslots[64];
   TRYE(hipMemcpyAsync(&steps, d_cnt + 1, 8, hipMemcpyDeviceToHost, s));          // thread-kernel steps
   TRYE(hipMemcpyAsync(&fsteps, d_cnt + 16, 8, hipMemcpyDeviceToHost, s));
-  { unsigned long long nset = 0; TRYE(hipMemcpyAsync(&nset, d_cnt + 20, 8, hipMemcpyDeviceToHost, s)); TRYE(hipStreamSynchronize(s)); e->settled_walks = nset; }
   TRYE(hipMemcpyAsync(wslots, d_cnt + 64, 64 * 8, hipMemcpyDeviceToHost, s));    // wavefront-kernel steps
   TRYE(hipStreamSynchronize(s));
   for (int i = 0; i < 64; i++) wsteps += wslots[i];
   steps += wsteps;
-  if (getenv("SHN_DEBUG")) {
+  if (shn_env_set("SHN_DEBUG")) {
     unsigned long long dbg[10];
     TRYE(hipMemcpyAsync(dbg, d_cnt + 32, 80, hipMemcpyDeviceToHost, s));
     TRYE(hipStreamSynchronize(s));
@@ -2808,7 +2550,6 @@ extern "C" uint64_t shn_ext_total_steps(const shn_ext* e) { return e ? e->total_
 extern "C" uint64_t shn_ext_wave_steps(const shn_ext* e) { return e ? e->wave_steps : 0; }
 extern "C" uint64_t shn_ext_fresh_steps(const shn_ext* e) { return e ? e->fresh_steps : 0; }
 extern "C" int shn_ext_dense_rounds(const shn_ext* e) { return e ? e->dense_rounds : 0; }
-extern "C" uint64_t shn_ext_settled_walks(const shn_ext* e) { return e ? e->settled_walks : 0; }
 
 extern "C" int shn_ext_stats_range(shn_ctx* ctx, const shn_ext* e, uint64_t lo, uint64_t n, uint32_t* n_right, uint32_t* n_left, uint64_t* tot_weight) {
   if (!ctx || !e || (n && (!n_right || !n_left || !tot_weight))) return shn_fail(SHN_ERR_ARG, "shn_ext_stats_range: NULL argument");

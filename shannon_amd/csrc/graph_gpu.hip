@@ -352,7 +352,7 @@ extern "C" int shn_unitigs_build(shn_ctx* ctx, const uint8_t* bases, const uint6
                                  int K, shn_unitigs** out) {
   if (!ctx || !out || (n_contigs && (!bases || !off || !part_of)) || K < 2 || K > 31) return shn_fail(SHN_ERR_ARG, "shn_unitigs_build: bad argument");
   *out = nullptr;
-  const bool dbg = getenv("SHN_DEBUG") != nullptr;
+  const bool dbg = shn_env_set("SHN_DEBUG");
   auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t0 = now();
   auto lap = [&](const char* what) { if (dbg) { double t = now(); fprintf(stderr, "[unitigs] %-34s %8.3f s\n", what, t - t0); t0 = t; } };

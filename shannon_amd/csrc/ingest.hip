@@ -180,14 +180,14 @@ extern "C" int shn_reads_ingest(shn_ctx* ctx, const uint8_t* text, uint64_t n_by
   if (format == 0) format = text[lead] == '@' ? 2 : 1;
   if (format != 1 && format != 2) return shn_fail(SHN_ERR_ARG, "shn_reads_ingest: bad format");
   const bool fastq = format == 2;
-  const bool dbg = getenv("SHN_DEBUG") != nullptr;
+  const bool dbg = shn_env_set("SHN_DEBUG");
   auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t_0 = now();
   double t_scan = 0, t_alloc = 0, t_parse = 0, t_wait = 0;
   const unsigned T = (unsigned)std::max(1, std::min(shn_host_cpus(), 64));
   // ranges of ~16 MB of text, cut at record starts
   uint64_t range_bytes = 16u << 20;
-  if (const char* e = getenv("SHN_INGEST_RANGE_BYTES")) range_bytes = std::max<uint64_t>(1, strtoull(e, nullptr, 10));     // (tests: many small ranges)
+  range_bytes = shn_env_u64("SHN_INGEST_RANGE_BYTES", range_bytes, 1);     // (tests: many small ranges)
   const uint64_t n_ranges = std::max<uint64_t>(1, std::min<uint64_t>(n_bytes / range_bytes + 1, 1u << 20));
   std::vector<Range> R(n_ranges);
   {
@@ -265,7 +265,7 @@ extern "C" int shn_reads_ingest(shn_ctx* ctx, const uint8_t* text, uint64_t n_by
   uint64_t cap = 0;
   for (auto& x : R) cap = std::max(cap, x.n_rec);
   uint64_t stage_bytes = 256ull << 20;
-  if (const char* e = getenv("SHN_INGEST_STAGE_BYTES")) stage_bytes = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+  stage_bytes = shn_env_u64("SHN_INGEST_STAGE_BYTES", stage_bytes, 1);
   cap = std::max<uint64_t>(cap, std::min<uint64_t>(N, stage_bytes / L + 1));
   // the pinned pair is kept between calls (pinning and unpinning 0.5 GB cost 70 of the 100 ms a 5 M-read file took); one ingest
   // at a time uses it
@@ -359,7 +359,7 @@ extern "C" int shn_reads_ingest_ragged(shn_ctx* ctx, const uint8_t* text, uint64
   const bool fastq = format == 2;
   const unsigned T = (unsigned)std::max(1, std::min(shn_host_cpus(), 64));
   uint64_t range_bytes = 16u << 20;
-  if (const char* e = getenv("SHN_INGEST_RANGE_BYTES")) range_bytes = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+  range_bytes = shn_env_u64("SHN_INGEST_RANGE_BYTES", range_bytes, 1);
   const uint64_t n_ranges = std::max<uint64_t>(1, std::min<uint64_t>(n_bytes / range_bytes + 1, 1u << 20));
   struct RRange { uint64_t b0 = 0, b1 = 0, n_rec = 0, rec0 = 0, bases = 0, base0 = 0; uint32_t max_len = 0; int bad = 0; };
   std::vector<RRange> R(n_ranges);

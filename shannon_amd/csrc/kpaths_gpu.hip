@@ -281,7 +281,7 @@ struct KpIndex { const unsigned long long* hkeys; uint64_t mask; const uint64_t*
 // their records (-1: a search ran too deep); first / last = the ends of the read's LAST path in that order, or the node the read lies
 // inside at its last such occurrence (mbgraph.py:1379-1384 sets Read.nodes again with every path)
 __device__ int kp_read_paths(const uint64_t* __restrict__ w, uint32_t L, const KpGraph& G, const KpIndex& X, uint32_t r, uint32_t st, uint32_t node0,
-                             uint32_t off0, const uint8_t* __restrict__ bases, int32_t* __restrict__ out, int32_t& first, int32_t& last,
+                             uint32_t off0, int32_t* __restrict__ out, int32_t& first, int32_t& last,
                              uint32_t* stk = nullptr, int max_depth = 0, uint32_t stride = 0) {
   first = -1; last = -1;
   if (st == 3) {
@@ -302,14 +302,7 @@ __device__ int kp_read_paths(const uint64_t* __restrict__ w, uint32_t L, const K
     const uint32_t nd = kp_node_of(G.off, X.n_nodes, p);
     const uint64_t left = G.off[nd + 1] - p;
     const uint32_t n = (uint32_t)min((uint64_t)L, left);
-    bool same = true;
-    if (G.pk) same = n <= (uint32_t)X.K || kp_same(w, (uint32_t)X.K, G.pk, p + (uint64_t)X.K, n - (uint32_t)X.K);
-    else
-    for (uint32_t i = X.K; i < n && same; i++) {
-      const uint32_t rb = (uint32_t)((w[i >> 5] >> (62 - 2 * (i & 31))) & 3ULL);
-      same = kp_code(bases[p + i]) == (int)rb;
-    }
-    if (!same) continue;
+    if (n > (uint32_t)X.K && !kp_same(w, (uint32_t)X.K, G.pk, p + (uint64_t)X.K, n - (uint32_t)X.K)) continue;
     if ((uint64_t)L <= left) { first = (int32_t)nd; last = (int32_t)nd; continue; }
     int32_t le = -1;
     const int wds = kp_dfs(w, L, G, r, nd, (uint32_t)(p - G.off[nd]), out ? out + words : nullptr, &le, stk, max_depth, stride);
@@ -337,14 +330,14 @@ __global__ void kp_search_all(RView v, KpGraph G, KpIndex X, uint8_t* __restrict
   const uint64_t* w = v.words + (v.woff ? v.woff[r] : r * v.wpr);
   const uint32_t node0 = (uint32_t)node_out[r], off0 = off_out[r];
   int32_t f, l;
-  const int need = kp_read_paths(w, L, G, X, (uint32_t)r, st, node0, off0, G.bases, nullptr, f, l, stk, KP_DEEP, 64);
+  const int need = kp_read_paths(w, L, G, X, (uint32_t)r, st, node0, off0, nullptr, f, l, stk, KP_DEEP, 64);
   bool done = need == 0;
   if (need > 0) {
     const unsigned long long at = atomicAdd(&counters[0], (unsigned long long)need);
     if (at + (unsigned long long)need <= cap) {
       const unsigned long long q = atomicAdd(&counters[2], 1ULL);
       if (q < rec_cap) {
-        kp_read_paths(w, L, G, X, (uint32_t)r, st, node0, off0, G.bases, paths + at, f, l, stk, KP_DEEP, 64);
+        kp_read_paths(w, L, G, X, (uint32_t)r, st, node0, off0, paths + at, f, l, stk, KP_DEEP, 64);
         rec_cnt[2 * q] = (uint32_t)r; rec_cnt[2 * q + 1] = cnt[r];
         done = true;
       }
@@ -575,7 +568,7 @@ int shn_known_paths_dev(shn_ctx* ctx, const shn_reads* reads, int K, const uint8
   TRYK(bufs.get(&d_pk, (pk_words + 2) * 8));
   TRYK(hipMemsetAsync(d_pk + pk_words, 0, 16, s));
   hipLaunchKernelGGL(kp_pack_kernel, dim3((uint32_t)cdiv(pk_words, 256)), dim3(256), 0, s, (const uint8_t*)d_bases, total, d_pk, pk_words);
-  KpGraph G{d_bases, d_off, kp->d_eoff, kp->d_edst, d_eov, (getenv("SHN_KP_PACKED") && getenv("SHN_KP_PACKED")[0] == '0') ? (const uint64_t*)nullptr : (const uint64_t*)d_pk};
+  KpGraph G{d_bases, d_off, kp->d_eoff, kp->d_edst, d_eov, (const uint64_t*)d_pk};
   KpIndex X{d_hkeys, T - 1, d_goff, d_occ, (uint32_t)n_nodes, K};
   // (kp_insert's count of bad nodes sits in d_cnt2[1]; the search keeps its own counters in [0], [2], [3])
   { TimerRegion tse(ctx, T_KP_SEARCH);

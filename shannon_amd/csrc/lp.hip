@@ -569,8 +569,7 @@ extern "C" int shn_lp_solve_batch(shn_ctx* ctx, uint32_t n_problems, const uint3
   std::vector<LpProblem> probs(n_problems);
   std::vector<uint32_t> bprob, bfirst, lprob, lfirst, cprob, cfirst, wprob, wfirst;       // blocks of the vertex kernel (state in HBM / in LDS) / of the centre kernel / chunks of the wavefront-per-trial kernel
   uint64_t lds_words = 0, coop_words = 0;
-  const char* coop_env = getenv("SHN_LP_COOP");
-  const bool use_coop = !(coop_env && coop_env[0] == '0');
+  const bool use_coop = shn_env_flag("SHN_LP_COOP", true);
   // the in-LDS trial kernel asks for up to LP_LDS_WORDS * 8 = 156 KB of dynamic LDS: asked for once per process; a device or driver
   // that does not grant it gets the HBM form of the same kernel for every problem
   static const bool lds_granted = []() {

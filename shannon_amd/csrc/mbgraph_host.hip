@@ -93,7 +93,7 @@ template <class V> static void sort_runs(V& v) {
 // partition, which bounds the stage, included.  Partitions are started largest first, so the large ones get their threads first.
 struct ThreadBudget {
   std::mutex mu; std::condition_variable cv; int avail;
-  ThreadBudget() { const int hw = shn_host_cpus(); avail = std::max(4, hw); if (getenv("SHN_GRAPH_HOST_THREADS")) avail = std::max(1, atoi(getenv("SHN_GRAPH_HOST_THREADS"))); total = avail; }
+  ThreadBudget() { const int hw = shn_host_cpus(); avail = (int)shn_env_u64("SHN_GRAPH_HOST_THREADS", (uint64_t)std::max(4, hw), 1, 1u << 20); total = avail; }
   int total;
   // large requests (the large partitions, which bound the stage) never wait -- they may overdraw the budget; small ones wait for it
   void acquire(int n) { n = std::min(n, total); std::unique_lock<std::mutex> lk(mu); if (n < 8) cv.wait(lk, [&] { return avail >= n; }); avail -= n; }
@@ -918,8 +918,8 @@ struct Graph {
     const uint64_t mask = K == 32 ? ~0ULL : ((1ULL << (2 * K)) - 1);
     // ---- device path (kpaths_gpu.hip): every read is classified where the reads are; the host searches only the reads that run
     // past the end of the node they start in, against an index of just their first K-mers
-    { const char* kv = getenv("SHN_GRAPH_KP_GPU");
-      if (ctx && K <= 31 && !(kv && kv[0] == '0') && n_rd() && ensure_dreads(&d_reads)) {
+    {
+      if (ctx && K <= 31 && shn_env_flag("SHN_GRAPH_KP_GPU", true) && n_rd() && ensure_dreads(&d_reads)) {
         std::string nb;
         std::vector<uint64_t> noff(1, 0);
         { size_t tot = 0; for (int n : order) tot += bases[n].size(); nb.reserve(tot); noff.reserve(order.size() + 1); }
@@ -1046,7 +1046,7 @@ struct Graph {
           if (!ensure_dreads(&d_reads)) { attrs_rc = shn_fail(SHN_ERR_INTERNAL, "find_known_paths: the distinct reads could not be gathered again"); return; }
           tk1 = nowk();
         }
-        const bool kp_dev_search = !(getenv("SHN_GRAPH_KP_SEARCH") && getenv("SHN_GRAPH_KP_SEARCH")[0] == '0');
+        const bool kp_dev_search = shn_env_flag("SHN_GRAPH_KP_SEARCH", true);
         const int rcs = kp_dev_search
             ? shn_known_paths_search(ctx, d_reads, K, (const uint8_t*)nb.data(), noff.data(), order.size(), eoff.data(), edst.data(), eov.data(), st.data(),
                                      nd.data(), no.data(), precs.data(), precs.size(), &precs_used)
@@ -1456,7 +1456,7 @@ static int mbgraph_run_rows_impl(shn_ctx* ctx, const shn_unitigs* ug, uint32_t p
   if (!ctx || !src_a || !host_a || (n_reads && !didx && !d_didx) || (paired && (!src_b || !host_b)) || !src_a->fixed_len ||
       (paired && src_b->fixed_len != src_a->fixed_len))
     return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run_rows: needs a context, fixed-length resident read sets and their host matrices");
-  const bool dbg = getenv("SHN_GRAPH_LAPS") && n_reads >= strtoull(getenv("SHN_GRAPH_LAPS"), nullptr, 10);
+  const bool dbg = shn_env_set("SHN_GRAPH_LAPS") && n_reads >= shn_env_u64("SHN_GRAPH_LAPS", 0);
   const double t0 = dbg ? Graph::tnow() : 0.0;
   const int rc = mbgraph_run_impl(ctx, ug->K, rows, n_rows, ug, part, nullptr, nullptr, nullptr, nullptr, n_reads, paired, SHN_ENC_CODES, nullptr, nullptr, out,
                                   src_a, src_b, didx, host_a, host_b, d_didx);
@@ -1495,7 +1495,7 @@ static int mbgraph_run_impl(shn_ctx* ctx, int K, const uint8_t* rows, uint64_t n
   g.L = n_reads ? (int)read_len0 : -1;
   g.SIZE_THRESHOLD = g.L;
   // SHN_DEBUG: the laps of every partition; SHN_GRAPH_LAPS=n: of the partitions with at least n routed reads
-  const bool dbg = getenv("SHN_DEBUG") != nullptr || (getenv("SHN_GRAPH_LAPS") && n_reads >= strtoull(getenv("SHN_GRAPH_LAPS"), nullptr, 10));
+  const bool dbg = shn_env_set("SHN_DEBUG") || (shn_env_set("SHN_GRAPH_LAPS") && n_reads >= shn_env_u64("SHN_GRAPH_LAPS", 0));
   g.laps = dbg;
   auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double tt = now();
@@ -1512,7 +1512,7 @@ static int mbgraph_run_impl(shn_ctx* ctx, int K, const uint8_t* rows, uint64_t n
     return 0;
   };
   const bool resident = ctx && src_a && (didx || d_didx) && src_a->fixed_len && (!paired || (src_b && src_b->fixed_len == src_a->fixed_len)) &&
-                        n_reads && read_len0 == src_a->fixed_len && (host_a || getenv("SHN_GRAPH_RESIDENT_READS") == nullptr);
+                        n_reads && read_len0 == src_a->fixed_len && (host_a || !shn_env_set("SHN_GRAPH_RESIDENT_READS"));
   if (resident) { g.src_a = src_a; g.src_b = paired ? src_b : nullptr; }
   const uint64_t N_in = src_a ? src_a->n_reads : 0;
   auto origin_of = [&](uint64_t j, uint32_t& row, uint8_t& flag) {
@@ -1533,7 +1533,7 @@ static int mbgraph_run_impl(shn_ctx* ctx, int K, const uint8_t* rows, uint64_t n
                    ug->e_src.data() + e0, ug->e_dst.data() + e0, ug->e_out_rank.data() + e0, ug->e_in_rank.data() + e0, e1 - e0);
     g.precondensed = true;
     n_kmer_nodes = ug->n_kmers[part];
-    if (getenv("SHN_GRAPH_CHECK")) {
+    if (shn_env_set("SHN_GRAPH_CHECK")) {
       if (!rows && n_rows == 0 && n1 != n0) return shn_fail(SHN_ERR_ARG, "SHN_GRAPH_CHECK needs the k1-mer rows");
       Graph h;
       h.K = K;
@@ -1541,9 +1541,9 @@ static int mbgraph_run_impl(shn_ctx* ctx, int K, const uint8_t* rows, uint64_t n
       const uint64_t hk = h.order.size();
       h.condense_all();
       if (hk != n_kmer_nodes || h.signature() != g.signature()) {
-        if (getenv("SHN_GRAPH_CHECK_DUMP")) {
-          FILE* fa = fopen((std::string(getenv("SHN_GRAPH_CHECK_DUMP")) + ".host").c_str(), "w"); if (fa) { fputs(h.signature().c_str(), fa); fclose(fa); }
-          FILE* fb = fopen((std::string(getenv("SHN_GRAPH_CHECK_DUMP")) + ".gpu").c_str(), "w"); if (fb) { fputs(g.signature().c_str(), fb); fclose(fb); }
+        if (const char* dump = shn_env_str("SHN_GRAPH_CHECK_DUMP")) {
+          FILE* fa = fopen((std::string(dump) + ".host").c_str(), "w"); if (fa) { fputs(h.signature().c_str(), fa); fclose(fa); }
+          FILE* fb = fopen((std::string(dump) + ".gpu").c_str(), "w"); if (fb) { fputs(g.signature().c_str(), fb); fclose(fb); }
         }
         return shn_fail(SHN_ERR_INTERNAL, "SHN_GRAPH_CHECK: GPU unitigs differ from load_k1mers + condense_all (partition " + std::to_string(part) + ": " +
                         std::to_string(n_kmer_nodes) + " / " + std::to_string(hk) + " K-mers, " + std::to_string(g.order.size()) + " / " +
@@ -1584,9 +1584,8 @@ static int mbgraph_run_impl(shn_ctx* ctx, int K, const uint8_t* rows, uint64_t n
   Scratch* sc = nullptr;
   // the distinct reads found on the device: with the host matrices always, with gathered rows for large sets
   uint64_t bulk_min = 1u << 17;                         // reads from which the duplicates are found in parallel (tests lower it)
-  if (getenv("SHN_GRAPH_BULK_MIN")) bulk_min = strtoull(getenv("SHN_GRAPH_BULK_MIN"), nullptr, 10);
-  const char* dd_env = getenv("SHN_GRAPH_DEVICE_DEDUP");
-  const bool dev_dedup = resident && (host_a || ((!dd_env || dd_env[0] != '0') && enc == SHN_ENC_CODES &&
+  bulk_min = shn_env_u64("SHN_GRAPH_BULK_MIN", bulk_min);
+  const bool dev_dedup = resident && (host_a || (shn_env_flag("SHN_GRAPH_DEVICE_DEDUP", true) && enc == SHN_ENC_CODES &&
                                                  std::min<uint64_t>(n_reads, cutoff + 1) * (paired ? 2 : 1) >= bulk_min));
   const size_t need_text = (size_t)std::min<uint64_t>(n_reads, cutoff + 1) * (paired ? 2 : 1) * (size_t)read_len0 / (dev_dedup ? 2 : 1);
   { std::lock_guard<std::mutex> lk(scratch_mu);
@@ -1619,10 +1618,9 @@ static int mbgraph_run_impl(shn_ctx* ctx, int K, const uint8_t* rows, uint64_t n
   g.origin_row.resize(0); g.origin_flag.resize(0);                      // (capacity kept; empty until a path fills them)
   // the fast form of the rows mode (graph_dev.h): the duplicate search leaves its arrays on the device, the host gets rows + strands
   // (for the lazily decoded text) and nothing else per read.  SHN_GRAPH_DEV_ATTRS=0: the host-array form below.
-  const char* dav = getenv("SHN_GRAPH_DEV_ATTRS");
-  const bool lazy_ok = host_a && !(getenv("SHN_GRAPH_LAZY_TEXT") && getenv("SHN_GRAPH_LAZY_TEXT")[0] == '0') && src_a && src_a->n_invalid == 0 &&
+  const bool lazy_ok = host_a && shn_env_flag("SHN_GRAPH_LAZY_TEXT", true) && src_a && src_a->n_invalid == 0 &&
                        (!paired || (src_b && src_b->n_invalid == 0));
-  if (dev_dedup && lazy_ok && g.ctx && K <= 31 && !(dav && dav[0] == '0')) {
+  if (dev_dedup && lazy_ok && g.ctx && K <= 31 && shn_env_flag("SHN_GRAPH_DEV_ATTRS", true)) {
     const uint64_t used = std::min<uint64_t>(n_reads, cutoff + 1);
     const uint64_t Lr = read_len0;
     double t_dec = now();
@@ -1654,8 +1652,7 @@ static int mbgraph_run_impl(shn_ctx* ctx, int K, const uint8_t* rows, uint64_t n
     if (dbg) fprintf(stderr, "[mbgraph]   distinct reads (GPU)   %8.3f s  used=%llu distinct=%llu\n", now() - t_dec, (unsigned long long)used, (unsigned long long)nd);
     StringInterner& R = g.rindex;
     R.hashes.assign(nd, 0);
-    const char* lzv = getenv("SHN_GRAPH_LAZY_TEXT");
-    const bool lazy = host_a && !(lzv && lzv[0] == '0') && src_a->n_invalid == 0 && (!paired || src_b->n_invalid == 0);
+    const bool lazy = host_a && shn_env_flag("SHN_GRAPH_LAZY_TEXT", true) && src_a->n_invalid == 0 && (!paired || src_b->n_invalid == 0);
     if (lazy) {
       g.lz_a = host_a; g.lz_b = host_b; g.lz_L = (uint32_t)Lr; g.lz_buf = sc->lazy_text(nd * Lr + 1);
       if (!g.lz_buf) return shn_fail(SHN_ERR_NOMEM, "shn_mbgraph_run: out of host memory for the reads' text");
@@ -1764,7 +1761,7 @@ static int mbgraph_run_impl(shn_ctx* ctx, int K, const uint8_t* rows, uint64_t n
     const unsigned hwc = (unsigned)shn_host_cpus();
     unsigned nt = std::min<unsigned>(32, std::max<unsigned>(1, hwc / 8 / (unsigned)std::max(1, active.n / 2)));
     nt = std::max<unsigned>(nt, (unsigned)std::min<uint64_t>(std::min<uint64_t>(32, std::max(1u, hwc / 2)), (used * (paired ? 2 : 1)) >> 18));
-    if (getenv("SHN_GRAPH_BULK_MIN")) nt = std::max(nt, 4u);
+    if (shn_env_set("SHN_GRAPH_BULK_MIN")) nt = std::max(nt, 4u);
     if (used * nm < bulk_min) nt = used < 4096 ? 1 : std::min<unsigned>(nt, (unsigned)(used / 2048));   // small sets: a few threads for the decode only
     BudgetGuard budget((int)nt);                          // held until the reads are numbered
     if (nt <= 1) work(0, used);

@@ -199,7 +199,7 @@ std::vector<int32_t> multilevel(const Graph& g0, int n_parts, int ufactor) {
     levels.push_back(Level{std::move(cur), std::move(cmap)});
     cur = std::move(c);
   }
-  const bool dbg = getenv("SHN_DEBUG") != nullptr;
+  const bool dbg = shn_env_set("SHN_DEBUG");
   auto now = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + ts.tv_nsec * 1e-9; };
   const double t_c = now();
   std::vector<int32_t> part = grow_partition(cur, n_parts);

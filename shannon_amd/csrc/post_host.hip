@@ -33,7 +33,7 @@ extern "C" int shn_find_reps(const uint8_t* names, const uint64_t* name_off, con
 static int find_reps_core(const uint8_t* const* nptr, const uint64_t* nlen, const uint8_t* const* sptr, const uint64_t* slen, uint64_t n, int ds, int r,
                           uint8_t* keep_out, PostDev* dev, const uint64_t* goff) {
   if (r < 1 || r > 32) return shn_fail(SHN_ERR_ARG, "shn_find_reps: r must be in [1,32]");
-  const bool dbgf = getenv("SHN_DEBUG") != nullptr || getenv("SHN_POST_LAPS") != nullptr;
+  const bool dbgf = shn_env_set("SHN_DEBUG") || shn_env_set("SHN_POST_LAPS");
   auto nowf = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + ts.tv_nsec * 1e-9; };
   const double tf0 = nowf();
   StringInterner ids(n + 16);
@@ -529,7 +529,7 @@ static int post_finalize_lines(std::vector<SV>& lines, std::vector<uint64_t>& li
       rec_li.push_back((uint32_t)li);
     }
   }
-  const bool dbgp = getenv("SHN_DEBUG") != nullptr || getenv("SHN_POST_LAPS") != nullptr;
+  const bool dbgp = shn_env_set("SHN_DEBUG") || shn_env_set("SHN_POST_LAPS");
   auto nowp = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + ts.tv_nsec * 1e-9; };
   const double tp0 = nowp();
   // ---- length sort: a dict keyed by header line (the last sequence of a repeated header line wins), by (len(seq line), header line)

@@ -174,7 +174,7 @@ extern "C" int shn_reads_dedup(shn_ctx* ctx, const shn_reads* a, const shn_reads
   }
   SHN_ENTER(ctx);
   hipStream_t s = ctx->stream; shn_use_stream(s);
-  const bool dbg = getenv("SHN_DEBUG") != nullptr;
+  const bool dbg = shn_env_set("SHN_DEBUG");
   auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t0 = now(), t_alloc = 0, t_up = 0, t_k = 0, t_scan = 0, t_alloc2 = 0;
   uint64_t T = 1024;

@@ -336,7 +336,7 @@ extern "C" int shn_route_reads_mode(shn_ctx* ctx, const shn_reads* r1, const shn
   uint32_t grid = (uint32_t)cdiv(N2, RBLK);
   // the one-line dictionary over the probe table (SHN_ROUTE_DICT=0: probes through the table)
   ProbeDict D{nullptr, 0};
-  if (probe->n >= 4096 && !(getenv("SHN_ROUTE_DICT") && getenv("SHN_ROUTE_DICT")[0] == '0')) {
+  if (probe->n >= 4096 && shn_env_flag("SHN_ROUTE_DICT", true)) {
     const uint64_t n_lines = probe->n / PD_PER_LINE + 1;
     void* pl;
     if (shn_ws(ctx)[31].get((n_lines + PD_HOPS + 1) * 128, &pl) == 0) {
@@ -405,7 +405,7 @@ extern "C" int shn_table_create(shn_ctx* ctx, const uint64_t* keys, const uint32
   if (!ctx || !out || (n && (!keys || !values))) return shn_fail(SHN_ERR_ARG, "shn_table_create: NULL argument");
   SHN_ENTER(ctx);
   hipStream_t s = ctx->stream; shn_use_stream(s);
-  if (n <= (1u << 22) && !getenv("SHN_TABLE_DEVICE_BUILD")) {
+  if (n <= (1u << 22) && !shn_env_set("SHN_TABLE_DEVICE_BUILD")) {
     // Small dictionaries (the graph stage's K-mer seed tables: a few 10^5 keys, one or two per partition, made by many host threads
     // at once) are laid out on the host -- bucket = top bits of fmix64(key), ascending inside a bucket, duplicates summed -- and
     // uploaded: three copies on the caller's stream instead of the dozen launches and syncs of the device pipeline, and no use of

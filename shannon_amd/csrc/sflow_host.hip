@@ -449,7 +449,7 @@ extern "C" int shn_sparse_flow_thread(shn_ctx* ctx, const shn_graph* const* grap
 extern "C" int shn_sparse_flow(shn_ctx* ctx, const shn_graph* const* graphs, uint32_t n_graphs, const char* const* snames, uint64_t seed, shn_sflow** out) {
   if (!ctx || !out || (n_graphs && (!graphs || !snames))) return shn_fail(SHN_ERR_ARG, "shn_sparse_flow: NULL argument");
   *out = nullptr;
-  const bool dbg = getenv("SHN_DEBUG") != nullptr || getenv("SHN_SFLOW_LAPS") != nullptr;
+  const bool dbg = shn_env_set("SHN_DEBUG") || shn_env_set("SHN_SFLOW_LAPS");
   auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_lap = now(), t_adv = 0, t_lp = 0, t_fin = 0, t_pack = 0;
   size_t n_small_rounds = 0, n_pend_total = 0; uint64_t n_trials_total = 0;
@@ -535,7 +535,7 @@ extern "C" int shn_sparse_flow(shn_ctx* ctx, const shn_graph* const* graphs, uin
     const unsigned free_ = cpus > busy ? cpus - busy : 0u;
     return beside ? std::max(2u, std::min(32u, free_ / calls)) : std::max(1u, std::min(32u, cpus));
   };
-  static const unsigned spin_alone = getenv("SHN_SFLOW_SPIN_US") ? (unsigned)atoi(getenv("SHN_SFLOW_SPIN_US")) : 400u;
+  static const unsigned spin_alone = (unsigned)shn_env_u64("SHN_SFLOW_SPIN_US", 400);
   const unsigned nt_max = small_job ? 1u : std::max(2u, std::min(32u, cpus));
   unsigned nt = threads_now();
   SflowPool pool(nt_max > 1 ? nt_max - 1 : 0);
@@ -649,7 +649,7 @@ extern "C" int shn_sparse_flow(shn_ctx* ctx, const shn_graph* const* graphs, uin
   // The components hold ~10^2 small vectors each (26 ms to give back on 16 threads at BASELINE configs[2]): they go to a
   // background thread, which frees them while the caller merges the transcripts; the thread of the call before is joined first, the
   // last one when the library is unloaded.  SHN_SFLOW_FREE_NOW=1: on the host threads, before returning.
-  if (getenv("SHN_SFLOW_FREE_NOW")) parallel([&](size_t k) { Component gone; std::swap(gone, comps[k]); });
+  if (shn_env_set("SHN_SFLOW_FREE_NOW")) parallel([&](size_t k) { Component gone; std::swap(gone, comps[k]); });
   else {
     struct Reaper {
       std::mutex mu; std::thread t;

@@ -1,7 +1,7 @@
 // Host-side (C++) contig bookkeeping of extension_correction.run_correction, rows a5-a6:
 // duplicate_check (extension_correction.py:247-270) and the contig graph by shared K-mers
 // (:372-397), sequential over the candidate contigs in seed order exactly as the reference.
-// This is control logic over contig bases (the k-mer-level walks are on the GPU, extend.hip); it is
+// This is control logic over contig bases (the k-mer-level walks are on the GPU, extend.hip; their contigs come out of ext_results.hip); it is
 // native code because at 10M reads ~2,000 candidate contigs x ~2,000 bases of Python dict work
 // were a third of the host time.
 #include "contig_graph.h"

@@ -31,7 +31,7 @@ __device__ __forceinline__ uint64_t probe_key(const RView& v, uint64_t r, uint32
   return shn_revcomp(shn_extract(v.words + wb, len - k - pos, k), k);
 }
 
-// ---- the probe table as a one-line dictionary (the scheme of the adjacency build, extend.hip): a 128-byte line holds ten keys (80
+// ---- the probe table as a one-line dictionary (the scheme of the adjacency build, k1dict.h): a 128-byte line holds ten keys (80
 // bytes), their ten values (40 bytes) and the number of keys that hashed there; four keys per line on average, a full line sends
 // its keys on to the next (PD_HOPS of them, then the table itself).  HBM serves 128 bytes per request whatever is asked for, and a
 // probe through the table was three requests (bucket offsets, keys, value): 186 GB per launch for 19 GB of algorithmic bytes.

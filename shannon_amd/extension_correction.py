@@ -1,7 +1,7 @@
 """Contig extension / error correction / contig-graph components -- host mirror of the
 reference's extension_correction.py (rows a3-a7) over the HIP walk kernel.
 
-Device (csrc/extend.hip): load_kmers + lowComplexity filter, seed ordering, the greedy
+Device (csrc/k1dict.hip, extend.hip, ext_results.hip): load_kmers + lowComplexity filter, seed ordering, the greedy
 bidirectional walks (the reference's dominant Python stage, extension_correction.py:334-354).
 Host (here): accept filter (:361), duplicate_check (:247-270), allowed set, contig graph by
 shared K-mers (:366-397), DFS components and the METIS / contig / remaining-bin files

@@ -428,24 +428,21 @@ def test_gpu_contig_stage_on_many_genes(ctx):
 
 
 @pytest.mark.parametrize("env", [{"SHN_EXT_BULK": "1"}, {"SHN_EXT_BULK": "1", "SHN_EXT_DENSE": "1"}, {"SHN_EXT_BULK": "1", "SHN_EXT_DENSE": "1000000000"},
-                                 {"SHN_EXT_BULK": "1", "SHN_EXT_PROMOTE_BULK": "0"}, {"SHN_EXT_BULK": "1", "SHN_EXT_PROMOTE_BULK": "1", "SHN_EXT_RESUME_WAVES": "3"},
-                                 {"SHN_EXT_BULK": "1", "SHN_EXT_PROMOTE_BULK": "5", "SHN_EXT_DENSE": "1"}, {"SHN_EXT_BULK": "1", "SHN_EXT_PREPASS": "0"},
-                                 {"SHN_EXT_PREPASS": "0"}, {"SHN_EXT_MEMO_RELEASE": "0"}, {"SHN_EXT_MEMO_RELEASE_MAX": "3"}, {"SHN_EXT_FIRST_LOOK": "1", "SHN_EXT_BULK": "1"},
-                                 {"SHN_EXT_BULK": "1", "SHN_EXT_FRESH_SPLIT": "5", "SHN_EXT_FRESH_SPLIT_MIN": "32"},
-                                 {"SHN_EXT_BULK": "1", "SHN_EXT_FRESH_SPLIT": "3", "SHN_EXT_FRESH_SPLIT_MIN": "32", "SHN_EXT_DENSE": "1"},
+                                 {"SHN_EXT_BULK": "1", "SHN_EXT_PREPASS": "0"},
+                                 {"SHN_EXT_PREPASS": "0"}, {"SHN_EXT_MEMO_RELEASE": "0"}, {"SHN_EXT_MEMO_RELEASE_MAX": "3"},
                                  # claim logs (round 6): off; with every round a bulk round releasing through the logs; with a pool that
                                  # runs out after a few hundred chunks (void logs: those rounds fall back to the begin pass); with rounds that
                                  # may give back at most 50 claims through memos / logs
                                  {"SHN_EXT_LOGS": "0"}, {"SHN_EXT_BULK": "1", "SHN_EXT_DENSE": "1000000000", "SHN_EXT_LOGS": "1"},
                                  {"SHN_EXT_BULK": "1", "SHN_EXT_DENSE": "1000000000", "SHN_EXT_LOG_CHUNKS": "256"},
                                  {"SHN_EXT_BULK": "1", "SHN_EXT_LOG_CHUNKS": "64"}, {"SHN_EXT_BULK": "2000", "SHN_EXT_TARGETED_MAX": "50"},
-                                 {"SHN_EXT_BULK": "2000", "SHN_EXT_DENSE": "1000000000"}])
+                                 {"SHN_EXT_BULK": "2000", "SHN_EXT_DENSE": "1000000000"}],
+                         # (the names the sets had in the longer list this one was cut from: a set keeps its name in the reports)
+                         ids=["env%d" % i for i in (0, 1, 2, 6, 7, 8, 9, 13, 14, 15, 16, 17, 18)])
 def test_bulk_rounds_give_the_same_contigs(ctx, env, monkeypatch):
     """Every round as a bulk round (thread walker only, no snapshot reads in a block's first round), with the begin / mark passes
-    as they come, all dense or all following the line flags; the hand-over of long walks to the packed second launch
-    (ext_walk_resume_kernel) off, after one step with three wavefronts for all of them, after five; the settling of void walks in a
-    block's first round off; the release of re-run walks' claims by the streaming begin pass only / through memos only in rounds of
-    at most three walks; the first look at the candidates' claims; a block's first round in 5 / 3 rank-ordered sub-launches: the same
+    as they come, all dense or all following the line flags; the settling of void walks in a block's first round off; the release
+    of re-run walks' claims by the streaming begin pass only / through memos only in rounds of at most three walks: the same
     walks, contigs and connections as the default path of a small table."""
     from shannon_amd import device, synth, extension_correction as ec
     (r1, r2), _ = synth.make_dataset(60000, 20, seed=91)
@@ -455,6 +452,54 @@ def test_bulk_rounds_give_the_same_contigs(ctx, env, monkeypatch):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         monkeypatch.setenv("SHN_EXT_AUDIT", "2")
+        got = ec.run_correction(ctx, t, 3, 75, 500, want_allowed=False)
+        assert got.contigs == ref.contigs and got.connections == ref.connections and len(ref.contigs) > 20
+    finally:
+        t.close()
+
+
+@pytest.mark.parametrize("case", ["no_k1mers", "no_seed"])
+def test_extension_of_nothing(ctx, case):
+    """A table without a k1-mer (eight reads of 20 bases, K+1 = 26) and a table none of whose k1-mers is heavy enough to be a seed
+    (min_weight = 1,000,000): no walk, no round, empty statistics / accept / emit results and no contigs -- as the oracle's seed
+    loop on the same counts, which walks nothing."""
+    from shannon_amd import device, synth, extension_correction as ec
+    from oracle import extension
+    if case == "no_k1mers":
+        codes, min_weight = np.random.RandomState(3).randint(0, 4, (8, 20)).astype(np.uint8), 3
+    else:
+        (r1, r2), _ = synth.make_dataset(2000, 2, seed=5)
+        codes, min_weight = np.concatenate([r1, r2]), 1000000
+    t = device.count_k1mers(ctx, [device.Reads.from_codes(ctx, codes)], 26)
+    try:
+        keys, cnts = t.dump()
+        assert (len(keys) == 0) == (case == "no_k1mers")
+        tab = {device.key_to_str(k, 26): int(c) for k, c in zip(keys, cnts)}
+        kmers, k1 = extension.load_kmers([(k, tab[k]) for k in sorted(tab, reverse=True)])
+        assert list(extension.python_walks(kmers, k1, min_weight)) == []
+        ext = ec.Extension(ctx, t, min_weight)
+        assert ext.n_walks == 0 and ext.iterations == 0 and ext.total_steps == 0
+        assert [len(a) for a in ext.stats()] == [0, 0, 0]
+        assert [len(a) for a in ext.live_stats(0)] == [0, 0, 0, 0]
+        assert [len(a) for a in ext.accept(26, 75, 3)] == [0, 0]
+        assert ext.emit(np.zeros(0, np.uint32), np.zeros(0, np.int64)) == []
+        ext.close()
+        res = ec.run_correction(ctx, t, min_weight, 75, 500, want_allowed=False)
+        assert res.contigs == [] and res.iterations == 0
+    finally:
+        t.close()
+
+
+def test_extension_error_leaves_the_context_usable(ctx):
+    """An extension that may run one round only does not converge and says so (a clean error return from the middle of the round
+    loop, not a device fault); the next extension on the same context gives the contigs and connections of the one before."""
+    from shannon_amd import device, synth, extension_correction as ec
+    (r1, r2), _ = synth.make_dataset(60000, 20, seed=91)
+    t = device.count_k1mers(ctx, [device.Reads.from_codes(ctx, np.concatenate([r1, r2]))], 26)
+    try:
+        ref = ec.run_correction(ctx, t, 3, 75, 500, want_allowed=False)
+        with pytest.raises(Exception, match="did not converge"):
+            ec.Extension(ctx, t, 3, max_iterations=1)
         got = ec.run_correction(ctx, t, 3, 75, 500, want_allowed=False)
         assert got.contigs == ref.contigs and got.connections == ref.connections and len(ref.contigs) > 20
     finally:

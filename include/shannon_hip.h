@@ -359,6 +359,23 @@ int shn_routes_download_range(shn_ctx* ctx, const shn_routes* r, uint64_t lo, ui
 int shn_filter_fp_hits(shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off, const uint32_t* t_part, uint64_t n_tr, uint32_t n_parts,
                        const shn_reads* r1, const shn_reads* r2, const shn_routes* routes, const uint32_t* h_pid, const uint32_t* h_frag,
                        uint64_t n_host, int strand_specific, uint32_t max_span, uint32_t* hits, uint64_t* stats);
+/* The two halves of shn_filter_fp_hits, for a job whose routes lie on several ranks (filter_FP.py:29-55 as run_MB_SF_fn.py:272-277
+ * runs it per partition: the depth file of a partition is the union of what every rank's pairs cover, because a fragment, its
+ * minimum cost and the placements that attain it belong to one rank and one partition).  shn_filter_fp_hits equals
+ * shn_filter_fp_cover on every share of the routes, then shn_filter_fp_count over the bitmaps.
+ *
+ * coverage bitmap of the concatenated text: bit (g & 63) of word (g >> 6) is set iff base g of the text lies under a best
+ * concordant placement of a fragment named by THESE routes.  cover: host, cdiv(t_off[n_tr], 64) words (written whole).
+ * Every other argument as shn_filter_fp_hits. */
+int shn_filter_fp_cover(shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off, const uint32_t* t_part, uint64_t n_tr, uint32_t n_parts,
+                        const shn_reads* r1, const shn_reads* r2, const shn_routes* routes, const uint32_t* h_pid, const uint32_t* h_frag,
+                        uint64_t n_host, int strand_specific, uint32_t max_span, uint64_t* cover, uint64_t* stats);
+/* hits[j] = popcount over transcript j's bases of the OR of n_covers bitmaps (the depth file's line count per transcript,
+ * filter_FP.py:7-13, run_MB_SF_fn.py:272-277).  covers: n_covers * n_words words (host, one bitmap after the other), each holding
+ * the text positions [64 * word0, 64 * (word0 + n_words)); t_off absolute, every transcript inside that window (SHN_ERR_ARG
+ * otherwise, and for n_covers == 0).  Bits of the boundary words that belong to neighbouring transcripts are ignored. */
+int shn_filter_fp_count(shn_ctx* ctx, const uint64_t* covers, uint32_t n_covers, uint64_t n_words, uint64_t word0, const uint64_t* t_off,
+                        uint64_t n_tr, uint32_t* hits);
 
 /* ---- K-mer seed scans of reads against graph nodes -----------------------------------------------
  * Replace the per-read Python loops of Read.find_bridging_reads (mbgraph.py:88-111) and known_paths

@@ -14,6 +14,7 @@ are accepted and reported as not built.
                                  transcript stays only if the pairs cover 90 % of its bases (shannon.py:170-195, filter_FP.py; the aligner is
                                  the rule of DESIGN.md "filter_FP", run on the GPU); per partition TEMP/<sample>_<name>algo_output/ then holds
                                  reconstructed.fasta (filtered), reconstructed_org.fasta and rec.log
+                                 (with -p N as well: the ranks' coverage is merged at the partitions' owners, the result is the one-process one)
     python shannon.py -o OUT --left r1.fasta --right r2.fasta -p 8        # one rank per GPU (the reference's -p nJobs, shannon.py:527-566)
 
 -p N / --gpus N: the reference fans its partitions out over nJobs processes (GNU parallel, shannon.py:527-566); here the N jobs
@@ -80,7 +81,8 @@ def launch_ranks(n, args):
 def rank_main(out_dir, reads, K, partition_size, min_weight, min_length, double_stranded, ignored, noted, kmer_hard_cutoff=1, filter_fp=False):
     """one rank of an N-rank run: its slice of the reads (by index, contiguous), shannon_amd.distributed.assemble_distributed,
     rank 0 writes OUT/ (shannon.fasta, log.txt, TEMP/<sample>_allalgo_output/all_reconstructed.fasta and the contig files; the
-    per-partition graph files stay with the ranks that owned the partitions)"""
+    per-partition graph files stay with the ranks that owned the partitions; with --filter_FP the three files of every partition,
+    TEMP/<sample>_<name>algo_output/reconstructed.fasta, reconstructed_org.fasta and rec.log)"""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -126,9 +128,6 @@ def rank_main(out_dir, reads, K, partition_size, min_weight, min_length, double_
         say("WARNING: flags outside the hot path ignored: " + " ".join(ignored))
     for msg in noted:
         say("NOTE: " + msg)
-    if filter_fp:
-        say("WARNING: --filter_FP is not applied on the N-rank path (-p N / --gpus N): the transcripts are NOT filtered; run with one "
-            "process for the filter")
     ctx = device.Context(dev_index)
     T = {}
     t0 = time.time()
@@ -181,7 +180,7 @@ def rank_main(out_dir, reads, K, partition_size, min_weight, min_length, double_
     say("Processed No of reads:%d, Avg. Read length: %.2f (every rank holds a slice of %d of them)" % (n, q1.shape[1] if n else 0, hi - lo))
     ops = distributed.GpuOps(ctx, d1, d2, kfc.ReadStore(q1, q2), K)
     res = distributed.assemble_distributed(ops, K, partition_size, sample, 0, timings=T, double_stranded=double_stranded,
-                                           min_weight=min_weight, min_length=min_length, kmer_hard_cutoff=kmer_hard_cutoff)
+                                           min_weight=min_weight, min_length=min_length, kmer_hard_cutoff=kmer_hard_cutoff, filter_fp=filter_fp)
     rc = 0
     if rank == 0:
         say("%d K-mers loaded; %d contigs; %d partitions" % (res["n_k1mers"], len(res["contigs"]), len(res["partitions"])))
@@ -189,6 +188,21 @@ def rank_main(out_dir, reads, K, partition_size, min_weight, min_length, double_
         os.makedirs(ai)
         with open(os.path.join(ai, "k1mer.dict_contig"), "w") as f:
             f.write("".join(c + "\n" for c in res["contigs"]))
+        if "filter_logs" in res:
+            # filter_FP.py:52-55: the filtered transcripts take the place of reconstructed.fasta, the sparse flow's stay beside them
+            for name in res["partitions"]:
+                base = os.path.join(temp, "%s_%s" % (sample, name))
+                os.makedirs(base + "algo_output")
+                kept, org = res["partitions"][name], res["partitions_org"][name]
+                open(os.path.join(base + "algo_output", "reconstructed.fasta"), "w").write(kept)
+                open(os.path.join(base + "algo_output", "reconstructed_org.fasta"), "w").write(org)
+                open(os.path.join(base + "algo_output", "rec.log"), "w").write(res["filter_logs"][name])
+                say("%s has completed: %d transcripts, %d after --filter_FP" % (base, org.count(">"), kept.count(">")))
+            st = res["filter_fp_stats"]
+            say("--filter_FP: %d of %d routed fragments placed as concordant pairs; %d of %d transcripts kept"
+                % (st.get("placed", 0), st.get("routes", 0), st.get("kept", 0), st.get("transcripts", 0)))
+        elif "filter_fp_note" in res:
+            say("NOTE: " + res["filter_fp_note"])
         alld = os.path.join(temp, sample + "_allalgo_output")
         os.makedirs(alld)
         with open(os.path.join(alld, "all_reconstructed.fasta"), "w") as f:

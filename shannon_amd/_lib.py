@@ -71,6 +71,8 @@ SIGNATURES = {
     "shn_routes_bounds": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, vp, vp]),
     "shn_routes_download_range": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, vp]),
     "shn_filter_fp_hits": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_uint32, vp, vp]),
+    "shn_filter_fp_cover": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_uint32, vp, vp]),
+    "shn_filter_fp_count": (C.c_int, [vp, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp]),
     "shn_lp_solve_batch": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]),
     "shn_lp_set_rule": (C.c_int, [vp, C.c_int]),
     "shn_lp_stats": (C.c_int, [vp, vp, C.c_int]),

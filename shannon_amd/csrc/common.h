@@ -51,8 +51,9 @@ enum {
   T_SK_HIST, T_SK_EMIT, T_SK_HIST2, T_SK_SCATTER2, T_SK_BUCKETS, T_SK_BIG, T_EXT_WALK_FRESH, T_EXT_BEGIN, T_SK_BUCKETS2,
   // round 6: the kernels of the contig stage, of the read -> graph mapping and the LP trials, one launch per region (bench.py's kernel table)
   T_CG_SORT, T_CG_HITS, T_CG_COVER, T_CG_COMPACT, T_KP_SEARCH, T_KP_CLASSIFY, T_SEED_SCAN, T_DD_INSERT, T_LP_TRIALS, T_EXT_AUDIT,
-  // --filter_FP (filter_fp.hip): index of the transcripts' 15-mers, mapping + marking of the routed pairs, per-transcript count
-  T_FFP_INDEX, T_FFP_MAP, T_FFP_COUNT, T_N = 48
+  // --filter_FP (filter_fp.hip): index of the transcripts' 15-mers, mapping + marking of the routed pairs, per-transcript count;
+  // the count over the OR of several ranks' bitmaps
+  T_FFP_INDEX, T_FFP_MAP, T_FFP_COUNT, T_FFP_MERGE, T_N = 49
 };
 
 // grow-only device workspace slot (process-wide ones: g_shn_ws below; per-context ones: shn_ctx::cws)

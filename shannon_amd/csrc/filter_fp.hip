@@ -16,6 +16,8 @@
 //           costs loads only.  (The rate of scattered 64-bit integer ORs on this chip is not measured anywhere in this
 //           repository; the load-first form is what keeps the kernel from depending on it.)
 //   count   bits set inside every transcript's range.
+//   merge   (N ranks) the same count over the OR of several bitmaps: every rank marks what ITS routes cover
+//           (shn_filter_fp_cover), the owner of a partition counts over all of them (shn_filter_fp_count).
 //
 // The thread-per-route shape trades lane divergence (mates differ in how many candidates their seeds name) for having no
 // intermediate candidate lists at all; DESIGN.md gives the measured time next to the byte models below.
@@ -307,6 +309,34 @@ __global__ void ffp_count_kernel(const unsigned long long* __restrict__ cov, con
   hits[j] = n;
 }
 
+// The OR of n_covers bitmaps and the masked count of a transcript's bits in one pass.  One wave a transcript: lane l takes the words
+// first + l, first + l + 64, ... of the transcript's range and reads that word of every bitmap, so the 64 lanes of a load read 512
+// consecutive bytes of one bitmap; the lanes' counts meet in a shuffle reduction.  (A thread a transcript -- ffp_count_kernel's shape
+// -- would walk n_covers bitmaps with a stride of one transcript between neighbouring lanes.)  Word w of the text is word w - word0
+// of every bitmap; the host has checked that every transcript lies inside the window.
+__global__ __launch_bounds__(FFP_BLOCK) void ffp_merge_count_kernel(const unsigned long long* __restrict__ covers, uint32_t n_covers, uint64_t n_words,
+                                                                    uint64_t word0, const uint64_t* __restrict__ t_off, uint64_t n_tr,
+                                                                    uint32_t* __restrict__ hits) {
+  const uint64_t j = (uint64_t)blockIdx.x * (FFP_BLOCK / 64) + (threadIdx.x >> 6);
+  if (j >= n_tr) return;                                   // (the whole wave)
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t g0 = t_off[j], g1 = t_off[j + 1];
+  uint32_t n = 0;
+  if (g1 > g0) {
+    const uint64_t last = (g1 - 1) >> 6;
+    for (uint64_t w = (g0 >> 6) + lane; w <= last; w += 64) {
+      const uint64_t b0 = w << 6;
+      const uint32_t lo = (uint32_t)((g0 > b0 ? g0 : b0) - b0), hi = (uint32_t)((g1 < b0 + 64 ? g1 : b0 + 64) - b0);
+      const unsigned long long m = (hi - lo == 64 ? ~0ULL : ((1ULL << (hi - lo)) - 1ULL)) << lo;
+      unsigned long long v = 0;
+      for (uint32_t c = 0; c < n_covers; c++) v |= covers[(uint64_t)c * n_words + (w - word0)];
+      n += (uint32_t)__popcll(v & m);
+    }
+  }
+  for (int off = 32; off; off >>= 1) n += __shfl_down(n, off, 64);
+  if (lane == 0) hits[j] = n;
+}
+
 static int ffp_set(shn_ctx* ctx, ShnDevBufs& bufs, const shn_reads* r, bool want_rc, FfpSet* out, uint64_t* rc_bytes) {
   hipStream_t s = ctx->stream;
   const bool use_mask = r->n_invalid != 0 && r->d_mask && r->d_bad;
@@ -332,23 +362,25 @@ static int ffp_set(shn_ctx* ctx, ShnDevBufs& bufs, const shn_reads* r, bool want
   return SHN_OK;
 }
 
-extern "C" int shn_filter_fp_hits(shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off, const uint32_t* t_part, uint64_t n_tr,
-                                  uint32_t n_parts, const shn_reads* r1, const shn_reads* r2, const shn_routes* routes, const uint32_t* h_pid,
-                                  const uint32_t* h_frag, uint64_t n_host, int strand_specific, uint32_t max_span, uint32_t* hits,
-                                  uint64_t* stats) {
-  if (!ctx || !r1 || !r2 || !t_off || (n_tr && (!text || !t_part || !hits)))
-    return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: NULL argument");
-  if (!routes && n_host && (!h_pid || !h_frag)) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: routes neither on the device nor on the host");
-  if (r1->n_reads != r2->n_reads) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: the two read sets are not mates of each other (different sizes)");
-  if (n_parts >= (1u << 31)) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: too many partitions");
+// Both halves of the filter's device work.  hits != NULL: index, map + mark, count -- the bitmap never leaves the device
+// (shn_filter_fp_hits).  cover != NULL: index, map + mark, the bitmap to the host (shn_filter_fp_cover).  fn: who is asked, for the messages.
+static int ffp_run(const char* fn_, shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off, const uint32_t* t_part, uint64_t n_tr, uint32_t n_parts,
+                   const shn_reads* r1, const shn_reads* r2, const shn_routes* routes, const uint32_t* h_pid, const uint32_t* h_frag, uint64_t n_host,
+                   int strand_specific, uint32_t max_span, uint32_t* hits, uint64_t* cover, uint64_t* stats) {
+  const std::string fn(fn_);
+  if (!ctx || !r1 || !r2 || !t_off || (n_tr && (!text || !t_part || (!hits && !cover))))
+    return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
+  if (!routes && n_host && (!h_pid || !h_frag)) return shn_fail(SHN_ERR_ARG, fn + ": routes neither on the device nor on the host");
+  if (r1->n_reads != r2->n_reads) return shn_fail(SHN_ERR_ARG, fn + ": the two read sets are not mates of each other (different sizes)");
+  if (n_parts >= (1u << 31)) return shn_fail(SHN_ERR_ARG, fn + ": too many partitions");
   const uint64_t n_pairs = r1->n_reads;
   const uint64_t total = t_off[n_tr];
-  if (t_off[0] != 0) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: t_off[0] is not 0");
-  if (total >= 0xFFFFFF00ULL) return shn_fail(SHN_ERR_OVERFLOW, "shn_filter_fp_hits: more than 2^32 transcript bases in one call");
+  if (t_off[0] != 0) return shn_fail(SHN_ERR_ARG, fn + ": t_off[0] is not 0");
+  if (total >= 0xFFFFFF00ULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": more than 2^32 transcript bases in one call");
   std::vector<uint64_t> rec_off(n_tr + 1, 0);
   for (uint64_t j = 0; j < n_tr; j++) {
-    if (t_off[j + 1] < t_off[j]) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: t_off not monotone");
-    if (t_part[j] >= n_parts) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: partition of a transcript out of range");
+    if (t_off[j + 1] < t_off[j]) return shn_fail(SHN_ERR_ARG, fn + ": t_off not monotone");
+    if (t_part[j] >= n_parts) return shn_fail(SHN_ERR_ARG, fn + ": partition of a transcript out of range");
     const uint64_t len = t_off[j + 1] - t_off[j];
     rec_off[j + 1] = rec_off[j] + (len >= FFP_SEED ? len - FFP_SEED + 1 : 0);
   }
@@ -356,7 +388,7 @@ extern "C" int shn_filter_fp_hits(shn_ctx* ctx, const uint8_t* text, const uint6
   if (!routes)
     for (uint64_t i = 0; i < n_host; i++)
       if (h_pid[i] >= n_parts || h_frag[i] >= (strand_specific ? n_pairs : 2 * n_pairs))
-        return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: a route names a partition or a fragment that does not exist");
+        return shn_fail(SHN_ERR_ARG, fn + ": a route names a partition or a fragment that does not exist");
   SHN_ENTER(ctx);
   shn_stage_begin(ctx);
   hipStream_t s = ctx->stream;
@@ -417,13 +449,13 @@ extern "C" int shn_filter_fp_hits(shn_ctx* ctx, const uint8_t* text, const uint6
   uint32_t flag = 0;
   HIP_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (flag) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: a transcript holds a base outside ACGT");
+  if (flag) return shn_fail(SHN_ERR_ARG, fn + ": a transcript holds a base outside ACGT");
 
   // ---- map + mark
   const uint64_t n_cov = cdiv(total, 64) + 1;
   HIP_TRY(bufs.get(&d_cov, n_cov * 8));
   HIP_TRY(bufs.get(&d_placed, 8));
-  HIP_TRY(bufs.get(&d_hits, n_tr * 4));
+  if (hits) HIP_TRY(bufs.get(&d_hits, n_tr * 4));
   HIP_TRY(hipMemsetAsync(d_cov, 0, n_cov * 8, s));
   HIP_TRY(hipMemsetAsync(d_placed, 0, 8, s));
   if (n_routes && n_rec) {
@@ -443,16 +475,80 @@ extern "C" int shn_filter_fp_hits(shn_ctx* ctx, const uint8_t* text, const uint6
                        n_parts, strand_specific ? 1 : 0, max_span, d_cov, d_placed);
   }
   // ---- count
-  {
+  if (hits) {
     TimerRegion treg(ctx, T_FFP_COUNT);
     treg.bytes(n_cov * 8 + n_tr * 20);          // the bitmap, two offsets read and a count written per transcript
     hipLaunchKernelGGL(ffp_count_kernel, dim3((uint32_t)cdiv(n_tr, 256)), dim3(256), 0, s, d_cov, d_toff, n_tr, d_hits);
   }
   unsigned long long placed = 0;
-  HIP_TRY(hipMemcpyAsync(hits, d_hits, n_tr * 4, hipMemcpyDeviceToHost, s));
+  if (hits) HIP_TRY(hipMemcpyAsync(hits, d_hits, n_tr * 4, hipMemcpyDeviceToHost, s));
+  if (cover && total) HIP_TRY(hipMemcpyAsync(cover, d_cov, cdiv(total, 64) * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(&placed, d_placed, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipGetLastError());
   if (stats) stats[1] = placed;
+  return SHN_OK;
+}
+
+extern "C" int shn_filter_fp_hits(shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off, const uint32_t* t_part, uint64_t n_tr,
+                                  uint32_t n_parts, const shn_reads* r1, const shn_reads* r2, const shn_routes* routes, const uint32_t* h_pid,
+                                  const uint32_t* h_frag, uint64_t n_host, int strand_specific, uint32_t max_span, uint32_t* hits,
+                                  uint64_t* stats) {
+  if (n_tr && !hits) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_hits: NULL argument");
+  return ffp_run("shn_filter_fp_hits", ctx, text, t_off, t_part, n_tr, n_parts, r1, r2, routes, h_pid, h_frag, n_host, strand_specific, max_span,
+                 hits, nullptr, stats);
+}
+
+// One rank's half of the filter on N ranks: what THESE routes cover, as the bitmap itself (filter_FP.py:29-55 as run_MB_SF_fn.py:272-277
+// runs it; the depth file of a partition is the union of what every rank's pairs cover).
+extern "C" int shn_filter_fp_cover(shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off, const uint32_t* t_part, uint64_t n_tr,
+                                   uint32_t n_parts, const shn_reads* r1, const shn_reads* r2, const shn_routes* routes, const uint32_t* h_pid,
+                                   const uint32_t* h_frag, uint64_t n_host, int strand_specific, uint32_t max_span, uint64_t* cover,
+                                   uint64_t* stats) {
+  if (n_tr && !cover) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_cover: NULL argument");
+  return ffp_run("shn_filter_fp_cover", ctx, text, t_off, t_part, n_tr, n_parts, r1, r2, routes, h_pid, h_frag, n_host, strand_specific, max_span,
+                 nullptr, cover, stats);
+}
+
+// The owner's half: the bitmaps of all ranks for a window of the text -> covered bases of every transcript inside it (the depth
+// file's line count per transcript, filter_FP.py:7-13).
+extern "C" int shn_filter_fp_count(shn_ctx* ctx, const uint64_t* covers, uint32_t n_covers, uint64_t n_words, uint64_t word0,
+                                   const uint64_t* t_off, uint64_t n_tr, uint32_t* hits) {
+  if (!ctx || !t_off || (n_tr && !hits)) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_count: NULL argument");
+  if (n_covers == 0) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_count: no bitmap to count (n_covers is 0)");
+  if (n_words && !covers) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_count: NULL argument");
+  if (word0 >= (1ULL << 56) || n_words >= (1ULL << 56)) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_count: window out of range");
+  const uint64_t lo = word0 * 64, hi = (word0 + n_words) * 64;
+  for (uint64_t j = 0; j <= n_tr; j++) {
+    if (j && t_off[j] < t_off[j - 1]) return shn_fail(SHN_ERR_ARG, "shn_filter_fp_count: t_off not monotone");
+    if (t_off[j] < lo || t_off[j] > hi)
+      return shn_fail(SHN_ERR_ARG, "shn_filter_fp_count: a transcript lies outside the window of the bitmaps (t_off " + std::to_string(t_off[j]) +
+                                       ", window " + std::to_string(lo) + " .. " + std::to_string(hi) + ")");
+  }
+  if (n_tr == 0) return SHN_OK;
+  SHN_ENTER(ctx);
+  shn_stage_begin(ctx);
+  hipStream_t s = ctx->stream;
+  ShnDevBufs bufs(s);
+  unsigned long long* d_cov = nullptr;
+  uint64_t* d_toff = nullptr;
+  uint32_t* d_hits = nullptr;
+  const uint64_t cov_bytes = (uint64_t)n_covers * n_words * 8;
+  HIP_TRY(bufs.get(&d_cov, cov_bytes + 8));
+  HIP_TRY(bufs.get(&d_toff, (n_tr + 1) * 8));
+  HIP_TRY(bufs.get(&d_hits, n_tr * 4));
+  if (cov_bytes) HIP_TRY(hipMemcpyAsync(d_cov, covers, cov_bytes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_toff, t_off, (n_tr + 1) * 8, hipMemcpyHostToDevice, s));
+  {
+    TimerRegion treg(ctx, T_FFP_MERGE);
+    // bytes: the words of every bitmap that lie under a transcript (a boundary word is read by both neighbours), two offsets read and
+    // a count written per transcript
+    treg.bytes((uint64_t)n_covers * (cdiv(t_off[n_tr] - t_off[0], 64) + n_tr) * 8 + n_tr * 20);
+    hipLaunchKernelGGL(ffp_merge_count_kernel, dim3((uint32_t)cdiv(n_tr, FFP_BLOCK / 64)), dim3(FFP_BLOCK), 0, s, d_cov, n_covers, n_words, word0, d_toff,
+                       n_tr, d_hits);
+  }
+  HIP_TRY(hipMemcpyAsync(hits, d_hits, n_tr * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipGetLastError());
   return SHN_OK;
 }

@@ -181,8 +181,12 @@ class _NoLock(object):
 
 
 def assemble_distributed(ops, K=25, partition_size=500, sample="shannon", seed=0, part_vectors=None, group=None,
-                         timings=None, lock=None, double_stranded=True, min_weight=3, min_length=75, kmer_hard_cutoff=1):
+                         timings=None, lock=None, double_stranded=True, min_weight=3, min_length=75, kmer_hard_cutoff=1, filter_fp=False):
     """Returns on rank 0 a dict {partitions: {name: fasta}, final, contigs, ...}; None elsewhere.
+    filter_fp: --filter_FP (shannon.py:170-195, run_MB_SF_fn.py:110, 272-277) -- between the owners' sparse flow and the gather every
+    partition's transcripts are held against the read pairs ALL ranks routed to it (filter_owned_texts); "partitions" and "final" are
+    the filtered ones, rank 0's dict gains "partitions_org", "filter_logs" and "filter_fp_stats".  Paired input only, as in the
+    reference (single-end: "filter_fp_note" says so, nothing is filtered); ops without filter_cover / filter_count are refused.
     min_weight / min_length: hyp_min_weight (--kmer_soft_cutoff) / hyp_min_length as run_correction gets them (shannon.py:243-247,
     457); kmer_hard_cutoff: `jellyfish dump -L` (shannon.py:237-241, 441), applied by the ops to the REDUCED counts -- on the owner
     of a k1-mer after the bucket exchange, never to a rank's local counts.  The ops read them as attributes of the same names.
@@ -196,6 +200,9 @@ def assemble_distributed(ops, K=25, partition_size=500, sample="shannon", seed=0
     ONE GPU it serialises the compute, so the per-stage compute times are those of a rank that has a GPU to itself."""
     import time
     ss = not double_stranded
+    if filter_fp and not (hasattr(ops, "filter_cover") and hasattr(ops, "filter_count")):
+        raise ValueError("assemble_distributed: filter_fp=True needs ops that map read pairs onto transcripts (filter_cover / filter_count: "
+                         "GpuOps has them); these ops do not, and nothing would be filtered")
     if ss and not getattr(ops, "supports_strand_specific", False):
         raise NotImplementedError("assemble_distributed: these ops do not implement -s / --strand_specific (forward counting, plain read "
                                   "indices, pairs of reads_1 and RC(reads_2)); a strand_specific run needs ops that do (GpuOps does)")
@@ -354,8 +361,12 @@ def assemble_distributed(ops, K=25, partition_size=500, sample="shannon", seed=0
         except Exception as ex:                     # told to every rank below: nobody waits in the gather for a rank that has left
             texts, err = {}, "%s: %s" % (type(ex).__name__, ex)
         if texts is not None:
+            extra = None
+            if filter_fp:
+                texts, extra, err = _filter_step(ops, part, texts, names, owner, group, tick, lock, err)
             lock.release()
-            return _gather_and_merge(texts, names, res, gk, group, rank, W, lock, tick, error=err, ops=ops, double_stranded=double_stranded)
+            return _gather_and_merge(texts, names, res, gk, group, rank, W, lock, tick, error=err, ops=ops, double_stranded=double_stranded,
+                                     extra=extra)
 
     def one(i):
         singles, comps = ops.graph(part, names[i], mine.get(i, []), K, paired)      # pieces: [(global indices, reads)] per source rank
@@ -384,8 +395,148 @@ def assemble_distributed(ops, K=25, partition_size=500, sample="shannon", seed=0
         txt += sparse_flow.single_nodes_fasta(sname, singles)
         texts[i] = txt
     tick("sparse flow", t0)
+    extra, err = None, None
+    if filter_fp:
+        texts, extra, err = _filter_step(ops, part, texts, names, owner, group, tick, lock, None)
     lock.release()
-    return _gather_and_merge(texts, names, res, gk, group, rank, W, lock, tick, ops=ops, double_stranded=double_stranded)
+    return _gather_and_merge(texts, names, res, gk, group, rank, W, lock, tick, error=err, ops=ops, double_stranded=double_stranded, extra=extra)
+
+
+def _filter_step(ops, part, texts, names, owner, group, tick, lock, err):
+    """--filter_FP between the owners' sparse flow and the gather: (texts for the merge, what travels beside them, error).  Whether
+    the step runs is decided from what every rank holds (the flag, ops.paired), so every rank reaches its collectives or none does."""
+    if not ops.paired:
+        return texts, {"note": "--filter_FP: single-end input -- the reference sets the flag only for paired-end runs "
+                               "(run_MB_SF_fn.py:110); nothing filtered"}, err
+    kept, org, logs, stats, ferr = filter_owned_texts(texts, names, owner, lambda seqs, part_of, n_parts: ops.filter_cover(part, seqs, part_of, n_parts),
+                                                      ops.filter_count, getattr(ops, "device", None), group, tick, lock)
+    return kept, {"org": org, "logs": logs, "stats": stats}, err or ferr
+
+
+def _runs_of(owner, d):
+    """[(first, last + 1)] of the maximal runs of consecutive partitions that rank d owns"""
+    runs = []
+    for i in np.nonzero(np.asarray(owner) == d)[0].tolist():
+        if runs and runs[-1][1] == i:
+            runs[-1][1] = i + 1
+        else:
+            runs.append([i, i + 1])
+    return [tuple(r) for r in runs]
+
+
+def filter_owned_texts(texts, names, owner, cover, count, device=None, group=None, tick=None, lock=None):
+    """--filter_FP on N ranks (filter_FP.py:29-55 as run_MB_SF_fn.py:272-277 runs it per partition).  A fragment lives on one rank; its
+    minimum cost and the placements that attain it depend on the fragment and on its partition's transcripts alone, and coverage is a
+    set union over fragments: the OR over the ranks of what each rank's pairs cover IS the one-process bitmap, provided every rank
+    marks the same layout of the same transcripts.
+      texts   {partition index: unfiltered FASTA text} of the partitions this rank owns (owner[i] == rank)
+      cover   (seqs, part_of, n_parts) -> (uint64 bitmap of the layout filter_fp.text_offsets(seqs), {"routes", "placed"}): what this
+              rank's routes cover (GpuOps.filter_cover: shn_filter_fp_cover; the CPU tests: numpy)
+      count   (covers [W, n_words], t_off, word0) -> hits (GpuOps.filter_count: shn_filter_fp_count; filter_fp.hits_from_bitmaps(None, ...))
+    1. the owners' texts to every rank (all-gather of bytes), parsed and laid out in partition order: one layout on all ranks;
+    2. cover; 3. for every owner the words under each run of its partitions (one all-to-all of bytes; a boundary word may carry a
+    neighbour's bits, count ignores them), the owner counts over the W pieces; 4. the owner decides (filter_fp._filter_records).
+    Every rank reaches every collective: a rank whose cover or count raises goes on with zeros and returns the message.
+    lock: held on entry and on return, released around the collectives.
+    Returns (kept {i: text}, org {i: text as given}, logs {i: rec.log text}, stats summed over the ranks, error or None)."""
+    import time
+    from . import filter_fp as ffp
+    W, rank = dist.get_world_size(group), dist.get_rank(group)
+    lock = lock or _NoLock()
+    tick = tick or (lambda name, t0: None)
+    cdev = exchange.coll_device(device, group)
+    P = len(names)
+    err = None
+    # ---- 1. texts to every rank
+    t0 = time.time()
+    mine = {int(i): _as_bytes(t) for i, t in texts.items()}
+    buf = _pack_columns({i: [a] for i, a in mine.items()}, 1)
+    tick("filter_FP", t0)
+    lock.release()
+    t0 = time.time()
+    got = exchange.all_gather_arrays((buf,), cdev, group, "filter_FP texts (the owners' unfiltered transcripts to every rank, all-gather)")
+    tick("x:filter_FP texts", t0)
+    lock.acquire()
+    t0 = time.time()
+    n_words = 0
+    seqs, part_of, first = [], [], np.zeros(P + 1, dtype=np.int64)
+    parsed = [([], [])] * P
+    try:
+        every = {}
+        for (b,) in got:
+            every.update({i: cols[0] for i, cols in _unpack_columns(b, 1).items()})
+        parsed = [ffp.records(every[i]) if i in every else ([], []) for i in range(P)]
+        for i, (_nm, sq) in enumerate(parsed):
+            seqs += sq
+            part_of += [i] * len(sq)
+            first[i + 1] = len(seqs)
+        t_off = ffp.text_offsets(seqs)
+        n_words = (int(t_off[-1]) + 63) // 64
+    except Exception as ex:
+        err = "%s: %s" % (type(ex).__name__, ex)
+        seqs, part_of, first, t_off = [], [], np.zeros(P + 1, dtype=np.int64), np.zeros(1, np.uint64)
+    # ---- 2. what this rank's routes cover
+    st = {}
+    bitmap = None
+    if err is None:
+        try:
+            bitmap, st = cover(seqs, part_of, P)
+            bitmap = np.ascontiguousarray(bitmap, dtype=np.uint64)
+            if bitmap.shape != (n_words,):
+                raise ValueError("filter_owned_texts: a bitmap of %s words for a text of %d" % (bitmap.shape, n_words))
+        except Exception as ex:
+            err, bitmap = "%s: %s" % (type(ex).__name__, ex), None
+    if bitmap is None:
+        bitmap = np.zeros(n_words, dtype=np.uint64)
+    # ---- 3. the words under every owner's partitions to that owner
+    def windows(d):           # [(first transcript, behind the last, first word, behind the last word)] per run of d's partitions
+        out = []
+        for a, b in _runs_of(owner, d):
+            ta, tb = int(first[a]), int(first[b])
+            if tb > ta:
+                out.append((ta, tb, int(t_off[ta]) >> 6, (int(t_off[tb]) + 63) // 64))
+        return out
+    send = [np.concatenate([bitmap[w0:w1] for _a, _b, w0, w1 in windows(d)] + [np.zeros(0, np.uint64)]).view(np.uint8) for d in range(W)]
+    tick("filter_FP", t0)
+    lock.release()
+    t0 = time.time()
+    got = exchange.all_to_all_bytes(send, device, group, "filter_FP coverage (every rank's bitmap words under an owner's partitions, all-to-all)")
+    tick("x:filter_FP coverage", t0)
+    lock.acquire()
+    t0 = time.time()
+    hits = np.zeros(len(seqs), dtype=np.uint32)
+    if err is None:
+        try:
+            pieces = [np.ascontiguousarray(b).view(np.uint64) for b in got]
+            at = 0
+            for ta, tb, w0, w1 in windows(rank):
+                covers = np.stack([p_[at:at + (w1 - w0)] for p_ in pieces])
+                hits[ta:tb] = count(covers, t_off[ta:tb + 1], w0)
+                at += w1 - w0
+        except Exception as ex:
+            err = "%s: %s" % (type(ex).__name__, ex)
+    # ---- 4. the owner decides
+    kept, org, logs = {}, {}, {}
+    n_tr = n_kept = 0
+    for i in sorted(mine):
+        nm, sq = parsed[i]
+        k, lg = "", ""
+        if err is None:
+            try:
+                k, lg = ffp._filter_records(nm, sq, hits[int(first[i]):int(first[i + 1])].tolist())
+            except Exception as ex:
+                err = "%s: %s" % (type(ex).__name__, ex)
+        kept[i], org[i], logs[i] = k, mine[i], lg
+        n_tr += len(sq)
+        n_kept += k.count(">")
+    tick("filter_FP", t0)
+    lock.release()
+    t0 = time.time()
+    parts = exchange.all_gather_object((int(st.get("routes", 0)), int(st.get("placed", 0)), n_tr, n_kept), group, "filter_FP counters")
+    tick("x:filter_FP coverage", t0)
+    lock.acquire()
+    tot = np.asarray(parts, dtype=np.int64).sum(axis=0).tolist()
+    return kept, org, logs, dict(zip(("routes", "placed", "transcripts", "kept"), tot)), err
 
 
 class LocalRows(object):
@@ -416,9 +567,36 @@ def _as_bytes(t):
     return np.frombuffer(t.encode(), dtype=np.uint8) if isinstance(t, str) else np.ascontiguousarray(t, dtype=np.uint8)
 
 
-def _gather_and_merge(texts, names, res, gk, group, rank, W, lock, tick, error=None, ops=None, double_stranded=True):
+def _pack_columns(cols, ncol):
+    """{partition index: [ncol uint8 arrays]} -> one uint8 array: the count, (index, sizes) per partition, then the bytes"""
+    idx = sorted(cols)
+    head = np.asarray([len(idx)] + [v for i in idx for v in [i] + [cols[i][c].size for c in range(ncol)]], dtype=np.int64).view(np.uint8)
+    return np.concatenate([head] + [cols[i][c] for i in idx for c in range(ncol)])
+
+
+def _unpack_columns(b, ncol):
+    """inverse of _pack_columns (views into b)"""
+    out = {}
+    if b.size == 0:
+        return out
+    n = int(b[:8].view(np.int64)[0])
+    wd = 8 * (1 + ncol)
+    head = b[8:8 + wd * n].view(np.int64).reshape(n, 1 + ncol)
+    pos = 8 + wd * n
+    for row in head.tolist():
+        out[int(row[0])] = []
+        for sz in row[1:]:
+            out[int(row[0])].append(b[pos:pos + sz])
+            pos += sz
+    return out
+
+
+def _gather_and_merge(texts, names, res, gk, group, rank, W, lock, tick, error=None, ops=None, double_stranded=True, extra=None):
     """the per-partition FASTA of every owner to rank 0, which merges (shannon.py:584-604).  error: what went wrong in this rank's
-    graph stage, if anything -- it travels with the gather, so every rank raises together and none is left waiting."""
+    graph stage, if anything -- it travels with the gather, so every rank raises together and none is left waiting.
+    extra (--filter_FP): {"org", "logs": {i: text}, "stats"} -- the unfiltered texts and the rec.log texts travel beside the kept
+    ones (three columns per partition instead of one), rank 0's dict gains partitions_org / filter_logs / filter_fp_stats; or
+    {"note": ...} for a run that was not filtered."""
     import time
     t0 = time.time()
     # what went wrong, if anything (a few bytes per rank); then the texts as bytes to rank 0 -- what rank 0 produced itself stays put
@@ -427,31 +605,26 @@ def _gather_and_merge(texts, names, res, gk, group, rank, W, lock, tick, error=N
     if errors:
         tick("x:gather fasta", t0)
         raise RuntimeError("graph stage failed on " + "; ".join(errors))
-    mine = {int(i): _as_bytes(t) for i, t in texts.items()}
-    merged = {}
+    filtered = extra is not None and "org" in extra
+    ncol = 3 if filtered else 1
+    mine = {int(i): [_as_bytes(t)] + ([_as_bytes(extra["org"][i]), _as_bytes(extra["logs"][i])] if filtered else []) for i, t in texts.items()}
+    cols = {}
     if W > 1:
         if rank != 0:
-            idx = sorted(mine)
-            head = np.asarray([len(idx)] + [v for i in idx for v in (i, mine[i].size)], dtype=np.int64).view(np.uint8)
-            out = np.concatenate([head] + [mine[i] for i in idx])
+            out = _pack_columns(mine, ncol)
         bufs = [out if (d == 0 and rank != 0) else np.zeros(0, np.uint8) for d in range(W)]
         got = exchange.all_to_all_bytes(bufs, getattr(ops, "device", None), group, "FASTA gather (per-partition transcripts to rank 0)")
         if rank == 0:
             for src, b in enumerate(got):
-                if src == 0 or b.size == 0:
-                    continue
-                n = int(b[:8].view(np.int64)[0])
-                head = b[8:8 + 16 * n].view(np.int64).reshape(n, 2)
-                pos = 8 + 16 * n
-                for i, sz in head.tolist():
-                    merged[int(i)] = b[pos:pos + sz]
-                    pos += sz
+                if src != 0:
+                    cols.update(_unpack_columns(b, ncol))
     tick("x:gather fasta", t0)
     if rank != 0:
         return None
     lock.acquire()
     t0 = time.time()
-    merged.update(mine)
+    cols.update(mine)
+    merged = {i: c[0] for i, c in cols.items()}
     single = "".join(">Single_%d\n%s\n" % (i, c) for i, c in enumerate(res.single_contigs))
     order = [merged[i] for i in range(len(names))]
     # the merge over the texts as they are (process_concatenated_fasta.py + faster_reps.py: post.finalize_texts, on the device when
@@ -468,9 +641,16 @@ def _gather_and_merge(texts, names, res, gk, group, rank, W, lock, tick, error=N
     parts = _Texts(names, order)
     tick("merge (rank 0)", t0)
     lock.release()
-    return {"partitions": parts, "final": final, "contigs": res.contigs,
-            "n_k1mers": int(gk.numel()) if gk is not None else int(getattr(res, "n_k1mers_table", 0)),
-            "extension": {k: getattr(res, k, None) for k in ("iterations", "n_walks", "total_steps", "wave_steps", "fresh_steps", "dense_rounds")}}
+    out = {"partitions": parts, "final": final, "contigs": res.contigs,
+           "n_k1mers": int(gk.numel()) if gk is not None else int(getattr(res, "n_k1mers_table", 0)),
+           "extension": {k: getattr(res, k, None) for k in ("iterations", "n_walks", "total_steps", "wave_steps", "fresh_steps", "dense_rounds")}}
+    if filtered:
+        out["partitions_org"] = _Texts(names, [cols[i][1] for i in range(len(names))])
+        out["filter_logs"] = _Texts(names, [cols[i][2] for i in range(len(names))])
+        out["filter_fp_stats"] = dict(extra["stats"])
+    elif extra is not None:
+        out["filter_fp_note"] = extra["note"]
+    return out
 
 
 def _a2a_objects(recv, payload, group):
@@ -911,6 +1091,21 @@ class GpuOps(object):
                 g.close()
             self.unitigs.close()
             self.unitigs = None
+
+    def filter_cover(self, part, seqs, part_of, n_parts):
+        """--filter_FP, this rank's half: (what ALL routes of this rank's reads cover on the transcripts `seqs`, as the bitmap of
+        filter_fp.coverage_bitmap; routes looked at / fragments placed).  A rank without reads or routes covers nothing."""
+        from . import filter_fp as ffp
+        stats = self.filter_fp_local = {}                 # (this rank's own counters: tests, diagnostics)
+        rdev = part.get("routes_dev")
+        if rdev is None or len(self.d1) == 0:
+            return np.zeros((int(ffp.text_offsets(seqs)[-1]) + 63) // 64, dtype=np.uint64), stats
+        return ffp.coverage_bitmap(self.ctx, seqs, part_of, n_parts, self.d1, self.d2, rdev[0], self.strand_specific, stats=stats), stats
+
+    def filter_count(self, covers, t_off, word0):
+        """--filter_FP, the owner's half: covered bases of every transcript from the bitmaps of all ranks (shn_filter_fp_count)"""
+        from . import filter_fp as ffp
+        return ffp.hits_from_bitmaps(self.ctx, covers, t_off, word0)
 
     def collect(self, sel):
         """the reads of the doubled indices `sel` as they travel to a partition's owner: stored code rows + strand

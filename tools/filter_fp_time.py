@@ -9,7 +9,9 @@ Per size: one warm-up step of each kind, then `repeats` steps of each kind, alte
 texts on the host, the device call, writing the filtered texts), of the kernels' HIP-event time per timer slot
 (filter_fp.index / .map / .count) with the algorithmic bytes their launch sites declare; routes looked at / fragments placed;
 transcripts kept / total; and -- for scale -- the rate of the tests' brute force (tests/filter_fp_cases.py) on 300 routed
-pairs of the same input.  One JSON object on the last line of the output."""
+pairs of the same input.  Then the owner's half of the filter on N ranks alone (shn_filter_fp_count, timer filter_fp.merge): the OR
+of --merge-covers synthetic bitmaps (8: one per rank of a node) and the count per transcript over --merge-bases bases of
+transcripts of 200 .. 3,000 bases, with the bytes the launch site declares.  One JSON object on the last line of the output."""
 import argparse, json, os, statistics, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,11 +23,40 @@ def spread(v):
     return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4), "n": len(v)}
 
 
+def time_merge(ctx, n_covers, n_bases, repeats, seed):
+    """shn_filter_fp_count on synthetic input: the kernel's HIP-event time (filter_fp.merge) and the call's wall time (the upload of
+    the bitmaps included), one warm-up call first; the result is held against the numpy mirror on the first 2,000 transcripts"""
+    import numpy as np
+    from shannon_amd import filter_fp
+    rng = np.random.Generator(np.random.PCG64(seed))
+    lens = rng.integers(200, 3001, max(1, n_bases // 1600))
+    t_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    n_words = (int(t_off[-1]) + 63) // 64
+    covers = rng.integers(0, 1 << 63, (n_covers, n_words), dtype=np.uint64) & rng.integers(0, 1 << 63, (n_covers, n_words), dtype=np.uint64)
+    hits = filter_fp.hits_from_bitmaps(ctx, covers, t_off)
+    k = min(2000, len(lens))
+    w = (int(t_off[k]) + 63) // 64
+    assert hits[:k].tolist() == filter_fp.hits_from_bitmaps(None, covers[:, :w], t_off[:k + 1]).tolist()
+    ms, wall = [], []
+    for _ in range(repeats):
+        ctx.timer_reset()
+        t0 = time.time()
+        filter_fp.hits_from_bitmaps(ctx, covers, t_off)
+        ctx.sync()
+        wall.append(time.time() - t0)
+        ms.append(ctx.timers()["filter_fp.merge"][0])
+    byts = ctx.timer_bytes()["filter_fp.merge"]
+    return {"covers": n_covers, "transcripts": int(len(lens)), "bases": int(t_off[-1]), "bitmap_bytes": int(covers.nbytes), "kernel_ms": spread(ms),
+            "call_seconds": spread(wall), "kernel_bytes": byts, "kernel_GBps_at_median": round(byts / (statistics.median(ms) * 1e-3) / 1e9, 2)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, nargs="+", default=[1_000_000, 10_000_000])
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--seed", type=int, default=20240501)
+    ap.add_argument("--merge-covers", type=int, default=8)
+    ap.add_argument("--merge-bases", type=int, default=50_000_000)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import numpy as np
@@ -87,6 +118,9 @@ def main():
         del R, last
         d1.close()
         d2.close()
+    if args.merge_covers > 0 and args.merge_bases > 0:
+        report["merge"] = time_merge(ctx, args.merge_covers, args.merge_bases, args.repeats, args.seed)
+        print(json.dumps(report["merge"]), flush=True)
     ctx.close()
     line = json.dumps(report)
     if args.out:

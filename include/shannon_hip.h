@@ -559,6 +559,15 @@ void shn_malloc_tune_now(void);
  * reverse-complemented if bit 1 is set; the selected rows must hold ACGT only.                                                   */
 int shn_reads_gather(shn_ctx* ctx, const shn_reads* a, const shn_reads* b, const uint32_t* rows, const uint8_t* flags, uint64_t n,
                      shn_reads** out);
+/* Reads of resident sets -- fixed-length or ragged, with or without bases outside ACGT -- as base codes one after the other:
+ * output read i = read sel[i] of set a (flags[i] bit 0 clear) or of set b (bit 0 set), AS STORED (no reverse complement; the
+ * other bits of flags[i] must be 0).  Codes 0..3, 4 for a base outside ACGT (d_mask).  lens_out[n] = the reads' lengths.
+ * codes_out == NULL: only lens_out (may be NULL too) and *total_out -- the sizing call.  SHN_ERR_ARG, before any launch, for a
+ * sel[i] >= the set's reads, bit 0 set with b == NULL, another flag bit set, or codes_cap < the total where the host can know
+ * the total (fixed-length sets); with a ragged set the total is the device's, and codes_cap < the total is SHN_ERR_ARG after the
+ * one synchronisation: nothing is written past codes_cap, *total_out says what is needed.  n == 0 is fine.                       */
+int shn_reads_collect(shn_ctx* ctx, const shn_reads* a, const shn_reads* b, const uint32_t* sel, const uint8_t* flags, uint64_t n,
+                      uint32_t* lens_out, uint8_t* codes_out, uint64_t codes_cap, uint64_t* total_out);
 /* The inverse of shn_graph_export (sizes[9] as shn_graph_sizes; arrays as shn_graph_export without `info`): a graph object from
  * flattened nodes / edges / paths tables, e.g. the reference's own files.                                                       */
 int shn_graph_from_tables(const uint64_t* sizes, const uint64_t* s_off, const uint8_t* s_bases, const double* s_cc, const double* s_norm,

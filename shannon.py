@@ -22,6 +22,7 @@ are N ranks, one per GPU of the node (torch.distributed over RCCL): this process
 children (torch.distributed.run on 127.0.0.1) and returns their exit code; every rank ingests its slice of the reads, the k1-mer
 buckets are exchanged once, partitions are dealt to the ranks, rank 0 merges and writes OUT/ (shannon_amd/distributed.py).
 -p is capped at the number of GPUs the node shows (one GPU: the one-process path, partitions concurrently on host threads).
+-p N takes reads of any lengths, trimmed reads and mates of two lengths included, as the one-process path does.
 """
 import os, sys, time, json
 
@@ -133,54 +134,62 @@ def rank_main(out_dir, reads, K, partition_size, min_weight, min_length, double_
     t0 = time.time()
     paired = len(reads) == 2
     # every rank ingests ITS share of the files (by bytes; distributed.ingest_rank_slice) -- the records [n r / W, n (r + 1) / W) of the
-    # job, in the files' order; files that cannot be shared out that way (.gz, reads of several lengths, multi-line FASTA) are read
-    # whole on every rank as before
+    # job, in the files' order, reads of different lengths included; files that cannot be shared out that way (.gz, multi-line
+    # FASTA) are read whole on every rank as before
     ing_stats = {}
-    sl = distributed.ingest_rank_slice(reads, rank, world, None, exchange.coll_device(torch.device("cuda", dev_index), None), stats=ing_stats)
-    mats = []
+    cdev = exchange.coll_device(torch.device("cuda", dev_index), None)
+    sl = distributed.ingest_rank_slice(reads, rank, world, None, cdev, stats=ing_stats, ragged=True)
     if sl is not None:
-        q1 = sl[0][0]
-        q2 = sl[0][1] if paired else None
-        n = sl[1]
+        qs, n = list(sl[0]), sl[1]
         lo, hi = rank * n // world, (rank + 1) * n // world
-    for p in (reads if sl is None else []):
-        try:
-            _d, r = device.Reads.ingest(None, p)                # (the host code matrix only: the rank uploads its own slice below)
-            if isinstance(r, device.RaggedCodes):
-                raise _lib.ShannonError("unsupported: ragged reads on the N-rank path")
-        except _lib.ShannonError as ex:
-            if "unsupported" not in str(ex):
-                raise
-            seqs = read_fasta(p)
-            L = len(seqs[0]) if seqs else 0
-            if any(len(x) != L for x in seqs):
-                say("ERROR: the N-rank path takes reads of one length; run without -p / --gpus")
-                return 2
-            code = np.full(256, 4, np.uint8)
-            for j, c in enumerate(b"ACGT"):
-                code[c] = j
-            r = code[np.frombuffer("".join(seqs).encode(), dtype=np.uint8)].reshape(len(seqs), L) if seqs else np.zeros((0, 1), np.uint8)
-        mats.append(r)
-    if sl is None:
+    else:
+        mats = []
+        for p in reads:
+            try:
+                _d, r = device.Reads.ingest(None, p)                # (the host codes only: the rank uploads its own slice below)
+            except _lib.ShannonError as ex:
+                if "unsupported" not in str(ex):
+                    raise
+                seqs = read_fasta(p)
+                code = np.full(256, 4, np.uint8)
+                for j, c in enumerate(b"ACGT"):
+                    code[c] = j
+                off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+                off[1:] = np.cumsum([len(x) for x in seqs], dtype=np.uint64)
+                flat = code[np.frombuffer("".join(seqs).encode(), dtype=np.uint8)]
+                L = len(seqs[0]) if seqs else 0
+                if all(len(x) == L for x in seqs):
+                    r = flat.reshape(len(seqs), L) if seqs else np.zeros((0, 1), np.uint8)
+                else:
+                    r = device.RaggedCodes(flat, off)
+            mats.append(r)
         if paired and len(mats[0]) != len(mats[1]):
             say("ERROR: --left and --right hold different numbers of reads")
             return 2
         n = len(mats[0])
         lo, hi = rank * n // world, (rank + 1) * n // world
-        q1 = np.ascontiguousarray(mats[0][lo:hi])
-        q2 = np.ascontiguousarray(mats[1][lo:hi]) if paired else None
+        qs = [m[lo:hi] if isinstance(m, device.RaggedCodes) else np.ascontiguousarray(m[lo:hi]) for m in mats]
         del mats
+    if any(isinstance(q, device.RaggedCodes) for q in qs):         # one kind of store for both mates
+        qs = [q if isinstance(q, device.RaggedCodes) else device.RaggedCodes.from_matrix(q) for q in qs]
+    q1, q2 = qs[0], (qs[1] if paired else None)
     T["ingest path"] = "byte share of the files" if sl is not None else "whole files on every rank"
     if ing_stats:
         T["ingest bytes scanned by this rank"] = ing_stats["bytes_scanned"]
         T["ingest bytes of the files"] = ing_stats["file_bytes"]
-    d1 = device.Reads.from_codes(ctx, q1)
-    d2 = device.Reads.from_codes(ctx, q2) if paired else None
+
+    def resident(q):
+        return device.Reads.from_ragged(ctx, q.codes, q.off) if isinstance(q, device.RaggedCodes) else device.Reads.from_codes(ctx, q)
+    d1 = resident(q1)
+    d2 = resident(q2) if paired else None
     T["ingest"] = time.time() - t0
-    say("Processed No of reads:%d, Avg. Read length: %.2f (every rank holds a slice of %d of them)" % (n, q1.shape[1] if n else 0, hi - lo))
+    bases = torch.tensor([q1.total_bases if isinstance(q1, device.RaggedCodes) else q1.size], dtype=torch.int64, device=cdev)
+    dist.all_reduce(bases)
+    say("Processed No of reads:%d, Avg. Read length: %.2f (every rank holds a slice of %d of them)" % (n, int(bases.item()) / max(1, n), hi - lo))
     ops = distributed.GpuOps(ctx, d1, d2, kfc.ReadStore(q1, q2), K)
     res = distributed.assemble_distributed(ops, K, partition_size, sample, 0, timings=T, double_stranded=double_stranded,
                                            min_weight=min_weight, min_length=min_length, kmer_hard_cutoff=kmer_hard_cutoff, filter_fp=filter_fp)
+    T["collect path"] = getattr(ops, "collect_path", "host")
     rc = 0
     if rank == 0:
         say("%d K-mers loaded; %d contigs; %d partitions" % (res["n_k1mers"], len(res["contigs"]), len(res["partitions"])))

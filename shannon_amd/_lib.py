@@ -118,6 +118,7 @@ SIGNATURES = {
     "shn_reads_dedup": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_int, vp, vp, vp, vp, vp]),
     "shn_mbgraph_run_resident": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, vp, vp, vpp]),
     "shn_reads_gather": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, vpp]),
+    "shn_reads_collect": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]),
     "shn_graph_from_tables": (C.c_int, [vp] * 20 + [vpp]),
     "shn_sparse_flow": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, vpp]),
     "shn_sparse_flow_thread": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, vpp]),

@@ -53,7 +53,9 @@ enum {
   T_CG_SORT, T_CG_HITS, T_CG_COVER, T_CG_COMPACT, T_KP_SEARCH, T_KP_CLASSIFY, T_SEED_SCAN, T_DD_INSERT, T_LP_TRIALS, T_EXT_AUDIT,
   // --filter_FP (filter_fp.hip): index of the transcripts' 15-mers, mapping + marking of the routed pairs, per-transcript count;
   // the count over the OR of several ranks' bitmaps
-  T_FFP_INDEX, T_FFP_MAP, T_FFP_COUNT, T_FFP_MERGE, T_N = 49
+  T_FFP_INDEX, T_FFP_MAP, T_FFP_COUNT, T_FFP_MERGE,
+  // the reads of resident sets as base codes (reads_collect.hip): the expansion kernel
+  T_READS_COLLECT, T_N = 50
 };
 
 // grow-only device workspace slot (process-wide ones: g_shn_ws below; per-context ones: shn_ctx::cws)

@@ -89,7 +89,22 @@ class RaggedCodes(object):
         return len(self.off) - 1
 
     def __getitem__(self, i):
+        if isinstance(i, slice):
+            # reads [lo:hi] as a RaggedCodes of their own: a view of the codes, offsets that start at 0
+            lo, hi, step = i.indices(len(self))
+            if step != 1:
+                raise IndexError("RaggedCodes: slices of step 1 only")
+            hi = max(hi, lo)
+            o = self.off[lo:hi + 1]
+            return RaggedCodes(self.codes[int(o[0]):int(o[-1])], o - o[0])
         return self.codes[int(self.off[i]):int(self.off[i + 1])]
+
+    @classmethod
+    def from_matrix(cls, rows):
+        """a code matrix [n, L] as codes + offsets (a view of the rows)"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        n, L = rows.shape if rows.ndim == 2 else (0, 0)
+        return cls(rows.reshape(-1), np.arange(n + 1, dtype=np.uint64) * np.uint64(L))
 
     @property
     def total_bases(self):
@@ -112,8 +127,9 @@ class RaggedCodes(object):
 class Reads(object):
     """A set of reads packed 2 bits/base in HBM (+1 bit/base non-ACGT mask)."""
 
-    def __init__(self, ctx, h):
+    def __init__(self, ctx, h, fixed_len=None):
         self.ctx, self.h = ctx, h
+        self.fixed_len = fixed_len        # the one length of the set's reads where the constructor knows it (collect sizes its output by it)
 
     @classmethod
     def from_strings(cls, ctx, reads):
@@ -133,7 +149,47 @@ class Reads(object):
         n, L = codes.shape
         h = C.c_void_p()
         _lib.check(_lib.lib().shn_reads_create(ctx.h, codes.ctypes.data, None, n, L, ENC_CODES, C.byref(h)))
+        return cls(ctx, h, fixed_len=int(L))
+
+    @classmethod
+    def from_ragged(cls, ctx, codes, off):
+        """reads of different lengths from base codes one after the other + offsets uint64[n + 1] (a RaggedCodes' two arrays)"""
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        if len(off) < 1 or (len(off) > 1 and int(off[-1]) > len(codes)):
+            raise ValueError("Reads.from_ragged: offsets beyond the codes")
+        buf = codes if len(codes) else np.zeros(1, np.uint8)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().shn_reads_create(ctx.h, buf.ctypes.data, off.ctypes.data, len(off) - 1, 0, ENC_CODES, C.byref(h)))
         return cls(ctx, h)
+
+    @staticmethod
+    def collect(a, b, sel, flags):
+        """(codes uint8[total], off uint64[n + 1]): read i = read sel[i] of the resident set a (flags[i] == 0) or b (flags[i] == 1) as
+        stored, base codes 0..3 and 4 for a base outside ACGT, one read after the other -- RaggedCodes.take over device sets
+        (shn_reads_collect).  The output is sized from the sets' read length where both are known to be of one length; otherwise
+        a sizing call asks the device first."""
+        sel = np.ascontiguousarray(sel, dtype=np.uint32)
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        n = len(sel)
+        if len(flags) != n:
+            raise ValueError("Reads.collect: %d indices, %d flags" % (n, len(flags)))
+        L = _lib.lib()
+        args = (a.ctx.h, a.h, b.h if b is not None else None, sel.ctypes.data if n else None, flags.ctypes.data if n else None, n)
+        lens = np.empty(max(n, 1), dtype=np.uint32)
+        total = C.c_uint64(0)
+        nb = int(np.count_nonzero(flags))
+        La, Lb = a.fixed_len, (b.fixed_len if b is not None else None)
+        if (nb == n or La is not None) and (nb == 0 or Lb is not None or b is None):
+            cap = (n - nb) * int(La or 0) + nb * int(Lb or 0)
+        else:
+            _lib.check(L.shn_reads_collect(*args, None, None, 0, C.byref(total)))
+            cap = int(total.value)
+        codes = np.empty(max(cap, 1), dtype=np.uint8)
+        _lib.check(L.shn_reads_collect(*args, lens.ctypes.data, codes.ctypes.data, cap, C.byref(total)))
+        off = np.zeros(n + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(lens[:n], dtype=np.uint64)
+        return codes[:int(total.value)], off
 
     @classmethod
     def ingest(cls, ctx, source, fmt=0, want_codes=True):
@@ -164,7 +220,7 @@ class Reads(object):
                 raise
             return cls._ingest_ragged(ctx, text, fmt)
         codes = buf[:n.value * L.value].reshape(n.value, L.value) if want_codes else None
-        return (cls(ctx, h) if ctx is not None else None), codes
+        return (cls(ctx, h, fixed_len=int(L.value)) if ctx is not None else None), codes
 
     @classmethod
     def _ingest_ragged(cls, ctx, text, fmt):

@@ -68,7 +68,7 @@ def _all_gather_var_(t, group=None):
     return out.to(t.device), ns
 
 
-def ingest_rank_slice(paths, rank, world, group, device, ctx=None, stats=None):
+def ingest_rank_slice(paths, rank, world, group, device, ctx=None, stats=None, ragged=False):
     """The N-rank CLI's reads by BYTES of the files (round 6; the reference streams its read files once, 10 M reads at a time:
     kmers_for_component.py:322-403).  Every rank counts the records that start in its share of each file's bytes
     (shn_text_records_in_range), the counts of all ranks say which record every share starts with, and the records
@@ -76,6 +76,10 @@ def ingest_rank_slice(paths, rank, world, group, device, ctx=None, stats=None):
     Host memory and parsing per rank: its share of the text (memory-mapped) + its slice's code matrix, not the whole job's.
     Returns (code matrices of this rank's slice, one per file; n records of the job) or None when a file cannot be shared out this
     way (.gz: no random access; reads of different lengths; multi-line FASTA) and the caller reads whole files as before.
+    ragged=True: reads of different lengths are shared out too.  A rank whose stretch of text holds them keeps the
+    device.RaggedCodes it ingests as; the ranks tell each other (the flags all-gather), and where some rank's slice of a file is
+    ragged -- or two ranks hold matrices of two lengths -- every rank's slice of that file becomes RaggedCodes (a matrix is codes
+    + arange * L already): one kind of store per file on all ranks.
     stats (dict): bytes this rank looked at / holds."""
     import ctypes as C
     from . import _lib, device as dev_mod
@@ -93,8 +97,9 @@ def ingest_rank_slice(paths, rank, world, group, device, ctx=None, stats=None):
         ptr = text.ctypes.data if B else None
         ok = 1
         # (with the count: the offset of every 1,024th record of the share -- from the shares' sparse indices any record of the file is
-        # at most 1,023 records away, whoever's share it starts in)
-        STRIDE = 1024
+        # at most 1,023 records away, whoever's share it starts in; shares below 4 MB index more densely, one record per 4 KB of the
+        # share, so that the walk to a slice's first record stays a few per cent of the share: the same on every rank)
+        STRIDE = int(max(16, min(1024, (B // max(world, 1)) >> 12)))
         idx_buf = np.zeros(max(1, (hi_b - lo_b) // (2 * STRIDE) + 2), dtype=np.uint64)         # (a record is at least 2 bytes)
         try:
             _lib.check(L_.shn_text_records_in_range(ptr, B, lo_b, hi_b, 0, C.byref(first), C.byref(cnt), STRIDE, idx_buf.ctypes.data, len(idx_buf),
@@ -140,19 +145,25 @@ def ingest_rank_slice(paths, rank, world, group, device, ctx=None, stats=None):
                 if "unsupported" not in str(ex):
                     raise
                 codes = None
-        fine = codes is not None and not isinstance(codes, dev_mod.RaggedCodes) and len(codes) == rhi - rlo
-        flag = torch.tensor([1 if fine else 0, codes.shape[1] if fine and len(codes) else 0], dtype=torch.int64, device=device)
+        is_ragged = isinstance(codes, dev_mod.RaggedCodes)
+        fine = codes is not None and (ragged or not is_ragged) and len(codes) == rhi - rlo
+        flag = torch.tensor([1 if fine else 0, codes.shape[1] if fine and not is_ragged and len(codes) else 0, 1 if fine and is_ragged else 0],
+                            dtype=torch.int64, device=device)
         flags = [torch.zeros_like(flag) for _ in range(world)]
         dist.all_gather(flags, flag, group=group)
         ft = np.stack([x.cpu().numpy() for x in flags])
         lens = set(int(v) for v in ft[:, 1] if v)
-        if not ft[:, 0].all() or len(lens) > 1:
+        some_ragged = bool(ft[:, 2].any()) or len(lens) > 1
+        if not ft[:, 0].all() or (some_ragged and not ragged):
             return None
-        if len(codes) == 0 and lens:                                          # (a rank without records still holds a matrix of the job's read length)
+        if some_ragged:
+            if not is_ragged:
+                codes = dev_mod.RaggedCodes.from_matrix(codes) if len(codes) else dev_mod.RaggedCodes(np.zeros(0, np.uint8), np.zeros(1, np.uint64))
+        elif len(codes) == 0 and lens:                                        # (a rank without records still holds a matrix of the job's read length)
             codes = np.zeros((0, lens.pop()), np.uint8)
         scanned += b - a
-        held += (b - a) + codes.size
-        mats.append(np.ascontiguousarray(codes))
+        held += (b - a) + (codes.total_bases if some_ragged else codes.size)
+        mats.append(codes if some_ragged else np.ascontiguousarray(codes))
         del text
     if stats is not None:
         stats.update({"bytes_scanned": int(scanned), "bytes_held": int(held), "file_bytes": int(sum(os.path.getsize(p) for p in paths)), "records": int(n_job or 0)})
@@ -921,8 +932,9 @@ class GpuOps(object):
         def _matrix(m):
             return isinstance(m, np.ndarray) and m.dtype == np.uint8 and m.ndim == 2 and m.flags["C_CONTIGUOUS"]
         import os
+        # (mates of two different lengths: the duplicate search on the device takes read sets of one length, as in pipeline.py)
         return (self.unitigs is not None and _matrix(getattr(self.store, "r1", None)) and (not self.paired or _matrix(getattr(self.store, "r2", None)))
-                and os.environ.get("SHN_GRAPH_ROWS", "1") != "0")
+                and self.one_length and os.environ.get("SHN_GRAPH_ROWS", "1") != "0")
     array_payload = True               # collect() returns (code rows, strand flags): travels as bytes, not as pickles
 
     def extension(self, table, partition_size, group=None, presharded=None):
@@ -983,6 +995,8 @@ class GpuOps(object):
         from . import kmers_for_component as kfc, mbgraph_native
         import os
         self.unitigs, self.part_index = None, None
+        # (which way collect() goes on this rank; the CLI puts it beside its stage times -- the timings dict itself holds seconds only)
+        self.collect_path = "device" if self.collect_on_device else "host"
         gpu_graph = K <= 31 and os.environ.get("SHN_GRAPH_GPU", "1") != "0"
         part = kfc.kmers_for_component(self.ctx, res, self.d1, self.d2, K, partition_size, part_vectors=part_vectors, want_rows=False,
                                        timings=getattr(self, "timings", None), lazy_routes=True, lazy_graph_inputs=gpu_graph,
@@ -1001,9 +1015,50 @@ class GpuOps(object):
         return part["n_kmer_nodes"][name]
 
     @staticmethod
-    def _merge_pieces(pieces):
-        """the pieces of one partition from their source ranks -> (code rows, strand flags) in the global strand-doubled order"""
+    def _as_ragged(data, halves=False):
+        """a fixed-length piece (rows, flags) as a RaggedPiece; halves: the rows hold the two mates of a -s pair side by side"""
+        if isinstance(data, exchange.RaggedPiece):
+            return data
+        rows, rc1 = data
+        n, L2 = rows.shape
+        L = L2 // 2 if halves else L2
+        off = np.arange(n + 1, dtype=np.uint64) * np.uint64(L)
+        if not halves:
+            return exchange.RaggedPiece(rows.reshape(-1), off, rc1)
+        return exchange.RaggedPiece(np.ascontiguousarray(rows[:, :L]).reshape(-1), off, rc1, np.ascontiguousarray(rows[:, L:]).reshape(-1), off)
+
+    @staticmethod
+    def _merge_ragged(pieces, halves=False):
+        """_merge_pieces for pieces that carry lengths: one RaggedPiece in the order of the global indices (a stable sort of the
+        indices, one gather of the reads' runs of codes per mate)"""
+        from . import _lib
+        gidx = np.concatenate([g for g, _ in pieces])
+        ps = [GpuOps._as_ragged(d, halves) for _, d in pieces]
+        if any(p.paired != ps[0].paired for p in ps):
+            raise ValueError("GpuOps: pieces with and without second mates for one partition")
+
+        def joined(codes, offs):
+            base = np.concatenate([[0], np.cumsum([int(o[-1]) for o in offs])]).astype(np.uint64)
+            return np.concatenate(codes), np.concatenate([offs[0][:1]] + [o[1:] + b for o, b in zip(offs, base)])
+        one = len(ps) == 1
+        c1, o1 = (ps[0].codes, ps[0].off) if one else joined([p.codes for p in ps], [p.off for p in ps])
+        c2, o2 = (None, None) if not ps[0].paired else ((ps[0].codes2, ps[0].off2) if one else joined([p.codes2 for p in ps], [p.off2 for p in ps]))
+        rc1 = ps[0].rc if one else np.concatenate([p.rc for p in ps])
+        if len(gidx) > 1 and not bool((gidx[1:] > gidx[:-1]).all()):
+            order = np.argsort(gidx, kind="stable")
+            c1, o1 = _lib.gather_segments(c1, o1, order)
+            if c2 is not None:
+                c2, o2 = _lib.gather_segments(c2, o2, order)
+            rc1 = np.ascontiguousarray(rc1[order])
+        return exchange.RaggedPiece(c1, o1, rc1, c2, o2)
+
+    @staticmethod
+    def _merge_pieces(pieces, halves=False):
+        """the pieces of one partition from their source ranks -> (code rows, strand flags) in the global strand-doubled order; a
+        RaggedPiece (codes + offsets instead of rows) where a piece carries lengths.  halves: see _as_ragged."""
         pieces = [p for p in pieces if len(p[0])]
+        if any(isinstance(d, exchange.RaggedPiece) for _, d in pieces):
+            return GpuOps._merge_ragged(pieces, halves)
         if not pieces:
             return np.zeros((0, 1), np.uint8), np.zeros(0, np.uint8)
         one = len(pieces) == 1                                    # (no copy of a 100 MB piece)
@@ -1032,10 +1087,18 @@ class GpuOps(object):
         def one(i):
             pieces = mine.get(i, [])
             local = pieces[0][1] if (len(pieces) == 1 and isinstance(pieces[0][1], LocalRows)) else None
-            rows, rc1 = (np.zeros((0, 1), np.uint8), np.zeros(0, np.uint8)) if local is not None else self._merge_pieces(pieces)
+            merged = (np.zeros((0, 1), np.uint8), np.zeros(0, np.uint8)) if local is not None else self._merge_pieces(pieces, self.strand_specific and paired)
+            ragged = merged if isinstance(merged, exchange.RaggedPiece) else None
+            rows, rc1 = (np.zeros((0, 1), np.uint8), np.zeros(0, np.uint8)) if ragged is not None else merged
             rb = None
             for _attempt in (0, 1):
                 try:
+                    if ragged is not None:
+                        # reads that carry their lengths: codes + offsets straight to the graph stage, as the one-process path hands
+                        # ragged reads over (pipeline.py: gather_codes / gather_codes_ss -> run_partition_handle)
+                        b1, o1, b2, o2, r1, r2 = self._ragged_args(ragged, paired)
+                        return mbgraph_native.run_partition_handle(rb, 0 if rb is None else len(rb) // (K + 1), K, b1, o1, b2, o2, ctx=self.ctx, enc=1,
+                                                                   rc1=r1, rc2=r2, unitigs=self.unitigs, part=i)
                     if self.strand_specific and len(rows):
                         # -s: the rows hold reads_1[i] and, for pairs, reads_2[i] side by side (collect); the second mate is read on its
                         # reverse strand (rc2 = 1): the pairs (reads_1[i], RC(reads_2[i])) of shannon.py:407-411, not strand-doubled
@@ -1092,6 +1155,22 @@ class GpuOps(object):
             self.unitigs.close()
             self.unitigs = None
 
+    def _ragged_args(self, m, paired):
+        """(b1, o1, b2, o2, rc1, rc2) of run_partition_handle(enc=1) for a merged RaggedPiece.  Double-stranded pairs: the second
+        mates are the same stored reads on the other strand (pipeline.py: b2, o2 = b1, o1; rc2 = 1 - rc1); -s pairs: reads_2 as
+        stored, read reversed (rc2 = 1)."""
+        n = len(m)
+        b1 = m.codes if len(m.codes) else np.zeros(1, np.uint8)
+        if self.strand_specific:
+            if not paired:
+                return b1, m.off, None, None, np.zeros(n, np.uint8), None
+            if not m.paired:
+                raise ValueError("GpuOps: a -s pair's piece without its second mates")
+            return b1, m.off, (m.codes2 if len(m.codes2) else np.zeros(1, np.uint8)), m.off2, np.zeros(n, np.uint8), np.ones(n, np.uint8)
+        if not paired:
+            return b1, m.off, None, None, m.rc, None
+        return b1, m.off, b1, m.off, m.rc, (1 - m.rc).astype(np.uint8)
+
     def filter_cover(self, part, seqs, part_of, n_parts):
         """--filter_FP, this rank's half: (what ALL routes of this rank's reads cover on the transcripts `seqs`, as the bitmap of
         filter_fp.coverage_bitmap; routes looked at / fragments placed).  A rank without reads or routes covers nothing."""
@@ -1107,27 +1186,87 @@ class GpuOps(object):
         from . import filter_fp as ffp
         return ffp.hits_from_bitmaps(self.ctx, covers, t_off, word0)
 
+    @property
+    def one_length(self):
+        """both stored mates are code matrices of one common read length: the pieces travel as rows"""
+        def _matrix(m):
+            return isinstance(m, np.ndarray) and m.ndim == 2
+        r1, r2 = getattr(self.store, "r1", None), getattr(self.store, "r2", None)
+        return _matrix(r1) and (not self.paired or (_matrix(r2) and r2.shape[1] == r1.shape[1]))
+
+    @property
+    def collect_on_device(self):
+        """SHN_COLLECT_DEVICE: unset -- the reads of a piece that carries lengths are collected from the resident sets
+        (shn_reads_collect), rows of one length from the host matrices as ever; 0 -- the host everywhere; 1 -- the device everywhere"""
+        v = os.environ.get("SHN_COLLECT_DEVICE", "")
+        return v[:1] == "1" if self.one_length else v[:1] != "0"
+
+    @staticmethod
+    def _host_take(src, idx):
+        """reads idx of a host store (a code matrix or device.RaggedCodes) as (codes, offsets)"""
+        if isinstance(src, np.ndarray):
+            rows = np.ascontiguousarray(src[idx])
+            return rows.reshape(-1), np.arange(len(idx) + 1, dtype=np.uint64) * np.uint64(src.shape[1])
+        c, o = src.take(idx)
+        return c[:int(o[-1])], o
+
     def collect(self, sel):
-        """the reads of the doubled indices `sel` as they travel to a partition's owner: stored code rows + strand
-        flags of the first mates (second mates: same rows, opposite strand)"""
+        """the reads of the doubled indices `sel` as they travel to a partition's owner.  Code matrices of one common length: stored
+        code rows + strand flags of the first mates (second mates: same rows, opposite strand).  Anything else -- reads of
+        different lengths, mates of two lengths: an exchange.RaggedPiece, the reads as stored with their lengths.
+          double-stranded   doubled index d < n: read d of reads_1; d >= n: read d - n of reads_2 (reads_1 when single-end),
+                            rc = (d >= n) -- what ReadStore._gather_ragged(idx, 1, False) gives;
+          -s                reads_1[i], rc = 0; for pairs reads_2[i] as stored beside them (the owner reads them reversed)."""
+        sel = np.asarray(sel, dtype=np.int64)
+        n_sel, n = len(sel), len(self.d1)
+        rows_out, dev = self.one_length, self.collect_on_device
+        L = int(self.store.r1.shape[1]) if rows_out else 0
+        zeros = np.zeros(n_sel, np.uint8)
+        Reads = self._dev.Reads
         if self.strand_specific:
             # plain read indices: reads_1[i] as stored and, for pairs, reads_2[i] as stored beside it (the owner reads it reversed)
-            b1, o1, _rc, enc = self.store.gather_codes_ss(sel, 1)
-            if enc != 1:
-                raise ValueError("GpuOps: -s on the N-rank path needs the reads stored as code matrices")
-            L = int(o1[1] - o1[0]) if len(o1) > 1 else 0
-            rows = b1.reshape(len(sel), L)
+            if dev:
+                c1, o1 = Reads.collect(self.d1, None, sel, zeros)
+                c2, o2 = Reads.collect(self.d2, None, sel, zeros) if self.paired else (None, None)
+            elif rows_out or self.store.ragged:
+                c1, o1, _rc, enc = self.store.gather_codes_ss(sel, 1)
+                if enc != 1:
+                    raise ValueError("GpuOps: -s on the N-rank path needs the reads stored as codes")
+                c2, o2 = self.store.gather_codes_ss(sel, 2)[:2] if self.paired else (None, None)
+            else:
+                c1, o1 = self._host_take(self.store.r1, sel)
+                c2, o2 = self._host_take(self.store.r2, sel) if self.paired else (None, None)
+            if not rows_out:
+                return exchange.RaggedPiece(c1, o1, zeros, c2, o2)
+            rows = c1[:n_sel * L].reshape(n_sel, L)
             if self.paired:
-                b2, o2, _rc2, _e = self.store.gather_codes_ss(sel, 2)
-                rows = np.concatenate([rows, b2.reshape(len(sel), L)], axis=1)
-            return (np.ascontiguousarray(rows), np.zeros(len(sel), np.uint8))
-        buf, off, rc1, enc = self.store.gather_codes(sel, 1)
-        L = int(off[1] - off[0]) if len(off) > 1 else 0
-        return (buf.reshape(len(sel), L), rc1)
+                rows = np.concatenate([rows, c2[:n_sel * L].reshape(n_sel, L)], axis=1)
+            return (np.ascontiguousarray(rows), zeros)
+        second = sel >= n
+        if dev:
+            codes, off = Reads.collect(self.d1, self.d2, np.where(second, sel - n, sel), (second if self.paired else zeros))
+            rc1 = second.astype(np.uint8)
+        elif rows_out or (self.store.ragged and n_sel):
+            codes, off, rc1, _enc = self.store.gather_codes(sel, 1)
+        else:
+            if n_sel > 1 and not bool((sel[1:] >= sel[:-1]).all()):
+                raise ValueError("GpuOps.collect: the doubled indices of a piece come in ascending order")
+            f = int(np.searchsorted(sel, n))
+            src2 = self.store.r1 if not self.paired else self.store.r2
+            (ca, oa), (cb, ob) = self._host_take(self.store.r1, sel[:f]), self._host_take(src2, sel[f:] - n)
+            codes, off, rc1 = np.concatenate([ca, cb]), np.concatenate([oa, ob[1:] + oa[-1]]), second.astype(np.uint8)
+        if not rows_out:
+            return exchange.RaggedPiece(codes, off, rc1)
+        return (codes[:n_sel * L].reshape(n_sel, L), rc1)
 
     def graph(self, part, name, pieces, K, paired):
         from . import mbgraph_native
         rb = part["k1mer_bytes"][name]                     # the partition's k1-mer file as fixed-width rows
+        if any(isinstance(d, exchange.RaggedPiece) and len(g) for g, d in pieces):
+            b1, o1, b2, o2, r1, r2 = self._ragged_args(self._merge_pieces(pieces, self.strand_specific and paired), paired)
+            singles, comps, _log = mbgraph_native.run_partition_arrays(rb if len(rb) else np.zeros(1, np.uint8), len(rb) // (K + 1), K, b1, o1, b2, o2,
+                                                                       ctx=self.ctx, enc=1, rc1=r1, rc2=r2)
+            return singles, comps
         if any(len(p[0]) for p in pieces):
             # global strand-doubled order = the reference's file order
             pieces = [p for p in pieces if len(p[0])]

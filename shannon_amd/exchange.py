@@ -267,15 +267,63 @@ def all_to_all_bytes(bufs, device, group=None, name="read exchange (capped reads
     return [out[offs[i]:offs[i + 1]] for i in range(world)]
 
 
+class RaggedPiece(object):
+    """Reads of different lengths on their way to a partition's owner: base codes one after the other (0..3, 4 = outside ACGT) +
+    offsets uint64[n + 1] + the strand flag of every read; codes2 / off2: the second mates of a -s pair as stored (any lengths)."""
+
+    def __init__(self, codes, off, rc, codes2=None, off2=None):
+        self.off = np.ascontiguousarray(off, dtype=np.uint64)
+        self.codes = np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1)[:int(self.off[-1])]
+        self.rc = np.ascontiguousarray(rc, dtype=np.uint8).reshape(-1)
+        self.off2 = None if off2 is None else np.ascontiguousarray(off2, dtype=np.uint64)
+        self.codes2 = None if off2 is None else np.ascontiguousarray(codes2, dtype=np.uint8).reshape(-1)[:int(self.off2[-1])]
+        if len(self.off) != len(self.rc) + 1 or (self.off2 is not None and len(self.off2) != len(self.off)):
+            raise ValueError("RaggedPiece: offsets and flags of different numbers of reads")
+
+    def __len__(self):
+        return len(self.rc)
+
+    @property
+    def paired(self):
+        return self.off2 is not None
+
+    def reads(self, second=False):
+        """the reads as a list of code arrays (tests)"""
+        c, o = (self.codes2, self.off2) if second else (self.codes, self.off)
+        return [c[int(o[i]):int(o[i + 1])] for i in range(len(self))]
+
+
+def _lens32(off):
+    lens = off[1:] - off[:-1]
+    if len(lens) and int(lens.max()) > 0xffffffff:
+        raise ValueError("a read of more than 2^32 - 1 bases")
+    return lens.astype(np.uint32)
+
+
 def pack_read_pieces(items):
-    """items: [(partition index, global doubled indices int64[n], (rows uint8[n, L], rc flags uint8[n]))] -> one uint8 array."""
+    """items: [(partition index, global doubled indices int64[n], (rows uint8[n, L], rc flags uint8[n]) or a RaggedPiece)] -> one
+    uint8 array.  Head: the number of items, then (partition, n, L) per item -- L = -1 marks a RaggedPiece, -2 one with second
+    mates.  Body per item: the indices, then rows + flags, or lengths uint32[n] (+ those of the second mates) + codes (+ the
+    second mates') + flags.  Fixed-length pieces alone give the bytes they always gave."""
     head = [len(items)]
     body = []
-    for p, gidx, (rows, rc1) in items:
+    for p, gidx, data in items:
+        g = np.ascontiguousarray(gidx, dtype=np.int64).view(np.uint8).reshape(-1)
+        if isinstance(data, RaggedPiece):
+            n = len(data)
+            head += [int(p), n, -2 if data.paired else -1]
+            body += [g, _lens32(data.off).view(np.uint8)]
+            if data.paired:
+                body.append(_lens32(data.off2).view(np.uint8))
+            body.append(data.codes)
+            if data.paired:
+                body.append(data.codes2)
+            body.append(data.rc)
+            continue
+        rows, rc1 = data
         n, L = int(rows.shape[0]), int(rows.shape[1]) if rows.ndim == 2 else 0
         head += [int(p), n, L]
-        body += [np.ascontiguousarray(gidx, dtype=np.int64).view(np.uint8).reshape(-1), np.ascontiguousarray(rows, dtype=np.uint8).reshape(-1),
-                 np.ascontiguousarray(rc1, dtype=np.uint8).reshape(-1)]
+        body += [g, np.ascontiguousarray(rows, dtype=np.uint8).reshape(-1), np.ascontiguousarray(rc1, dtype=np.uint8).reshape(-1)]
     return np.concatenate([np.asarray(head, dtype=np.int64).view(np.uint8)] + body)
 
 
@@ -287,8 +335,27 @@ def unpack_read_pieces(buf):
     head = buf[8:8 + 24 * n_items].view(np.int64).reshape(n_items, 3)
     pos = 8 + 24 * n_items
     out = []
+
+    def offsets(n):
+        nonlocal pos
+        o = np.zeros(n + 1, dtype=np.uint64)
+        o[1:] = np.cumsum(buf[pos:pos + 4 * n].view(np.uint32), dtype=np.uint64)
+        pos += 4 * n
+        return o
     for p, n, L in head.tolist():
         gidx = buf[pos:pos + 8 * n].view(np.int64); pos += 8 * n
+        if L < 0:
+            if L not in (-1, -2):
+                raise ValueError("unpack_read_pieces: piece kind %d" % L)
+            o1 = offsets(n)
+            o2 = offsets(n) if L == -2 else None
+            c1 = buf[pos:pos + int(o1[-1])]; pos += int(o1[-1])
+            c2 = None
+            if o2 is not None:
+                c2 = buf[pos:pos + int(o2[-1])]; pos += int(o2[-1])
+            rc1 = buf[pos:pos + n]; pos += n
+            out.append((p, gidx, RaggedPiece(c1, o1, rc1, c2, o2)))
+            continue
         rows = buf[pos:pos + n * L].reshape(n, L); pos += n * L
         rc1 = buf[pos:pos + n]; pos += n
         out.append((p, gidx, (rows, rc1)))

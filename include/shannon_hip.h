@@ -34,6 +34,7 @@ typedef struct shn_table shn_table;
 #define SHN_ERR_NOMEM -3
 #define SHN_ERR_OVERFLOW -4
 #define SHN_ERR_INTERNAL -5
+#define SHN_ERR_IO -6 /* a file could not be opened or written: the message holds the path and strerror(errno) */
 
 #define SHN_ENC_ASCII 0 /* 'A','C','G','T' (either case); anything else is "non-ACGT" */
 #define SHN_ENC_CODES 1 /* 0..3; anything else is "non-ACGT"                          */
@@ -56,7 +57,7 @@ int shn_ctx_fork(const shn_ctx* parent, shn_ctx** out);
 int shn_ctx_own_workspaces(shn_ctx* ctx);
 
 /* HIP-event timing on the context's stream (bench.py: per-kernel-group durations).
- * shn_timer_begin/end bracket a region under `slot` (0..31); shn_timer_ms() synchronises and
+ * shn_timer_begin/end bracket a region under `slot` (0..63); shn_timer_ms() synchronises and
  * returns the accumulated milliseconds and number of regions since the last reset. */
 int shn_timer_reset(shn_ctx* ctx);
 int shn_timer_ms(shn_ctx* ctx, int slot, double* ms, uint64_t* n_regions);
@@ -329,6 +330,9 @@ int shn_route_reads(shn_ctx* ctx, const shn_reads* r1, const shn_reads* r2, int 
  * (r1[d], RC(r2[d])) and matches through the k1-mers of r1[d] and of RC(r2[d]).  strand_specific == 0: shn_route_reads.          */
 int shn_route_reads_mode(shn_ctx* ctx, const shn_reads* r1, const shn_reads* r2, int k1, const shn_table* probe,
                          const uint32_t* set_off, const uint32_t* set_members, uint32_t n_sets, int strand_specific, shn_routes** out);
+/* A route list from host arrays: n (partition, read index) pairs, sorted by partition, then index, as shn_route_reads leaves them
+ * (the caller's word for it) -- the per-rank lists of an N-rank job, and the tests of the calls that read a list in place.        */
+int shn_routes_create(shn_ctx* ctx, const uint32_t* pid, const uint32_t* ridx, uint64_t n, shn_routes** out);
 void shn_routes_destroy(shn_routes* r);
 uint64_t shn_routes_size(const shn_routes* r);
 int shn_routes_download(shn_ctx* ctx, const shn_routes* r, uint32_t* pid, uint32_t* ridx);
@@ -338,6 +342,41 @@ int shn_routes_download(shn_ctx* ctx, const shn_routes* r, uint32_t* pid, uint32
  * (multibridging.py:26-30) instead of every route.                                                                       */
 int shn_routes_bounds(shn_ctx* ctx, const shn_routes* r, uint32_t n_parts, uint32_t split, uint64_t* start, uint64_t* below);
 int shn_routes_download_range(shn_ctx* ctx, const shn_routes* r, uint64_t lo, uint64_t n, uint32_t* ridx);
+
+/* ---- --inDisk: the files of one partition's hand-off to multibridging.py / algorithm_SF.py, formatted on the device ---------------
+ * shn_reads_fasta: the text of reads{comp}.fasta (single-end, kmers_for_component.py:349-351: '>e' + read) or of reads{comp}_1.fasta /
+ * _2.fasta (pairs, :396-397: '>e_1' / '>e_2') for entries [lo, lo + n) of `routes`, read in place on the device; shannon.py:496-509
+ * moves the files to TEMP/<sample>_<comp>algo_input/reads*.fasta.  Replaces the per-record Python writer of
+ * reference_api.kmers_for_component.  Record i is '>' decimal(e0 + i) suffix '\n' bases '\n', suffix "" (mate 0: single-end), "_1"
+ * (mate 1), "_2" (mate 2).  a / b: the run's resident read sets, fixed-length or ragged, of any two geometries (b NULL for
+ * single-end); N = reads of a.  The read behind a route entry d (kmers_for_component.ReadStore.mate1 / mate2):
+ *     mode SHN_READS_DOUBLED          mate 0:  d < N ? a[d] : RC(a[d-N])     mate 1:  d < N ? a[d] : RC(b[d-N])
+ *                                     mate 2:  d < N ? RC(a[d]) : b[d-N]
+ *     mode SHN_READS_STRAND_SPECIFIC  mate 0, 1:  a[d]                       mate 2:  RC(b[d])      (-s, shannon.py:407-411)
+ * Codes 0..3 are written as ACGT, a masked base as N (routed reads hold none: kmers_for_component.py:336, 376).
+ * out == NULL: the sizing call, only *total_out is set.  cap < the total: nothing is written at or past cap, SHN_ERR_ARG after the
+ * call's one synchronisation, *total_out says what is needed.  n == 0 is fine.  SHN_ERR_ARG before any launch: lo + n beyond the
+ * routes, mate != 0 with b == NULL (or with sets of different sizes), an unknown mode or mate.  A route that names a read outside
+ * the sets gets an empty sequence and the call SHN_ERR_ARG.                                                                       */
+#define SHN_READS_DOUBLED 0
+#define SHN_READS_STRAND_SPECIFIC 1
+int shn_reads_fasta(shn_ctx* ctx, const shn_reads* a, const shn_reads* b, const shn_routes* routes, uint64_t lo, uint64_t n, int mode, int mate,
+                    uint64_t e0, uint8_t* out, uint64_t cap, uint64_t* total_out);
+/* shn_k1mers_dict_text: the text of component{comp}k1mers_allowed.dict (kmers_for_component.py:452-477; TEMP/<sample>_<comp>algo_input/
+ * k1mer.dict after shannon.py:496-509) as reference_api.kmers_for_component writes it: for every contig in order (text / off: n_strings
+ * ASCII strings one after the other, host) and every k1-window in order, k1mer '\t' decimal(weight) '\n'; duplicates are kept.
+ * weights (host): one per window, in window order -- sum over the contigs of max(len - k1 + 1, 0) entries.  Sizing call and cap as
+ * shn_reads_fasta.  An empty contig list, or contigs without a window, give an empty text.                                      */
+int shn_k1mers_dict_text(shn_ctx* ctx, const uint8_t* text, const uint64_t* off, uint64_t n_strings, int k1, const uint32_t* weights, uint8_t* out,
+                         uint64_t cap, uint64_t* total_out);
+/* The same texts into the file `path` (created or truncated), chunk by chunk: a chunk holds at most SHN_INDISK_STAGE_BYTES bytes
+ * (default 32 MiB) and ends on a record boundary; while chunk c + 1 is formatted and copied into one of two pinned staging buffers,
+ * a host thread writes chunk c.  Names go on across chunks from e0.  A failed open or write: SHN_ERR_IO, the message holds the path
+ * and strerror(errno); the partial file is left, nothing is retried.  *bytes_out (may be NULL): the bytes written.                */
+int shn_reads_fasta_file(shn_ctx* ctx, const shn_reads* a, const shn_reads* b, const shn_routes* routes, uint64_t lo, uint64_t n, int mode, int mate,
+                         uint64_t e0, const char* path, uint64_t* bytes_out);
+int shn_k1mers_dict_file(shn_ctx* ctx, const uint8_t* text, const uint64_t* off, uint64_t n_strings, int k1, const uint32_t* weights, const char* path,
+                         uint64_t* bytes_out);
 
 /* ---- --filter_FP: coverage of the transcripts by the read pairs routed to their partition --------------
  * Replaces filter_FP.filter_FP (filter_FP.py:29-55: hisat-build, hisat --no-discordant, samtools view -f 0x2 / sort / depth) as

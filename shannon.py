@@ -10,6 +10,9 @@ are accepted and reported as not built.
     python shannon.py -o OUT --left r1.fasta --right r2.fasta [-s / --ss / --strand_specific]
     ... [--kmer_hard_cutoff N]   k1-mers counted fewer than N times are dropped (`jellyfish dump -L N`, shannon.py:237-241, 441; default 1)
     ... [--kmer_soft_cutoff N]   hyp_min_weight: seed threshold + hyperbola of the contig stage (shannon.py:243-247, 457; default 3)
+    ... [--inDisk]               the reference's default mode (shannon.py:39-40): per partition TEMP/<sample>_<name>algo_input/ holds reads.fasta
+                                 (pairs: reads_1.fasta + reads_2.fasta) and k1mer.dict, the hand-off to multibridging.py / algorithm_SF.py,
+                                 written from the device (one-process runs)
     ... [--filter_FP]            paired-end runs: after a partition's sparse flow its read pairs are mapped back onto its transcripts and a
                                  transcript stays only if the pairs cover 90 % of its bases (shannon.py:170-195, filter_FP.py; the aligner is
                                  the rule of DESIGN.md "filter_FP", run on the GPU); per partition TEMP/<sample>_<name>algo_output/ then holds
@@ -256,6 +259,7 @@ def parse_args(argv):
     takes_value = ("-o", "--single", "--left", "--right", "-K", "-p", "--gpus", "--partition", "--kmer_hard_cutoff", "--kmer_soft_cutoff")
     n_gpus = 0
     filter_fp = False
+    in_disk = False
     while i < len(argv):
         a = argv[i]
         if a in takes_value and i + 1 >= len(argv):
@@ -300,7 +304,12 @@ def parse_args(argv):
             if not filter_fp:
                 print("OPTIONS --filter_FP: False-positive filtering enabled")
             filter_fp = True; i += 1; continue
-        if a in ("--inDisk", "--only_reads"):
+        if a == "--inDisk":
+            # shannon.py:39-40, 186: the reference's default mode -- the partitions' reads*.fasta / k1mer.dict under TEMP/
+            if not in_disk:
+                print("OPTIONS --inDisk: In Memory mode disabled")
+            in_disk = True; i += 1; continue
+        if a == "--only_reads":
             noted.append("%s: the stages hand their data over in memory (the reference's --inMem contract); TEMP/ holds the per-stage "
                          "products but not reads{comp}.fasta / component*k1mers_allowed.dict (shannon_amd/reference_api.py writes those "
                          "when a single stage is driven through the reference's file interface)" % a)
@@ -313,7 +322,13 @@ def parse_args(argv):
         noted.append("--filter_FP: single-end input -- the reference applies the filter to paired-end runs only (run_MB_SF_fn.py:110); "
                      "nothing is filtered")
         filter_fp = False
+    if in_disk and max(nJobs, n_gpus) > 1:
+        noted.append("--inDisk: TEMP/<sample>_<comp>algo_input/reads*.fasta and k1mer.dict are written by one-process runs only; with "
+                     "-p N / --gpus N the stages hand their data over in memory (shannon_amd/reference_api.py writes the files when a "
+                     "single stage is driven through the reference's file interface)")
+        in_disk = False
     o = Options()
+    o.in_disk = in_disk
     o.K, o.partition_size, o.nJobs, o.n_gpus = K, partition_size, nJobs, n_gpus
     o.out_dir, o.reads, o.double_stranded = out_dir, reads, double_stranded
     o.min_weight, o.min_length, o.kmer_hard_cutoff = min_weight, min_length, kmer_hard_cutoff
@@ -410,11 +425,14 @@ def main(argv):
         R = pipeline.assemble_resident(ctx, sets[0], sets[1] if paired else None, kfc.ReadStore(r[0], r[1] if paired else None), K=K,
                                        partition_size=partition_size, min_weight=min_weight, min_length=min_length, sample=sample, seed=0,
                                        double_stranded=double_stranded, timings=T, kmer_hard_cutoff=kmer_hard_cutoff,
-                                       filter_fp=filter_fp)
+                                       filter_fp=filter_fp, in_disk_dir=temp if o.in_disk else None)
     else:
         R = pipeline.assemble(ctx, r[0], r[1] if paired else None, K=K, partition_size=partition_size, min_weight=min_weight,
                               min_length=min_length, sample=sample, seed=0, double_stranded=double_stranded, timings=T,
-                              kmer_hard_cutoff=kmer_hard_cutoff, filter_fp=filter_fp)
+                              kmer_hard_cutoff=kmer_hard_cutoff, filter_fp=filter_fp, in_disk_dir=temp if o.in_disk else None)
+    if o.in_disk:
+        say("--inDisk: reads*.fasta and k1mer.dict of %d partitions under %s (%d bytes)"
+            % (len(R.in_disk), temp, sum(sum(f.values()) for f in R.in_disk.values())))
     say("%d K-mers loaded; %d contigs; %d partitions" % (R.n_k1mers, len(R.extension.contigs), len(R.partitions)))
     # TEMP tree: the per-stage products of the reference (shannon.py:496-513, 584-595)
     from shannon_amd import extension_correction as ec, mbgraph

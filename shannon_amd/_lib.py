@@ -65,6 +65,7 @@ SIGNATURES = {
     "shn_probe_sets": (C.c_int, [vp, vp, vp]),
     "shn_route_reads": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp, C.c_uint32, vpp]),
     "shn_route_reads_mode": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp, C.c_uint32, C.c_int, vpp]),
+    "shn_routes_create": (C.c_int, [vp, vp, vp, C.c_uint64, vpp]),
     "shn_routes_destroy": (None, [vp]),
     "shn_routes_size": (C.c_uint64, [vp]),
     "shn_routes_download": (C.c_int, [vp, vp, vp, vp]),
@@ -119,6 +120,10 @@ SIGNATURES = {
     "shn_mbgraph_run_resident": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_int, vp, vp, vpp]),
     "shn_reads_gather": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, vpp]),
     "shn_reads_collect": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]),
+    "shn_reads_fasta": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_uint64, vp, C.c_uint64, u64p]),
+    "shn_reads_fasta_file": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_char_p, u64p]),
+    "shn_k1mers_dict_text": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_int, vp, vp, C.c_uint64, u64p]),
+    "shn_k1mers_dict_file": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_int, vp, C.c_char_p, u64p]),
     "shn_graph_from_tables": (C.c_int, [vp] * 20 + [vpp]),
     "shn_sparse_flow": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, vpp]),
     "shn_sparse_flow_thread": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint64, vpp]),

@@ -55,7 +55,9 @@ enum {
   // the count over the OR of several ranks' bitmaps
   T_FFP_INDEX, T_FFP_MAP, T_FFP_COUNT, T_FFP_MERGE,
   // the reads of resident sets as base codes (reads_collect.hip): the expansion kernel
-  T_READS_COLLECT, T_N = 50
+  T_READS_COLLECT,
+  // --inDisk (reads_text.hip): the expansion kernels of the two formatters (reads*.fasta, k1mer.dict)
+  T_READS_FASTA, T_K1MERS_DICT, T_N = 52
 };
 
 // grow-only device workspace slot (process-wide ones: g_shn_ws below; per-context ones: shn_ctx::cws)

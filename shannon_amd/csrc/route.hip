@@ -250,6 +250,24 @@ extern "C" void shn_routes_destroy(shn_routes* r) {
   if (r->d_ridx) shn_dev_free(r->d_ridx);
   delete r;
 }
+extern "C" int shn_routes_create(shn_ctx* ctx, const uint32_t* pid, const uint32_t* ridx, uint64_t n, shn_routes** out) {
+  if (!ctx || !out || (n && (!pid || !ridx))) return shn_fail(SHN_ERR_ARG, "shn_routes_create: NULL argument");
+  SHN_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  shn_routes* R = new shn_routes();
+  R->ctx = ctx; R->device = ctx->device; R->n = n; R->d_pid = nullptr; R->d_ridx = nullptr;
+  if (n) {
+    hipError_t e = shn_dev_malloc(&R->d_pid, n * 4);
+    if (e == hipSuccess) e = shn_dev_malloc(&R->d_ridx, n * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(R->d_pid, pid, n * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(R->d_ridx, ridx, n * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { shn_routes_destroy(R); return shn_fail(SHN_ERR_HIP, std::string("shn_routes_create: ") + hipGetErrorString(e)); }
+  }
+  *out = R;
+  return SHN_OK;
+}
+
 extern "C" uint64_t shn_routes_size(const shn_routes* r) { return r ? r->n : 0; }
 
 extern "C" int shn_routes_download(shn_ctx* ctx, const shn_routes* r, uint32_t* pid, uint32_t* ridx) {

@@ -532,7 +532,7 @@ def foreign_interference(ctx, local, acc, best_count, foreign, r=15, f=0.5):
 
 
 def run_correction(ctx, table, min_weight=3, min_length=75, comp_size_threshold=500, r=15, f=0.5, want_allowed=True, timings=None,
-                   shard=None, merge=None, gather=None, table_size=None):
+                   shard=None, merge=None, gather=None, table_size=None, want_weight_arrays=False):
     """extension_correction.run_correction (extension_correction.py:309-524) on a device k1-mer
     table.  Returns an ExtensionResult: contigs, allowed {k1mer: int}, connections, components,
     single_contigs, big_components [(contigs, metis_text)], remaining [[contig...]].
@@ -542,6 +542,8 @@ def run_correction(ctx, table, min_weight=3, min_length=75, comp_size_threshold=
     contig stages are sharded as well -- every rank decides its own candidates, a GPU r-mer join against the other shards'
     accepted contigs proves that none of them could have changed a duplicate_check decision (foreign_interference), else all
     ranks fall back to the global sequential pass.
+    want_weight_arrays (--inDisk): res.k1mer_keys / res.k1mer_weights = the distinct k1-mers of the contigs (packed, ascending) and
+    their weights -- what `allowed` holds, as two arrays from one shn_ext_weights call, without a dictionary entry per window.
     table_size: the number of k1-mers of the JOB when `table` is this rank's share of it already (whole components: shard = None
     with a gather) -- the choice between the contig stages must be the same on every rank."""
     import time as _t
@@ -814,6 +816,10 @@ def run_correction(ctx, table, min_weight=3, min_length=75, comp_size_threshold=
                 allowed[c[i:i + k1]] = w[p]
                 p += 1
     res.allowed = allowed
+    if want_weight_arrays:
+        keys, _nw = windows_to_keys_many(res.contigs, k1) if res.contigs else (np.zeros(0, np.uint64), None)
+        keys = np.unique(keys)
+        res.k1mer_keys, res.k1mer_weights = keys, ext.weights(keys)
     ext.close()
 
     # DFS components (:417-434, native: shn_contig_components) and file products (:458-513)

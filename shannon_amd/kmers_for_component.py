@@ -8,6 +8,7 @@ METIS's -- partitioned configurations are parity-checked given the same partitio
 """
 import ctypes as C
 import math
+import os
 import numpy as np
 from . import _lib, device
 from .extension_correction import windows_to_keys, windows_to_keys_many
@@ -287,9 +288,46 @@ def build_partitions(res, K, partition_size=500, overload=2, penalty=5, repartit
     return new_components, broken
 
 
+READS_DOUBLED, READS_STRAND_SPECIFIC = 0, 1           # SHN_READS_*: what a route's index means (shn_reads_fasta)
+
+
 class Routes(object):
-    def __init__(self, ctx, h):
+    def __init__(self, ctx, h, reads=None):
         self.ctx, self.h = ctx, h
+        self.reads = reads                # (reads1, reads2 or None): the resident sets the routes index (fasta / fasta_file)
+
+    @classmethod
+    def from_arrays(cls, ctx, pid, ridx, reads=None):
+        """a route list from host arrays, sorted by (partition, index) as the routing leaves them (shn_routes_create)"""
+        pid = np.ascontiguousarray(pid, dtype=np.uint32)
+        ridx = np.ascontiguousarray(ridx, dtype=np.uint32)
+        if len(pid) != len(ridx):
+            raise ValueError("Routes.from_arrays: %d partitions, %d indices" % (len(pid), len(ridx)))
+        h = C.c_void_p()
+        _lib.check(_lib.lib().shn_routes_create(ctx.h, pid.ctypes.data if len(pid) else None, ridx.ctypes.data if len(pid) else None, len(pid), C.byref(h)))
+        return cls(ctx, h, reads=reads)
+
+    def _fasta_args(self, lo, n, mode, mate, e0, reads):
+        a, b = reads if reads is not None else self.reads
+        return (self.ctx.h, a.h, b.h if b is not None else None, self.h, int(lo), int(n), int(mode), int(mate), int(e0))
+
+    def fasta(self, lo, n, mode, mate, e0=0, reads=None):
+        """bytes: the text of reads{comp}.fasta (mate 0) / reads{comp}_1.fasta (1) / _2.fasta (2) for routes [lo, lo + n), record i
+        named e0 + i, formatted on the device (shn_reads_fasta: a sizing call, then the text).  mode: READS_DOUBLED or
+        READS_STRAND_SPECIFIC.  For tests and small callers; files go through fasta_file."""
+        args = self._fasta_args(lo, n, mode, mate, e0, reads)
+        total = C.c_uint64(0)
+        _lib.check(_lib.lib().shn_reads_fasta(*args, None, 0, C.byref(total)))
+        out = np.empty(max(int(total.value), 1), dtype=np.uint8)
+        _lib.check(_lib.lib().shn_reads_fasta(*args, out.ctypes.data, int(total.value), C.byref(total)))
+        return out[:int(total.value)].tobytes()
+
+    def fasta_file(self, path, lo, n, mode, mate, e0=0, reads=None):
+        """the same text into `path`, in chunks through pinned staging buffers while a host thread writes (shn_reads_fasta_file);
+        returns the bytes written"""
+        nb = C.c_uint64(0)
+        _lib.check(_lib.lib().shn_reads_fasta_file(*self._fasta_args(lo, n, mode, mate, e0, reads), os.fsencode(path), C.byref(nb)))
+        return int(nb.value)
 
     def download(self):
         n = int(_lib.lib().shn_routes_size(self.h))
@@ -343,6 +381,91 @@ class RouteView(object):
     def __array__(self, dtype=None, copy=None):
         a = self.routes.download_range(self.lo, self.n)
         return a if dtype is None else a.astype(dtype)
+
+
+def _dict_args(ctx, text, off, k1, weights):
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    weights = np.ascontiguousarray(weights, dtype=np.uint32)
+    n = len(off) - 1 if len(off) else 0
+    n_win = int(np.maximum(np.diff(off.astype(np.int64)) - (int(k1) - 1), 0).sum()) if n else 0
+    if len(weights) != n_win:
+        raise ValueError("k1mers dict: %d weights for %d windows" % (len(weights), n_win))
+    keep = (text, off, weights)             # (the arrays the pointers point into)
+    return keep, (ctx.h, text.ctypes.data if len(text) else None, off.ctypes.data if n else None, n, int(k1), weights.ctypes.data if n_win else None)
+
+
+def k1mers_dict_text(ctx, text, off, k1, weights):
+    """bytes: component{comp}k1mers_allowed.dict -- k1mer TAB weight for every k1-window of the strings text[off[i]:off[i + 1]], in
+    order, weights uint32 in window order -- formatted on the device (shn_k1mers_dict_text).  For tests and small callers."""
+    _keep, args = _dict_args(ctx, text, off, k1, weights)
+    total = C.c_uint64(0)
+    _lib.check(_lib.lib().shn_k1mers_dict_text(*args, None, 0, C.byref(total)))
+    out = np.empty(max(int(total.value), 1), dtype=np.uint8)
+    _lib.check(_lib.lib().shn_k1mers_dict_text(*args, out.ctypes.data, int(total.value), C.byref(total)))
+    return out[:int(total.value)].tobytes()
+
+
+def k1mers_dict_file(ctx, path, text, off, k1, weights):
+    """the same text into `path`, chunk by chunk (shn_k1mers_dict_file); returns the bytes written"""
+    _keep, args = _dict_args(ctx, text, off, k1, weights)
+    nb = C.c_uint64(0)
+    _lib.check(_lib.lib().shn_k1mers_dict_file(*args, os.fsencode(path), C.byref(nb)))
+    return int(nb.value)
+
+
+def text_window_keys(text, off, k1):
+    """packed keys of all k1-windows of the strings text[off[i]:off[i + 1]], in order (shn_string_windows on the host)"""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n = len(off) - 1
+    n_win = int(np.maximum(np.diff(off.astype(np.int64)) - (int(k1) - 1), 0).sum()) if n > 0 else 0
+    keys = np.empty(n_win, dtype=np.uint64)
+    if n_win:
+        _lib.check(_lib.lib().shn_string_windows(text.ctypes.data, off.ctypes.data, n, int(k1), keys.ctypes.data, None))
+    return keys
+
+
+def write_in_disk(ctx, part, reads1, reads2, K, strand_specific, sample, in_disk_dir, k1mer_keys, k1mer_weights):
+    """--inDisk (shannon.py:39-40, the reference's default): for every partition `name` of `part` (kmers_for_component's result)
+    the directory <in_disk_dir>/<sample>_<name>algo_input/ with reads.fasta (pairs: reads_1.fasta + reads_2.fasta) -- ALL routed
+    reads, the cap of multibridging.py:385-391 comes after the files -- and k1mer.dict, as kmers_for_component.py:351, 396-397,
+    452-477 writes them and shannon.py:496-509 moves them.  Formatted on the device from the routes and the contig text
+    (Routes.fasta_file, k1mers_dict_file).  k1mer_keys (ascending) / k1mer_weights: the weights of the contigs' k1-mers
+    (run_correction(want_weight_arrays=True)).  Returns {name: {file name: bytes}}."""
+    k1 = K + 1
+    names = list(part["new_components"])
+    routes, starts = part["routes_dev"]
+    mode = READS_STRAND_SPECIFIC if strand_specific else READS_DOUBLED
+    flat = part.get("flat_text")
+    if flat is not None and flat[3] == sum(len(part["new_components"][nm]) for nm in names):
+        text, off = flat[0], flat[1]
+    else:                                   # (small inputs: the probe table was built on the host, there is no flat text yet)
+        contigs = [c for nm in names for c in part["new_components"][nm]]
+        text = np.frombuffer("".join(contigs).encode(), dtype=np.uint8) if contigs else np.zeros(1, np.uint8)
+        off = np.zeros(len(contigs) + 1, dtype=np.uint64)
+        if contigs:
+            off[1:] = np.cumsum(np.fromiter(map(len, contigs), dtype=np.int64, count=len(contigs)), dtype=np.uint64)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    written, c0 = {}, 0
+    for name in names:
+        d = os.path.join(in_disk_dir, "%s_%salgo_input" % (sample, name))
+        os.makedirs(d, exist_ok=True)
+        got = written[name] = {}
+        lo, n = starts[name], len(part["routes"][name])
+        for mate, fn in (((1, "reads_1.fasta"), (2, "reads_2.fasta")) if reads2 is not None else ((0, "reads.fasta"),)):
+            got[fn] = routes.fasta_file(os.path.join(d, fn), lo, n, mode, mate, reads=(reads1, reads2))
+        c1 = c0 + len(part["new_components"][name])
+        poff = off[c0:c1 + 1]
+        keys = text_window_keys(text, poff, k1)
+        # every window of a partition contig is a k1-mer of a contig of the extension: its weight is in the arrays
+        at = np.searchsorted(k1mer_keys, keys)
+        w = k1mer_weights[np.minimum(at, max(len(k1mer_keys) - 1, 0))] if len(keys) else np.zeros(0, np.uint32)
+        if len(keys) and not np.array_equal(k1mer_keys[np.minimum(at, len(k1mer_keys) - 1)], keys):
+            raise RuntimeError("--inDisk: a k1-mer of partition %s is not among the contigs' k1-mers" % name)
+        got["k1mer.dict"] = k1mers_dict_file(ctx, os.path.join(d, "k1mer.dict"), text, poff, k1, w)
+        c0 = c1
+    return written
 
 
 def make_table(ctx, keys, values, k, canonical=False):
@@ -426,7 +549,7 @@ def kmers_for_component(ctx, res, reads1, reads2, K, partition_size=500, overloa
         lap("route.kernel")
     if probe_h is None:
         h = _host_probe_and_route(ctx, comps, names, pid_of, reads1, reads2, k1, lap, strand_specific)
-    routes = Routes(ctx, h)
+    routes = Routes(ctx, h, reads=(reads1, reads2))
     if lazy_routes:                                   # routes stay on the device; RouteView fetches what is asked for
         start, below = routes.bounds(len(names), len(reads1))
         by_part = {n: RouteView(routes, start[i], start[i + 1] - start[i], below[i]) for i, n in enumerate(names)}

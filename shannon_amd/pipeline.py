@@ -71,11 +71,11 @@ def n_kmer_nodes(rows, K):
 
 def assemble(ctx, reads1, reads2=None, K=25, partition_size=500, min_weight=3, min_length=75, overload=2, penalty=5,
              sample="shannon", seed=0, double_stranded=True, part_vectors=None, timings=None, hits_factory=None,
-             native_graph=True, kmer_hard_cutoff=1, filter_fp=False):
+             native_graph=True, kmer_hard_cutoff=1, filter_fp=False, in_disk_dir=None):
     """reads1/reads2: lists of strings or uint8 code matrices (reads2 None = single-end).
     min_weight = the reference's hyp_min_weight (--kmer_soft_cutoff, shannon.py:243-247, 457); kmer_hard_cutoff = its
-    jellyfish_kmer_cutoff (--kmer_hard_cutoff, `jellyfish dump -L`, shannon.py:237-241, 441).  filter_fp: --filter_FP, see
-    assemble_resident.
+    jellyfish_kmer_cutoff (--kmer_hard_cutoff, `jellyfish dump -L`, shannon.py:237-241, 441).  filter_fp: --filter_FP, in_disk_dir:
+    --inDisk, see assemble_resident.
     Returns Result with .partitions {name: dict}, .all_reconstructed (lines), .final {name: seq}."""
     T = timings if timings is not None else {}
     paired = reads2 is not None
@@ -90,12 +90,14 @@ def assemble(ctx, reads1, reads2=None, K=25, partition_size=500, min_weight=3, m
     store = kfc.ReadStore(reads1, reads2)
     tick("upload+pack", t0)
     return assemble_resident(ctx, d1, d2, store, K, partition_size, min_weight, min_length, overload, penalty, sample, seed,
-                             double_stranded, part_vectors, T, hits_factory, native_graph, kmer_hard_cutoff=kmer_hard_cutoff, filter_fp=filter_fp)
+                             double_stranded, part_vectors, T, hits_factory, native_graph, kmer_hard_cutoff=kmer_hard_cutoff, filter_fp=filter_fp,
+                             in_disk_dir=in_disk_dir)
 
 
 def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3, min_length=75, overload=2, penalty=5,
                       sample="shannon", seed=0, double_stranded=True, part_vectors=None, timings=None, hits_factory=None,
-                      native_graph=True, graph_threads=None, keep_partitioning=False, defer_back=False, kmer_hard_cutoff=1, filter_fp=False):
+                      native_graph=True, graph_threads=None, keep_partitioning=False, defer_back=False, kmer_hard_cutoff=1, filter_fp=False,
+                      in_disk_dir=None):
     """Same as assemble() with the reads already packed in HBM (d1/d2: device.Reads).  graph_threads: partitions whose
     graph stage may run concurrently on host threads.  keep_partitioning: leave the partition stage's tables (partition ->
     contigs, routed read indices) on the result as `.partitioning` (tests/test_fullsize_gpu.py reads them).  defer_back: run count,
@@ -104,7 +106,11 @@ def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3
     filter_fp: --filter_FP (shannon.py:170-195, run_MB_SF_fn.py:110, 272-277) -- once the last sparse flow is done, every partition's
     transcripts are held against the read pairs routed to it in one device call (filter_fp.filter_texts) and the merge gets the
     texts without the transcripts the pairs do not cover; a record then holds reconstructed_fasta (filtered), reconstructed_org_fasta
-    and filter_log.  Paired-end input only, as in the reference (single-end: R.filter_fp_note says so, nothing is filtered)."""
+    and filter_log.  Paired-end input only, as in the reference (single-end: R.filter_fp_note says so, nothing is filtered).
+    in_disk_dir: --inDisk (shannon.py:39-40) -- right behind the routing every partition `name` gets <in_disk_dir>/<sample>_<name>algo_input/
+    with reads.fasta (pairs: reads_1.fasta + reads_2.fasta; all routed reads) and k1mer.dict, formatted on the device from the routes
+    and the contig text (kfc.write_in_disk); R.in_disk = {name: {file: bytes}}, the time under timings["inDisk"].  None: nothing
+    of this runs."""
     # double_stranded=False: -s / --ss / --strand_specific.  shannon.py:394-424 then leaves single-end reads as they are and
     # reverse-complements the second mates, without doubling; from :427 on double_stranded is False in BOTH modes, so only the read
     # set differs: forward counting (d2: its reverse complements), routes of plain read indices, pairs (R1[i], RC(R2[i])) in the
@@ -138,7 +144,8 @@ def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3
     R.n_k1mers, R.n_windows = len(table), table.total
     tick("count", t0)
     t0 = time.time()
-    res = ec.run_correction(ctx, table, min_weight, min_length, partition_size, want_allowed=not native_graph, timings=T)
+    res = ec.run_correction(ctx, table, min_weight, min_length, partition_size, want_allowed=not native_graph, timings=T,
+                            want_weight_arrays=in_disk_dir is not None)
     table.close()
     R.extension = res
     tick("extension", t0)
@@ -162,6 +169,10 @@ def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3
                                        want_rows=not native_graph, timings=T, lazy_graph_inputs=gpu_unitigs, strand_specific=ss,
                                        lazy_routes=rows_likely)
         tick("partition+route", t0)
+        if in_disk_dir is not None:
+            t0 = time.time()
+            R.in_disk = kfc.write_in_disk(mctx, part, d1, d2, K, ss, sample, in_disk_dir, res.k1mer_keys, res.k1mer_weights)
+            tick("inDisk", t0)
         if keep_partitioning:
             R.partitioning = part
         R.partitions = {}

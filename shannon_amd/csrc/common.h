@@ -54,9 +54,9 @@ enum {
   // --filter_FP (filter_fp.hip): index of the transcripts' 15-mers, mapping + marking of the routed pairs, per-transcript count;
   // the count over the OR of several ranks' bitmaps
   T_FFP_INDEX, T_FFP_MAP, T_FFP_COUNT, T_FFP_MERGE,
-  // the reads of resident sets as base codes (reads_collect.hip): the expansion kernel
+  // records_expand_kernel (record_expand_dev.h) by its record type: the reads of resident sets as base codes (reads_collect.hip),
   T_READS_COLLECT,
-  // --inDisk (reads_text.hip): the expansion kernels of the two formatters (reads*.fasta, k1mer.dict)
+  // --inDisk (reads_text.hip): the records of reads*.fasta, of k1mer.dict
   T_READS_FASTA, T_K1MERS_DICT, T_N = 52
 };
 

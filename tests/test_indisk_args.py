@@ -48,3 +48,14 @@ def test_host_side_of_the_file_drivers(tmp_path):
     subprocess.run([cxx, "-std=c++17", "-O1", "-pthread", os.path.join(ROOT, "tools", "indisk_host_check.cpp"), "-o", exe], check=True)
     p = subprocess.run([exe, str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
     assert p.returncode == 0 and "indisk_host_check: OK" in p.stdout, p.stdout
+
+
+def test_device_side_of_the_formatters_on_the_host(tmp_path):
+    """csrc/record_expand.h as plain C++ -- the length functions, the record search, every 16-byte chunk of collect, reads*.fasta
+    and k1mer.dict with arrays of exactly the allocated sizes -- against a per-record writer: the stand-alone program says OK"""
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no C++ compiler"
+    exe = str(tmp_path / "expand_host_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", os.path.join(ROOT, "tools", "expand_host_check.cpp"), "-o", exe], check=True)
+    p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert p.returncode == 0 and "expand_host_check: OK" in p.stdout, p.stdout

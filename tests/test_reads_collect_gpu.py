@@ -1,7 +1,7 @@
 """GPU: shn_reads_collect (device.Reads.collect) -- the reads of resident sets as base codes one after the other -- against
 device.RaggedCodes.take over the same reads on the host.  Fixed-length and ragged sets, two sets of different geometry in one
 call, bases outside ACGT at the edges of the 32-base words and of the 64-base mask words, selections with repeats, empty, of one
-read, and one that takes more than one pass of the grid."""
+read, and one that takes more than one pass of the grid; reads without a base; an output that ends exactly on a block."""
 import ctypes as C
 import numpy as np
 import pytest
@@ -9,6 +9,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 LENS = (1, 2, 31, 32, 33, 63, 64, 65, 100, 127, 128, 129, 250)
+EMPTY_LENS = [0, 5, 0, 0, 0, 33, 64, 0, 1, 0] * 30               # 300 reads: empty ones first, last and three in a row
 
 
 def _with_n(codes, off, every=5):
@@ -22,13 +23,13 @@ def _with_n(codes, off, every=5):
     return codes
 
 
-def _ragged(rng, lens, with_n):
+def _ragged(rng, lens, with_n, every=5):
     from shannon_amd import device
     off = np.zeros(len(lens) + 1, dtype=np.uint64)
     off[1:] = np.cumsum(lens, dtype=np.uint64)
     codes = rng.integers(0, 4, int(off[-1])).astype(np.uint8)
     if with_n:
-        codes = _with_n(codes, off)
+        codes = _with_n(codes, off, every)
     return device.RaggedCodes(codes, off)
 
 
@@ -49,6 +50,8 @@ class _Sets(object):
             for L in (31, 32, 33, 64, 80, 100):
                 self.add("L%d_%s" % (L, tag), *_fixed(rng, 300, L, with_n))
         self.add("short", _ragged(rng, [30 + (7 * i) % 67 for i in range(500)], True), None)
+        for with_n in (False, True):
+            self.add("empties_" + ("N" if with_n else "acgt"), _ragged(rng, EMPTY_LENS, with_n, every=3), None)
 
     def add(self, name, host, L):
         from shannon_amd import device
@@ -125,6 +128,59 @@ def test_a_selection_of_more_than_one_pass(sets):
     _check(sets, "short", None, sel, np.zeros(len(sel), np.uint8))
     flags = rng.integers(0, 2, len(sel)).astype(np.uint8)
     _check(sets, "short", "L31_acgt", np.where(flags == 1, sel % 300, sel).astype(np.uint32), flags)
+
+
+@pytest.mark.parametrize("tag", ["acgt", "N"])
+def test_a_ragged_set_with_empty_reads(sets, tag):
+    """reads without a base are stepped over wherever they lie; a selection of nothing but such reads launches no expansion"""
+    from shannon_amd import device
+    name = "empties_" + tag
+    n = len(sets.host[name])
+    empty = np.nonzero(np.asarray(EMPTY_LENS) == 0)[0]
+    assert n == 300 and len(empty) == 180 and empty[0] == 0 and empty[-1] == n - 1
+    rng = np.random.default_rng(8)
+    for sel in (np.arange(n), rng.integers(0, n, 1000), empty, empty[:1], np.array([n - 1])):
+        _check(sets, name, None, sel.astype(np.uint32), np.zeros(len(sel), np.uint8))
+    sets.ctx.timer_reset()
+    codes, off = device.Reads.collect(sets.dev[name], None, empty.astype(np.uint32), np.zeros(len(empty), np.uint8))
+    assert len(codes) == 0 and len(off) == len(empty) + 1 and not off.any()
+    assert "reads.collect" not in sets.ctx.timers()
+
+
+def _block_edge(sets):
+    """128 reads of 32 bases = 4,096 codes: exactly one block of the expansion (256 threads x 16 bytes)"""
+    sel = np.random.default_rng(9).integers(0, len(sets.host["L32_acgt"]), 128).astype(np.uint32)
+    return sel, np.zeros(128, np.uint8)
+
+
+def test_an_output_that_ends_on_a_block_and_one_code_behind_it(sets):
+    sel, flags = _block_edge(sets)
+    want, _off = _expected(sets, "L32_acgt", None, sel, flags)
+    assert len(want) == 4096
+    _check(sets, "L32_acgt", None, sel, flags)
+    assert sets.host["ragged_acgt"].off[1] == 1                    # read 0 of the ragged set: one base
+    sel, flags = np.append(sel, np.uint32(0)), np.append(flags, np.uint8(1))
+    want, _off = _expected(sets, "L32_acgt", "ragged_acgt", sel, flags)
+    assert len(want) == 4097
+    _check(sets, "L32_acgt", "ragged_acgt", sel, flags)
+
+
+def test_a_capacity_one_short_leaves_the_rest_of_the_buffer_alone(sets):
+    """4,097 codes into codes_cap = 4,096: refused, and nothing is written at or behind the capacity"""
+    from shannon_amd import _lib
+    sel, flags = _block_edge(sets)
+    sel, flags = np.append(sel, np.uint32(0)), np.append(flags, np.uint8(1))
+    want, _off = _expected(sets, "L32_acgt", "ragged_acgt", sel, flags)
+    assert len(want) == 4097
+    buf = np.full(4097 + 64, 0xAB, np.uint8)
+    total = C.c_uint64(0)
+    rc = _lib.lib().shn_reads_collect(sets.ctx.h, sets.dev["L32_acgt"].h, sets.dev["ragged_acgt"].h, sel.ctypes.data, flags.ctypes.data, len(sel), None,
+                                      buf.ctypes.data, 4096, C.byref(total))
+    assert rc != 0 and "codes_cap" in _lib.lib().shn_last_error().decode()
+    assert total.value == 4097                                     # (a ragged set: the device's total, known after the call)
+    assert np.all(buf[4096:] == 0xAB)
+    assert np.array_equal(buf[:4096], want[:4096])
+    _check(sets, "L32_acgt", "ragged_acgt", sel, flags)            # the context stays usable
 
 
 def test_bad_arguments_are_refused_and_the_context_stays_usable(sets):

@@ -416,6 +416,35 @@ int shn_filter_fp_cover(shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off
 int shn_filter_fp_count(shn_ctx* ctx, const uint64_t* covers, uint32_t n_covers, uint64_t n_words, uint64_t word0, const uint64_t* t_off,
                         uint64_t n_tr, uint32_t* hits);
 
+/* ---- --kallisto_cutoff: abundance of the final transcripts ------------------------------------------
+ * shannon.py:309-318, 609-614 and filter_kallisto.py:23-31 run `kallisto index` + `kallisto quant` on rec_before_kallisto.fasta and
+ * the original read files; kallisto is replaced by the rule of DESIGN.md 3.10.  The decision (filter_kallisto.py:8-21) stays on the
+ * host (shannon_amd/abundance.py).
+ *
+ * shn_abundance_classes -- what `kallisto quant` learns from pseudoalignment (filter_kallisto.py:29): for every pair of the two
+ * resident sets the set of transcripts that hold a concordant placement of its minimum cost (rules 2-5 of shn_filter_fp_hits, all
+ * transcripts one partition), the pairs with equal sets merged into classes.
+ *   text, t_off[n_tr + 1]  the transcripts one after the other; ACGT only; one shorter than SHN_FILTER_FP_SEED must be handed over empty
+ *   r1, r2                 the mates as the user gave them (all their pairs take part); max_span <= 8191
+ *   out                    a handle: sizes, classes as a CSR (members ascending inside a class), pairs per class, and the histogram of
+ *                          the spans v + |y| - u of the pairs that have exactly one placement of their minimum cost               */
+typedef struct shn_abundance shn_abundance;
+int shn_abundance_classes(shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off, uint64_t n_tr, const shn_reads* r1, const shn_reads* r2,
+                          int strand_specific, uint32_t max_span, shn_abundance** out);
+/* sizes[6]: transcripts, pairs, mapped pairs, classes, members of all classes, bins of the histogram (max_span + 1) */
+int shn_abundance_sizes(const shn_abundance* a, uint64_t* sizes);
+/* class_off[classes + 1], members[class_off[classes]], n_c[classes], hist[max_span + 1] (host) */
+int shn_abundance_export(const shn_abundance* a, uint64_t* class_off, uint32_t* members, uint64_t* n_c, uint64_t* hist);
+void shn_abundance_destroy(shn_abundance* a);
+/* shn_abundance_em -- the EM of `kallisto quant` (filter_kallisto.py:29; its est_counts column is what filter_kallisto.py:13-14 reads)
+ * on classes given as HOST arrays: alpha_j = 1 / m, then rounds of d_c = sum_{j in c} alpha_j / eff_j, alpha'_j = sum_{c with j}
+ * n_c (alpha_j / eff_j) / d_c in IEEE double with a fixed order of every sum (DESIGN.md 3.10 rule 4); tested after rounds 50, 100, ...,
+ * ends after 10,000 at the latest; alpha_j < 1e-8 is returned as 0.  Refused before anything is launched: m == 0, a class_off that
+ * is not monotone or does not start at 0, a member >= m, an eff that is not above 0.
+ *   alpha[m] (host, written), *rounds = rounds run */
+int shn_abundance_em(shn_ctx* ctx, const uint64_t* class_off, const uint32_t* members, const uint64_t* n_c, uint64_t n_classes, const double* eff,
+                     uint64_t m, double* alpha, uint32_t* rounds);
+
 /* ---- K-mer seed scans of reads against graph nodes -----------------------------------------------
  * Replace the per-read Python loops of Read.find_bridging_reads (mbgraph.py:88-111) and known_paths
  * (mbgraph.py:1355-1388).  `patterns`: plain K-mer keys -> value = id+1 (shn_table_create).

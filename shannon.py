@@ -3,8 +3,8 @@
 
 Keeps the reference CLI (sreeramkannan/Shannon shannon.py:145-321) for the flags that drive the
 hot path and produces the same products: OUT/shannon.fasta, OUT/log.txt, OUT/TEMP/ (shannon.py:
-634-638).  Flags that only select external tools outside the path (quorum, kallisto, --compare)
-are accepted and reported as not built.
+634-638).  Flags that only select external tools outside the path (quorum, --compare) are accepted
+and reported as not built.
 
     python shannon.py -o OUT --single reads.fasta            [-K 25] [--partition 500]
     python shannon.py -o OUT --left r1.fasta --right r2.fasta [-s / --ss / --strand_specific]
@@ -18,6 +18,12 @@ are accepted and reported as not built.
                                  the rule of DESIGN.md "filter_FP", run on the GPU); per partition TEMP/<sample>_<name>algo_output/ then holds
                                  reconstructed.fasta (filtered), reconstructed_org.fasta and rec.log
                                  (with -p N as well: the ranks' coverage is merged at the partitions' owners, the result is the one-process one)
+    ... [--kallisto_cutoff C]    FASTQ input only (a first read file whose name ends in `q`, or --fastq; --fasta turns it off), as in the
+                                 reference (shannon.py:289-318): the final transcripts are quantified against all read pairs and one stays
+                                 only if est_counts / eff_length * L >= C (shannon.py:609-614, filter_kallisto.py:8-21; kallisto itself is
+                                 the rule of DESIGN.md 3.10, run on the GPU); TEMP/<sample>_allalgo_output/ then holds
+                                 rec_before_kallisto.fasta and kallisto/abundance.tsv, OUT/shannon.fasta the filtered transcripts
+                                 (paired-end, one-process runs; otherwise a NOTE and nothing is filtered)
     python shannon.py -o OUT --left r1.fasta --right r2.fasta -p 8        # one rank per GPU (the reference's -p nJobs, shannon.py:527-566)
 
 -p N / --gpus N: the reference fans its partitions out over nJobs processes (GNU parallel, shannon.py:527-566); here the N jobs
@@ -256,10 +262,11 @@ def parse_args(argv):
     kmer_hard_cutoff = 1                                      # jellyfish_kmer_cutoff: shannon.py:55
     i = 1
     ignored, noted = [], []
-    takes_value = ("-o", "--single", "--left", "--right", "-K", "-p", "--gpus", "--partition", "--kmer_hard_cutoff", "--kmer_soft_cutoff")
+    takes_value = ("-o", "--single", "--left", "--right", "-K", "-p", "--gpus", "--partition", "--kmer_hard_cutoff", "--kmer_soft_cutoff", "--kallisto_cutoff")
     n_gpus = 0
     filter_fp = False
     in_disk = False
+    fastq_flag, fasta_flag, kallisto_arg, kallisto_at = False, False, None, 0
     while i < len(argv):
         a = argv[i]
         if a in takes_value and i + 1 >= len(argv):
@@ -298,6 +305,7 @@ def parse_args(argv):
             # shannon.py:166-207, 407-411: no strand doubling; of a pair, RC(reads_2) stands for reads_2
             double_stranded = False; i += 1; continue
         if a in ("--inMem", "--fasta", "--fastq"):
+            fastq_flag, fasta_flag = fastq_flag or a == "--fastq", fasta_flag or a == "--fasta"
             i += 1; continue
         if a == "--filter_FP":
             # shannon.py:170-174 (the reference refuses it with --inMem, :195, because it needs the read files; here the reads are resident)
@@ -314,9 +322,34 @@ def parse_args(argv):
                          "products but not reads{comp}.fasta / component*k1mers_allowed.dict (shannon_amd/reference_api.py writes those "
                          "when a single stage is driven through the reference's file interface)" % a)
             i += 1; continue
-        if a in ("--compare", "--kallisto_cutoff"):
+        if a == "--kallisto_cutoff":
+            # shannon.py:309-318: what the flag means is known once all of argv is read (the read files' names, --fastq, --fasta)
+            kallisto_arg, kallisto_at = argv[i + 1], len(ignored); i += 2; continue
+        if a == "--compare":
             ignored.append(a); i += 2; continue
         ignored.append(a); i += 1
+    kallisto_cutoff = None
+    if kallisto_arg is not None:
+        # shannon.py:289-307: FASTQ by the first read file's last letter or --fastq; --fasta turns it off
+        fastq = ((bool(reads) and reads[0][-1:] == "q") or fastq_flag) and not fasta_flag
+        if fastq:
+            try:
+                kallisto_cutoff = float(kallisto_arg)
+            except ValueError:
+                print("ERROR: --kallisto_cutoff needs a number, got %s" % kallisto_arg)
+                return 2
+            print("OPTIONS --kallisto_cutoff: Kallisto will be run to filter low expression transcripts below " + str(kallisto_cutoff))
+            if len(reads) != 2:
+                noted.append("--kallisto_cutoff: single-end input is not built (the reference runs kallisto --single -l 200 -s 20, "
+                             "filter_kallisto.py:25); nothing is filtered")
+                kallisto_cutoff = None
+            elif max(nJobs, n_gpus) > 1:
+                noted.append("--kallisto_cutoff: the abundance filter is built for one-process runs only; with -p N / --gpus N nothing is "
+                             "filtered")
+                kallisto_cutoff = None
+        else:
+            print("OPTIONS WARNING: --kallisto_cutoff NOT enabled. Option only works with fastq input.")
+            ignored.insert(kallisto_at, "--kallisto_cutoff")
     if filter_fp and len(reads) != 2:
         # run_MB_SF_fn.py:110: `if '--filter_FP' in n_inp and paired_end`
         noted.append("--filter_FP: single-end input -- the reference applies the filter to paired-end runs only (run_MB_SF_fn.py:110); "
@@ -333,6 +366,7 @@ def parse_args(argv):
     o.out_dir, o.reads, o.double_stranded = out_dir, reads, double_stranded
     o.min_weight, o.min_length, o.kmer_hard_cutoff = min_weight, min_length, kmer_hard_cutoff
     o.ignored, o.noted, o.filter_fp = ignored, noted, filter_fp
+    o.kallisto_cutoff = kallisto_cutoff
     return o
 
 
@@ -425,11 +459,12 @@ def main(argv):
         R = pipeline.assemble_resident(ctx, sets[0], sets[1] if paired else None, kfc.ReadStore(r[0], r[1] if paired else None), K=K,
                                        partition_size=partition_size, min_weight=min_weight, min_length=min_length, sample=sample, seed=0,
                                        double_stranded=double_stranded, timings=T, kmer_hard_cutoff=kmer_hard_cutoff,
-                                       filter_fp=filter_fp, in_disk_dir=temp if o.in_disk else None)
+                                       filter_fp=filter_fp, in_disk_dir=temp if o.in_disk else None, kallisto_cutoff=o.kallisto_cutoff)
     else:
         R = pipeline.assemble(ctx, r[0], r[1] if paired else None, K=K, partition_size=partition_size, min_weight=min_weight,
                               min_length=min_length, sample=sample, seed=0, double_stranded=double_stranded, timings=T,
-                              kmer_hard_cutoff=kmer_hard_cutoff, filter_fp=filter_fp, in_disk_dir=temp if o.in_disk else None)
+                              kmer_hard_cutoff=kmer_hard_cutoff, filter_fp=filter_fp, in_disk_dir=temp if o.in_disk else None,
+                              kallisto_cutoff=o.kallisto_cutoff)
     if o.in_disk:
         say("--inDisk: reads*.fasta and k1mer.dict of %d partitions under %s (%d bytes)"
             % (len(R.in_disk), temp, sum(sum(f.values()) for f in R.in_disk.values())))
@@ -460,6 +495,18 @@ def main(argv):
     alld = os.path.join(temp, sample + "_allalgo_output")
     os.makedirs(alld)
     open(os.path.join(alld, "all_reconstructed.fasta"), "w").write("".join(R.all_reconstructed))
+    if getattr(R, "abundance", None) is not None:
+        # shannon.py:611-614: the merged transcripts move to rec_before_kallisto.fasta, `kallisto quant -o <dir>/kallisto` leaves
+        # abundance.tsv there, what filter_using_kallisto keeps becomes the final FASTA
+        ab = R.abundance
+        os.makedirs(os.path.join(alld, "kallisto"))
+        open(os.path.join(alld, "rec_before_kallisto.fasta"), "w").write(ab["before"])
+        open(os.path.join(alld, "kallisto", "abundance.tsv"), "w").write(ab["tsv"])
+        say("--kallisto_cutoff %s: %d of %d fragments mapped, %d classes, %d EM rounds, L %s; %d of %d transcripts kept"
+            % (o.kallisto_cutoff, ab["mapped"], ab["fragments"], ab["classes"], ab["rounds"], repr(ab["L"]), ab["kept"], len(ab["names"])))
+        tm, tb = ctx.timers(), ctx.timer_bytes()                    # (HIP events around the launches, the bytes their sites price)
+        say("abundance kernels: " + json.dumps({k: {"ms": round(v[0], 4), "regions": v[1], "bytes": tb.get(k, 0)}
+                                                for k, v in sorted(tm.items()) if k.startswith("abundance.")}))
     if hasattr(R.final, "fasta"):                                   # (the native merge's buffers: the file's text without a string per record)
         with open(os.path.join(out_dir, "shannon.fasta"), "wb") as f:
             f.write(R.final.fasta())

@@ -74,6 +74,11 @@ SIGNATURES = {
     "shn_filter_fp_hits": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_uint32, vp, vp]),
     "shn_filter_fp_cover": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_uint32, vp, vp]),
     "shn_filter_fp_count": (C.c_int, [vp, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp]),
+    "shn_abundance_classes": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, C.c_int, C.c_uint32, vpp]),
+    "shn_abundance_sizes": (C.c_int, [vp, vp]),
+    "shn_abundance_export": (C.c_int, [vp, vp, vp, vp, vp]),
+    "shn_abundance_destroy": (None, [vp]),
+    "shn_abundance_em": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp]),
     "shn_lp_solve_batch": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]),
     "shn_lp_set_rule": (C.c_int, [vp, C.c_int]),
     "shn_lp_stats": (C.c_int, [vp, vp, C.c_int]),

@@ -1,0 +1,181 @@
+"""--kallisto_cutoff: drop the final transcripts that the reads barely express (shannon.py:309-318, 609-614, filter_kallisto.py).
+
+The reference moves reconstructed.fasta to rec_before_kallisto.fasta, runs `kallisto index` + `kallisto quant` on it and the
+original read files, and filter_using_kallisto (filter_kallisto.py:8-21) keeps a transcript when est_counts / eff_length * L of
+its abundance.tsv line reaches the cutoff.  Here kallisto is a stated rule run on the device
+(csrc/abundance.hip: shn_abundance_classes, shn_abundance_em); the table's text and the decision are the reference's, made on the host:
+
+    classes        the pairs' compatibility classes, span histogram and mapped count (the first device call)
+    eff_lengths    rule 2: effective lengths from the integer histogram, in double
+    em             rule 4 on host arrays of classes (the second device call)
+    quantify       names + sequences + resident mates -> table (classes, eff_lengths, em, tpm)
+    abundance_tsv  table -> the text of abundance.tsv, floats written with repr
+    decide         filter_kallisto.py:8-21 on the TEXT of abundance.tsv and of the FASTA -> the text of the filtered FASTA
+    apply          final transcripts {name: sequence} -> (filtered {name: sequence}, table, tsv text, FASTA text before)
+
+`eff_lengths`, `abundance_tsv` and `decide` need neither the library nor a GPU.
+"""
+import ctypes as C
+import io
+import numpy as np
+
+MAX_SPAN = 500        # as --filter_FP: the longest fragment a concordant pair may span
+SEED = 15             # a transcript shorter than this takes part in no class
+HEADER = "target_id\tlength\teff_length\test_counts\ttpm\n"
+
+
+def classes(ctx, seqs, d1, d2, strand_specific, max_span=MAX_SPAN):
+    """rules 1-3 (shn_abundance_classes): {"class_off", "members", "n_c", "hist", "mapped", "fragments"}.  A transcript shorter
+    than SEED bases or with a base outside ACGT is handed over empty: it takes part in no class."""
+    from . import _lib
+    seqs = [s if len(s) >= SEED and not s.encode().translate(None, b"ACGTacgt") else "" for s in seqs]
+    n_tr = len(seqs)
+    t_off = np.zeros(n_tr + 1, dtype=np.uint64)
+    if n_tr:
+        t_off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+    joined = "".join(seqs).encode()
+    text = np.frombuffer(joined, dtype=np.uint8) if joined else np.zeros(1, np.uint8)
+    h = C.c_void_p()
+    lib = _lib.lib()
+    _lib.check(lib.shn_abundance_classes(ctx.h, text.ctypes.data, t_off.ctypes.data, n_tr, d1.h, d2.h, 1 if strand_specific else 0, int(max_span),
+                                         C.byref(h)))
+    try:
+        sizes = np.zeros(6, dtype=np.uint64)
+        _lib.check(lib.shn_abundance_sizes(h, sizes.ctypes.data))
+        _n_tr, n_frag, mapped, n_classes, n_entries, n_bins = (int(x) for x in sizes)
+        class_off = np.zeros(n_classes + 1, dtype=np.uint64)
+        members = np.zeros(max(n_entries, 1), dtype=np.uint32)
+        n_c = np.zeros(max(n_classes, 1), dtype=np.uint64)
+        hist = np.zeros(n_bins, dtype=np.uint64)
+        _lib.check(lib.shn_abundance_export(h, class_off.ctypes.data, members.ctypes.data, n_c.ctypes.data, hist.ctypes.data))
+    finally:
+        lib.shn_abundance_destroy(h)
+    return {"class_off": class_off, "members": members[:n_entries], "n_c": n_c[:n_classes], "hist": hist, "mapped": mapped, "fragments": n_frag}
+
+
+def eff_lengths(lens, hist):
+    """rule 2: eff_j = len_j - mu_{len_j} + 1, mu_l = (sum of s h[s] over s <= l) / (sum of h[s] over s <= l), the two sums as
+    integers and their quotient rounded once to double; eff_j = len_j when that is < 1 or when no span is <= len_j."""
+    h = [int(x) for x in hist]
+    cnt, tot = [0] * (len(h) + 1), [0] * (len(h) + 1)            # prefix sums: spans < s
+    for s, x in enumerate(h):
+        cnt[s + 1] = cnt[s] + x
+        tot[s + 1] = tot[s] + s * x
+    out = []
+    for n in lens:
+        n = int(n)
+        k = min(n, len(h) - 1) + 1
+        eff = float(n)
+        if k > 0 and cnt[k]:
+            e = float(n) - tot[k] / cnt[k] + 1.0
+            if e >= 1.0:
+                eff = e
+        out.append(eff)
+    return np.array(out, dtype=np.float64)
+
+
+def em(ctx, class_off, members, n_c, eff):
+    """rule 4 (shn_abundance_em) on host arrays -> (alpha float64[m], rounds)"""
+    from . import _lib
+    class_off = np.ascontiguousarray(class_off, dtype=np.uint64)
+    members = np.ascontiguousarray(members, dtype=np.uint32)
+    n_c = np.ascontiguousarray(n_c, dtype=np.uint64)
+    eff = np.ascontiguousarray(eff, dtype=np.float64)
+    n_classes, m = len(class_off) - 1, len(eff)
+    if n_classes < 0 or len(n_c) != n_classes:
+        raise ValueError("abundance.em: class_off has %d entries for %d class counts" % (len(class_off), len(n_c)))
+    if n_classes and int(class_off[-1]) > len(members):
+        raise ValueError("abundance.em: class_off ends at %d, %d members given" % (int(class_off[-1]), len(members)))
+    alpha = np.zeros(max(m, 1), dtype=np.float64)
+    rounds = C.c_uint32(0)
+    _lib.check(_lib.lib().shn_abundance_em(ctx.h, class_off.ctypes.data, members.ctypes.data if len(members) else None,
+                                           n_c.ctypes.data if n_classes else None, n_classes, eff.ctypes.data if m else None, m, alpha.ctypes.data,
+                                           C.byref(rounds)))
+    return alpha[:m], int(rounds.value)
+
+
+def tpm_of(alpha, eff):
+    """tpm_j = 1e6 (alpha_j / eff_j) / sum_k (alpha_k / eff_k), the sum in index order; all zeros when nothing is mapped"""
+    rho = [float(a) / float(e) for a, e in zip(alpha, eff)]
+    total = 0.0
+    for r in rho:
+        total += r
+    return [1e6 * r / total if total > 0.0 else 0.0 for r in rho]
+
+
+def quantify(ctx, names, seqs, d1, d2, strand_specific, max_span=MAX_SPAN):
+    """the abundance table of the transcripts (names[j], seqs[j]) under the pairs of the resident sets d1 / d2 (device.Reads, the mates
+    as the user gave them): {"names", "length", "eff_length", "est_counts", "tpm"} (lists, in the order given) + "mapped",
+    "fragments", "classes", "rounds", "hist"."""
+    if len(names) != len(seqs):
+        raise ValueError("quantify: %d names for %d sequences" % (len(names), len(seqs)))
+    lens = [len(s) for s in seqs]
+    if not seqs:
+        return {"names": [], "length": [], "eff_length": [], "est_counts": [], "tpm": [], "mapped": 0, "fragments": len(d1), "classes": 0,
+                "rounds": 0, "hist": np.zeros(max_span + 1, np.uint64)}
+    cl = classes(ctx, seqs, d1, d2, strand_specific, max_span)
+    eff = eff_lengths(lens, cl["hist"])
+    alpha, rounds = em(ctx, cl["class_off"], cl["members"], cl["n_c"], eff)
+    return {"names": list(names), "length": lens, "eff_length": eff.tolist(), "est_counts": alpha.tolist(), "tpm": tpm_of(alpha, eff),
+            "mapped": cl["mapped"], "fragments": cl["fragments"], "classes": len(cl["n_c"]), "rounds": rounds, "hist": cl["hist"]}
+
+
+def abundance_tsv(table):
+    """the text of abundance.tsv: kallisto's header, then target_id, length, eff_length, est_counts, tpm per transcript, the floats
+    written with repr -- what filter_using_kallisto parses back is what was computed"""
+    out = [HEADER]
+    for name, n, el, ec, tpm in zip(table["names"], table["length"], table["eff_length"], table["est_counts"], table["tpm"]):
+        out.append("%s\t%d\t%s\t%s\t%s\n" % (name, n, repr(float(el)), repr(float(ec)), repr(float(tpm))))
+    return "".join(out)
+
+
+def decide(tsv_text, fasta_text, cutoff, L):
+    """filter_kallisto.py:8-21 on texts: a transcript is accepted iff float(est_counts) / float(eff_length) * L >= cutoff; a line of
+    the FASTA is written iff the last header line before it (itself included) names an accepted transcript -- `write_now` starts True
+    and carries over to the lines that follow."""
+    accepted = set()
+    lines = list(io.StringIO(tsv_text, newline=None))           # (the lines a file opened in text mode gives)
+    for line in lines[1:]:                                      # (:11 f.readline() skips the header)
+        name, _, el, ec, _weight = line.split()
+        cov = float(ec) / float(el) * L
+        if cov >= cutoff:
+            accepted.add(name)
+    write_now, out = True, []
+    for line in io.StringIO(fasta_text, newline=None):
+        fields = line.strip().split()
+        if fields and fields[0][0] == ">":
+            write_now = fields[0][1:] in accepted
+        if write_now:
+            out.append(line)
+    return "".join(out)
+
+
+def fragment_bases(d1, d2):
+    """L of the decision: (bases of reads_1 + bases of reads_2) / pairs -- for mates of one length the reference's
+    L * len(original_reads_files), shannon.py:613"""
+    from . import _lib
+    lib = _lib.lib()
+    n = len(d1)
+    return (int(lib.shn_reads_total_bases(d1.h)) + int(lib.shn_reads_total_bases(d2.h))) / n if n else 0.0
+
+
+def apply(ctx, final, d1, d2, strand_specific, cutoff, max_span=MAX_SPAN):
+    """the whole step on the final transcripts (a mapping name -> sequence in file order): (kept {name: sequence}, table, tsv text,
+    text of rec_before_kallisto.fasta)"""
+    names, seqs = [], []
+    for name, seq in final.items():
+        names.append(name)
+        seqs.append(seq)
+    before = "".join(">%s\n%s\n" % (n, s) for n, s in zip(names, seqs))
+    table = quantify(ctx, names, seqs, d1, d2, strand_specific, max_span)
+    tsv = abundance_tsv(table)
+    table["L"] = fragment_bases(d1, d2)
+    kept_text = decide(tsv, before, float(cutoff), table["L"])
+    kept, name = {}, None
+    for line in kept_text.splitlines():
+        if line.startswith(">"):
+            name = line[1:]
+        elif name is not None:
+            kept[name] = line
+    table["kept"] = len(kept)
+    return kept, table, tsv, before

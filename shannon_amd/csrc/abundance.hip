@@ -1,0 +1,523 @@
+// --kallisto_cutoff on the device: how many read pairs every final transcript explains (shannon.py:309-318, 609-614,
+// filter_kallisto.py:23-31 -- `kallisto index` + `kallisto quant`).  kallisto is replaced by the rule of DESIGN.md 3.10 ("abundance");
+// the kernels below state the part of it they implement.  The placement of a pair is --filter_FP's (filter_fp_dev.h: the same
+// index, the same enumeration), all transcripts forming one partition.
+//
+//   map      one thread per fragment, three passes over the same enumeration: the minimum cost; the number of placements that attain
+//            it (and the span of the only one: the fragment-length histogram, integer atomics in LDS, then one global add per
+//            bin and block); behind an exclusive scan of the numbers, the placements' transcript ids -- count, scan, fill, so
+//            nothing is capped.  The filling thread then sorts its list, drops the repeats (two placements on one transcript)
+//            and hashes what is left.
+//   classes  the fragments sorted by the hash of their list (shn_sort_pairs, stable: equal hashes stay in fragment order; an
+//            unmapped fragment carries the largest key and ends up behind the mapped ones); a fragment heads a class iff its LIST
+//            differs from its predecessor's, element by element -- two lists with one hash give two classes, a hash that falls
+//            between two runs of one list splits that list's class in two, which the EM does not notice; scan of the head flags ->
+//            class_off[] / members[] / n_c[].
+//   EM       the transposed CSR once (entries sorted by transcript with the same stable sort: a transcript's entries stay in class
+//            order); a round is two gather passes, a wave a row: d_c = sum over the members of alpha_j / eff_j, then alpha'_j = sum
+//            over the classes of j of n_c (alpha_j / eff_j) / d_c.  Every sum has ONE order: lane l adds the row's terms l, l + 64,
+//            l + 128, ... in that order, starting from 0, then the 64 partial sums meet in the shuffle tree of strides 32, 16, 8, 4, 2, 1
+//            (lane l takes lane l + stride).  No floating-point atomic anywhere: two runs give the same bits.
+#include "filter_fp_dev.h"
+
+#define ABD_MAX_SPAN 8191u     // bins of the span histogram a block keeps in LDS (32 KiB); a larger max_span is refused
+#define ABD_INSERTION 32u      // a fragment's list up to this many ids is sorted by insertion, a longer one by heapsort
+
+struct shn_abundance {
+  uint64_t n_tr = 0, n_frag = 0, mapped = 0;
+  std::vector<uint64_t> class_off, n_c, hist;
+  std::vector<uint32_t> members;
+};
+
+// f(j, span) for every placement of fragment i whose cost is `best` (both oriented pairs unless strand-specific)
+template <class F>
+__device__ __forceinline__ void abd_each_best(const FfpIndex& I, const FfpSet& A, const FfpSet& B, uint64_t i, int ss, uint32_t max_span,
+                                              uint32_t best, F&& f) {
+  const FfpRead a = ffp_read(A, i, false), b_rc = ffp_read(B, i, true);
+  ffp_each_placement<true>(I, 0, a, b_rc, max_span, &best, [&](uint32_t c, uint64_t j, uint64_t u, uint64_t v) {
+    if (c == best) f(j, (uint32_t)(v + b_rc.L - u));
+  });
+  if (!ss) {
+    const FfpRead b = ffp_read(B, i, false), a_rc = ffp_read(A, i, true);
+    ffp_each_placement<true>(I, 0, b, a_rc, max_span, &best, [&](uint32_t c, uint64_t j, uint64_t u, uint64_t v) {
+      if (c == best) f(j, (uint32_t)(v + a_rc.L - u));
+    });
+  }
+}
+
+// pass 1 + 2: best[i] = the fragment's minimum cost (FFP_NONE: unmapped), cnt[i] = placements of that cost; a fragment with exactly one
+// adds 1 to the bin of its span
+__global__ __launch_bounds__(FFP_BLOCK) void abd_count_kernel(FfpIndex I, FfpSet A, FfpSet B, uint64_t n_pairs, int ss, uint32_t max_span,
+                                                              uint32_t* __restrict__ best_out, uint32_t* __restrict__ cnt,
+                                                              unsigned long long* __restrict__ hist, unsigned long long* __restrict__ n_mapped,
+                                                              uint32_t* __restrict__ too_many) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t abd_lh[];
+  for (uint32_t k = threadIdx.x; k <= max_span; k += FFP_BLOCK) abd_lh[k] = 0;
+  __syncthreads();
+  const uint64_t i = (uint64_t)blockIdx.x * FFP_BLOCK + threadIdx.x;
+  bool placed = false;
+  if (i < n_pairs) {
+    uint32_t best = FFP_NONE;
+    ffp_min_cost(I, 0, ffp_read(A, i, false), ffp_read(B, i, true), max_span, &best);
+    if (!ss) ffp_min_cost(I, 0, ffp_read(B, i, false), ffp_read(A, i, true), max_span, &best);
+    uint64_t n = 0;
+    uint32_t span = 0;
+    if (best != FFP_NONE) abd_each_best(I, A, B, i, ss, max_span, best, [&](uint64_t, uint32_t sp) { n++; span = sp; });
+    if (n > 0xFFFFFFFEULL) { atomicOr(too_many, 1u); n = 0; }
+    placed = n != 0;
+    best_out[i] = placed ? best : FFP_NONE;
+    cnt[i] = (uint32_t)n;
+    if (n == 1 && span <= max_span) atomicAdd(&abd_lh[span], 1u);
+  }
+  const unsigned long long vote = __ballot(placed);
+  if ((threadIdx.x & 63) == 0 && vote) atomicAdd(n_mapped, (unsigned long long)__popcll(vote));
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k <= max_span; k += FFP_BLOCK)
+    if (abd_lh[k]) atomicAdd(&hist[k], (unsigned long long)abd_lh[k]);
+}
+
+__device__ __forceinline__ uint64_t abd_mix(uint64_t h, uint64_t v) {
+  h ^= v + 0x9E3779B97F4A7C15ULL;
+  h ^= h >> 33; h *= 0xFF51AFD7ED558CCDULL; h ^= h >> 33; h *= 0xC4CEB9FE1A85EC53ULL; h ^= h >> 33;
+  return h;
+}
+
+// max-heap L[0 .. n): the value at p sinks to its place
+__device__ __forceinline__ void abd_sift_down(uint32_t* L, uint64_t p, uint64_t n) {
+  const uint32_t v = L[p];
+  for (;;) {
+    uint64_t c = 2 * p + 1;
+    if (c >= n) break;
+    if (c + 1 < n && L[c + 1] > L[c]) c++;
+    if (L[c] <= v) break;
+    L[p] = L[c];
+    p = c;
+  }
+  L[p] = v;
+}
+
+// pass 3: the transcript ids of fragment i's placements into ids[off[i] .. off[i + 1]), sorted, repeats dropped: nuniq[i] of them
+// stay at the front.  key[i] = 63 bits of the list's hash; an unmapped fragment: all ones.
+__global__ __launch_bounds__(FFP_BLOCK) void abd_fill_kernel(FfpIndex I, FfpSet A, FfpSet B, uint64_t n_pairs, int ss, uint32_t max_span,
+                                                             const uint32_t* __restrict__ best_in, const uint64_t* __restrict__ off,
+                                                             uint32_t* __restrict__ ids, uint32_t* __restrict__ nuniq, uint64_t* __restrict__ key,
+                                                             uint32_t* __restrict__ frag) {
+  const uint64_t i = (uint64_t)blockIdx.x * FFP_BLOCK + threadIdx.x;
+  if (i >= n_pairs) return;
+  frag[i] = (uint32_t)i;
+  const uint64_t o = off[i], n = off[i + 1] - o;
+  if (n == 0) { nuniq[i] = 0; key[i] = ~0ULL; return; }
+  uint32_t* L = ids + o;
+  uint64_t k = 0;
+  abd_each_best(I, A, B, i, ss, max_span, best_in[i], [&](uint64_t j, uint32_t) { if (k < n) L[k] = (uint32_t)j; k++; });
+  // (k == n: the same enumeration as the counting pass.)  The list is a few ascending runs, one per seed and orientation (a seed's
+  // hits are in text order).  Up to ABD_INSERTION ids: insertion sort; a longer list (a fragment inside a repeat that many
+  // transcripts share) by heapsort in place, so that one lane never does more than n log n moves while its wave waits.
+  if (n <= ABD_INSERTION) {
+    for (uint64_t p = 1; p < n; p++) {
+      const uint32_t v = L[p];
+      uint64_t q = p;
+      while (q > 0 && L[q - 1] > v) { L[q] = L[q - 1]; q--; }
+      L[q] = v;
+    }
+  } else {
+    for (uint64_t p = n / 2; p-- > 0;) abd_sift_down(L, p, n);
+    for (uint64_t e = n - 1; e > 0; e--) {
+      const uint32_t v = L[0]; L[0] = L[e]; L[e] = v;
+      abd_sift_down(L, 0, e);
+    }
+  }
+  uint64_t u = 1;
+  for (uint64_t p = 1; p < n; p++)
+    if (L[p] != L[u - 1]) L[u++] = L[p];
+  uint64_t h = abd_mix(0, u);
+  for (uint64_t p = 0; p < u; p++) h = abd_mix(h, L[p]);
+  nuniq[i] = (uint32_t)u;
+  key[i] = h >> 1;
+}
+
+// sorted position r heads a class iff its fragment's list is not its predecessor's
+__global__ void abd_heads_kernel(uint64_t n_mapped, const uint32_t* __restrict__ frag, const uint64_t* __restrict__ off, const uint32_t* __restrict__ nuniq,
+                                 const uint32_t* __restrict__ ids, uint32_t* __restrict__ head) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_mapped) return;
+  uint32_t h = 1;
+  if (r) {
+    const uint32_t f = frag[r], g = frag[r - 1];
+    const uint32_t n = nuniq[f];
+    if (n == nuniq[g]) {
+      const uint32_t *a = ids + off[f], *b = ids + off[g];
+      uint32_t p = 0;
+      while (p < n && a[p] == b[p]) p++;
+      h = p < n;
+    }
+  }
+  head[r] = h;
+}
+
+// class c = the head flags before its head: first[c] = sorted position of its head, size[c] = members
+__global__ void abd_first_kernel(uint64_t n_mapped, uint64_t n_classes, const uint32_t* __restrict__ head, const uint64_t* __restrict__ head_scan,
+                                 const uint32_t* __restrict__ frag, const uint32_t* __restrict__ nuniq, uint64_t* __restrict__ first,
+                                 uint32_t* __restrict__ size) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_mapped) return;
+  if (head[r]) {
+    const uint64_t c = head_scan[r];
+    if (c < n_classes) { first[c] = r; size[c] = nuniq[frag[r]]; }
+  }
+  if (r == n_mapped - 1) first[n_classes] = n_mapped;
+}
+
+__global__ void abd_members_kernel(uint64_t n_classes, const uint64_t* __restrict__ first, const uint32_t* __restrict__ frag,
+                                   const uint64_t* __restrict__ off, const uint32_t* __restrict__ ids, const uint64_t* __restrict__ class_off,
+                                   uint32_t* __restrict__ members, uint64_t* __restrict__ n_c) {
+  const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_classes) return;
+  const uint32_t* src = ids + off[frag[first[c]]];
+  const uint64_t o = class_off[c], n = class_off[c + 1] - o;
+  for (uint64_t p = 0; p < n; p++) members[o + p] = src[p];
+  n_c[c] = first[c + 1] - first[c];
+}
+
+// Classes of the read pairs of two resident sets on the final transcripts (kallisto's pseudoalignment, `kallisto quant`,
+// filter_kallisto.py:29, replaced by DESIGN.md 3.10 rules 1-3).
+extern "C" int shn_abundance_classes(shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off, uint64_t n_tr, const shn_reads* r1, const shn_reads* r2,
+                                     int strand_specific, uint32_t max_span, shn_abundance** out) {
+  const std::string fn("shn_abundance_classes");
+  if (!ctx || !r1 || !r2 || !t_off || !out || (n_tr && !text)) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
+  if (r1->n_reads != r2->n_reads) return shn_fail(SHN_ERR_ARG, fn + ": the two read sets are not mates of each other (different sizes)");
+  if (max_span > ABD_MAX_SPAN) return shn_fail(SHN_ERR_ARG, fn + ": max_span " + std::to_string(max_span) + " above the " + std::to_string(ABD_MAX_SPAN) +
+                                                                " bins the span histogram holds");
+  if (n_tr >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many transcripts");
+  const uint64_t n_pairs = r1->n_reads;
+  if (n_pairs >= 0xFFFFFFFEULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many read pairs in one call");
+  if (t_off[0] != 0) return shn_fail(SHN_ERR_ARG, fn + ": t_off[0] is not 0");
+  std::vector<uint64_t> rec_off(n_tr + 1, 0);
+  for (uint64_t j = 0; j < n_tr; j++) {
+    if (t_off[j + 1] < t_off[j]) return shn_fail(SHN_ERR_ARG, fn + ": t_off not monotone");
+    const uint64_t len = t_off[j + 1] - t_off[j];
+    rec_off[j + 1] = rec_off[j] + (len >= FFP_SEED ? len - FFP_SEED + 1 : 0);
+  }
+  const uint64_t total = t_off[n_tr], n_rec = rec_off[n_tr];
+  if (total >= 0xFFFFFF00ULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": more than 2^32 transcript bases in one call");
+  shn_abundance* R = new shn_abundance();
+  R->n_tr = n_tr; R->n_frag = n_pairs;
+  R->hist.assign((size_t)max_span + 1, 0);
+  R->class_off.assign(1, 0);
+  struct Guard { shn_abundance* p; ~Guard() { delete p; } } guard{R};
+  auto done = [&]() { *out = R; guard.p = nullptr; return SHN_OK; };
+  if (n_rec == 0 || n_pairs == 0) return done();
+  SHN_ENTER(ctx);
+  shn_stage_begin(ctx);
+  hipStream_t s = ctx->stream;
+  ShnDevBufs bufs(s);
+
+  // ---- index (all transcripts in partition 0)
+  FfpIndex I;
+  uint64_t n_tw = 0;
+  {
+    std::vector<uint32_t> t_part(n_tr, 0);
+    int rc = ffp_index_build(fn, ctx, bufs, T_ABD_INDEX, text, t_off, t_part.data(), n_tr, 1, rec_off, &I, &n_tw);
+    if (rc) return rc;
+  }
+
+  // ---- map: minimum cost + placements per fragment + span histogram, scan, lists
+  uint32_t *d_best = nullptr, *d_cnt = nullptr, *d_flag = nullptr, *d_ids = nullptr, *d_nuniq = nullptr, *d_frag = nullptr, *d_frag_tmp = nullptr;
+  uint64_t *d_off = nullptr, *d_key = nullptr, *d_key_tmp = nullptr;
+  unsigned long long *d_hist = nullptr, *d_mapped = nullptr;
+  const uint64_t n_bins = (uint64_t)max_span + 1;
+  HIP_TRY(bufs.get(&d_best, n_pairs * 4));
+  HIP_TRY(bufs.get(&d_cnt, n_pairs * 4));
+  HIP_TRY(bufs.get(&d_flag, 4));
+  HIP_TRY(bufs.get(&d_off, (n_pairs + 1) * 8));
+  HIP_TRY(bufs.get(&d_hist, n_bins * 8));
+  HIP_TRY(bufs.get(&d_mapped, 8));
+  HIP_TRY(hipMemsetAsync(d_flag, 0, 4, s));
+  HIP_TRY(hipMemsetAsync(d_hist, 0, n_bins * 8, s));
+  HIP_TRY(hipMemsetAsync(d_mapped, 0, 8, s));
+  FfpSet A, B;
+  uint64_t rc_bytes = 0, n_place = 0;
+  const uint32_t grid = (uint32_t)cdiv(n_pairs, FFP_BLOCK);
+  const uint64_t per_pair = (r1->n_words + r2->n_words) * 8 / n_pairs * (strand_specific ? 1 : 2);
+  {
+    TimerRegion treg(ctx, T_ABD_MAP);
+    int rc = ffp_set(ctx, bufs, r1, !strand_specific, &A, &rc_bytes);
+    if (!rc) rc = ffp_set(ctx, bufs, r2, true, &B, &rc_bytes);
+    if (rc) return rc;
+    // bytes: both mates of every fragment in each orientation used (2 bits a base), minimum cost and count written (8 B); the index
+    // and the text are re-read from the caches and priced once; a block's non-empty bins (at most 8 B each, not priced); what the
+    // reverse complements cost is added above
+    treg.bytes(rc_bytes + n_pairs * (per_pair + 8) + n_rec * 12 + n_tw * 8);
+    hipLaunchKernelGGL(abd_count_kernel, dim3(grid), dim3(FFP_BLOCK), n_bins * 4, s, I, A, B, n_pairs, strand_specific ? 1 : 0, max_span, d_best, d_cnt,
+                       d_hist, d_mapped, d_flag);
+    // the scan of the numbers: a count read, an offset written (12 B a fragment)
+    treg.bytes(n_pairs * 12);
+    rc = shn_device_scan_u32(ctx, d_cnt, n_pairs, d_off, &n_place);             // (synchronises)
+    if (rc) return rc;
+  }
+  uint32_t flag = 0;
+  unsigned long long mapped = 0;
+  HIP_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&mapped, d_mapped, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(R->hist.data(), d_hist, n_bins * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipGetLastError());
+  if (flag) return shn_fail(SHN_ERR_OVERFLOW, fn + ": a fragment has 2^32 or more placements of its minimum cost");
+  if (n_place >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": " + std::to_string(n_place) + " placements in one call (2^32 - 1 at most)");
+  R->mapped = mapped;
+  if (mapped == 0) return done();
+  HIP_TRY(bufs.get(&d_ids, (n_place + 1) * 4));
+  HIP_TRY(bufs.get(&d_nuniq, n_pairs * 4));
+  HIP_TRY(bufs.get(&d_key, (n_pairs + 1) * 8));
+  HIP_TRY(bufs.get(&d_key_tmp, (n_pairs + 1) * 8));
+  HIP_TRY(bufs.get(&d_frag, (n_pairs + 1) * 4));
+  HIP_TRY(bufs.get(&d_frag_tmp, (n_pairs + 1) * 4));
+  {
+    TimerRegion treg(ctx, T_ABD_MAP);
+    // bytes: the mates again, cost and two offsets read (20 B), the ids written, sorted in place and read for the hash (12 B a
+    // placement), count, key and fragment id written (16 B)
+    treg.bytes(n_pairs * (per_pair + 36) + n_place * 12 + n_rec * 12 + n_tw * 8);
+    hipLaunchKernelGGL(abd_fill_kernel, dim3(grid), dim3(FFP_BLOCK), 0, s, I, A, B, n_pairs, strand_specific ? 1 : 0, max_span, d_best, d_off, d_ids,
+                       d_nuniq, d_key, d_frag);
+  }
+
+  // ---- classes
+  uint32_t *d_head = nullptr, *d_size = nullptr, *d_members = nullptr;
+  uint64_t *d_head_scan = nullptr, *d_first = nullptr, *d_class_off = nullptr, *d_nc = nullptr;
+  uint64_t n_classes = 0, n_entries = 0;
+  HIP_TRY(bufs.get(&d_head, mapped * 4));
+  HIP_TRY(bufs.get(&d_head_scan, (mapped + 1) * 8));
+  {
+    TimerRegion treg(ctx, T_ABD_CLASSES);
+    // bytes: 8 sort passes over (key, fragment) pairs (24 B a pair and pass), then per mapped fragment its list and its predecessor's
+    // (8 B a member at the most: n_place bounds both), ids, counts, offsets (32 B) and the flag (4 B)
+    treg.bytes(8 * n_pairs * 24 + mapped * 36 + n_place * 8);
+    int rc = shn_sort_pairs(ctx, d_key, d_frag, d_key_tmp, d_frag_tmp, n_pairs, 0, 64);
+    if (rc) return rc;
+    hipLaunchKernelGGL(abd_heads_kernel, dim3((uint32_t)cdiv(mapped, 256)), dim3(256), 0, s, mapped, d_frag, d_off, d_nuniq, d_ids, d_head);
+    // the scan of the head flags: a flag read, a number written (12 B a mapped fragment)
+    treg.bytes(mapped * 12);
+    rc = shn_device_scan_u32(ctx, d_head, mapped, d_head_scan, &n_classes);
+    if (rc) return rc;
+  }
+  HIP_TRY(bufs.get(&d_first, (n_classes + 1) * 8));
+  HIP_TRY(bufs.get(&d_size, n_classes * 4));
+  HIP_TRY(bufs.get(&d_class_off, (n_classes + 1) * 8));
+  HIP_TRY(bufs.get(&d_nc, n_classes * 8));
+  {
+    TimerRegion treg(ctx, T_ABD_CLASSES);
+    // bytes: a mapped fragment's flag (4 B); a head's number and fragment read, its count read, first and size written (28 B a
+    // class); the scan of the sizes (12 B a class)
+    treg.bytes(mapped * 4 + n_classes * 40);
+    hipLaunchKernelGGL(abd_first_kernel, dim3((uint32_t)cdiv(mapped, 256)), dim3(256), 0, s, mapped, n_classes, d_head, d_head_scan, d_frag, d_nuniq,
+                       d_first, d_size);
+    int rc = shn_device_scan_u32(ctx, d_size, n_classes, d_class_off, &n_entries);
+    if (rc) return rc;
+  }
+  HIP_TRY(bufs.get(&d_members, (n_entries + 1) * 4));
+  {
+    TimerRegion treg(ctx, T_ABD_CLASSES);
+    // bytes: per class head, fragment, three offsets read, its count written (52 B); a member read and written (8 B)
+    treg.bytes(mapped * 16 + n_classes * 52 + n_entries * 8);
+    hipLaunchKernelGGL(abd_members_kernel, dim3((uint32_t)cdiv(n_classes, 256)), dim3(256), 0, s, n_classes, d_first, d_frag, d_off, d_ids, d_class_off,
+                       d_members, d_nc);
+  }
+  R->class_off.resize(n_classes + 1);
+  R->n_c.resize(n_classes);
+  R->members.resize(n_entries);
+  HIP_TRY(hipMemcpyAsync(R->class_off.data(), d_class_off, (n_classes + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(R->n_c.data(), d_nc, n_classes * 8, hipMemcpyDeviceToHost, s));
+  if (n_entries) HIP_TRY(hipMemcpyAsync(R->members.data(), d_members, n_entries * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipGetLastError());
+  return done();
+}
+
+extern "C" int shn_abundance_sizes(const shn_abundance* a, uint64_t* sizes) {
+  if (!a || !sizes) return shn_fail(SHN_ERR_ARG, "shn_abundance_sizes: NULL argument");
+  sizes[0] = a->n_tr; sizes[1] = a->n_frag; sizes[2] = a->mapped; sizes[3] = a->n_c.size(); sizes[4] = a->members.size(); sizes[5] = a->hist.size();
+  return SHN_OK;
+}
+
+extern "C" int shn_abundance_export(const shn_abundance* a, uint64_t* class_off, uint32_t* members, uint64_t* n_c, uint64_t* hist) {
+  if (!a || !class_off || !hist || (a->n_c.size() && !n_c) || (a->members.size() && !members))
+    return shn_fail(SHN_ERR_ARG, "shn_abundance_export: NULL argument");
+  std::copy(a->class_off.begin(), a->class_off.end(), class_off);
+  std::copy(a->members.begin(), a->members.end(), members);
+  std::copy(a->n_c.begin(), a->n_c.end(), n_c);
+  std::copy(a->hist.begin(), a->hist.end(), hist);
+  return SHN_OK;
+}
+
+extern "C" void shn_abundance_destroy(shn_abundance* a) { delete a; }
+
+// ------------------------------------------------------------------------------------------------------------------------ EM
+// the sum of a wave's partial sums in lane 0: strides 32, 16, 8, 4, 2, 1, lane l takes lane l + stride
+__device__ __forceinline__ double abd_wave_sum(double x) {
+  for (int off = 32; off; off >>= 1) x += __shfl_down(x, off, 64);
+  return x;
+}
+
+// entry e of the classes' CSR: key = its transcript, value = e; cls[e] = its class (the last c with class_off[c] <= e)
+__global__ void abd_entries_kernel(uint64_t n_entries, uint64_t n_classes, const uint64_t* __restrict__ class_off, const uint32_t* __restrict__ members,
+                                   uint64_t* __restrict__ key, uint32_t* __restrict__ val, uint32_t* __restrict__ cls) {
+  const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_entries) return;
+  uint64_t lo = 0, hi = n_classes;
+  while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (class_off[mid] <= e) lo = mid; else hi = mid; }
+  key[e] = members[e];
+  val[e] = (uint32_t)e;
+  cls[e] = (uint32_t)lo;
+}
+
+// the transposed CSR from the sorted entries: tr_off[j] = first sorted entry of transcript j (j = m: all), tr_cls[k] = class of the k-th
+__global__ void abd_transpose_kernel(uint64_t n_entries, uint64_t m, const uint64_t* __restrict__ key, const uint32_t* __restrict__ val,
+                                     const uint32_t* __restrict__ cls, uint64_t* __restrict__ tr_off, uint32_t* __restrict__ tr_cls) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n_entries) tr_cls[t] = cls[val[t]];
+  if (t <= m) {
+    uint64_t lo = 0, hi = n_entries;
+    while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (key[mid] < t) lo = mid + 1; else hi = mid; }
+    tr_off[t] = lo;
+  }
+}
+
+__global__ void abd_em_init_kernel(uint64_t m, const double* __restrict__ eff, double* __restrict__ alpha, double* __restrict__ w) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const double a = 1.0 / (double)m;
+  alpha[j] = a;
+  w[j] = a / eff[j];
+}
+
+// d_c = sum over the members of class c of w_j = alpha_j / eff_j: a wave a class
+__global__ __launch_bounds__(FFP_BLOCK) void abd_em_d_kernel(uint64_t n_classes, const uint64_t* __restrict__ class_off, const uint32_t* __restrict__ members,
+                                                             const double* __restrict__ w, double* __restrict__ d) {
+  const uint64_t c = (uint64_t)blockIdx.x * (FFP_BLOCK / 64) + (threadIdx.x >> 6);
+  if (c >= n_classes) return;                               // (the whole wave)
+  const uint32_t lane = threadIdx.x & 63;
+  double x = 0.0;
+  for (uint64_t e = class_off[c] + lane, end = class_off[c + 1]; e < end; e += 64) x += w[members[e]];
+  x = abd_wave_sum(x);
+  if (lane == 0) d[c] = x;
+}
+
+// alpha'_j = sum over the classes c of transcript j of n_c w_j / d_c (a class with d_c == 0 gives nothing): a wave a transcript.
+// check != 0: *moved is raised when alpha'_j > 1e-2 and |alpha'_j - alpha_j| > 1e-2 alpha'_j.  alpha and w are replaced in place: a
+// wave reads and writes its own transcript's only.
+__global__ __launch_bounds__(FFP_BLOCK) void abd_em_alpha_kernel(uint64_t m, const uint64_t* __restrict__ tr_off, const uint32_t* __restrict__ tr_cls,
+                                                                 const double* __restrict__ n_c, const double* __restrict__ d,
+                                                                 const double* __restrict__ eff, double* __restrict__ alpha, double* __restrict__ w,
+                                                                 int check, uint32_t* __restrict__ moved) {
+  const uint64_t j = (uint64_t)blockIdx.x * (FFP_BLOCK / 64) + (threadIdx.x >> 6);
+  if (j >= m) return;                                       // (the whole wave)
+  const uint32_t lane = threadIdx.x & 63;
+  const double wj = w[j];
+  double x = 0.0;
+  for (uint64_t t = tr_off[j] + lane, end = tr_off[j + 1]; t < end; t += 64) {
+    const uint32_t c = tr_cls[t];
+    const double dc = d[c];
+    if (dc != 0.0) x += n_c[c] * wj / dc;
+  }
+  x = abd_wave_sum(x);
+  if (lane == 0) {
+    const double old = alpha[j];
+    alpha[j] = x;
+    w[j] = x / eff[j];
+    if (check && x > 1e-2 && fabs(x - old) > 1e-2 * x) *moved = 1u;
+  }
+}
+
+// The EM of `kallisto quant` (filter_kallisto.py:29) on classes given as host arrays: DESIGN.md 3.10 rule 4.
+extern "C" int shn_abundance_em(shn_ctx* ctx, const uint64_t* class_off, const uint32_t* members, const uint64_t* n_c, uint64_t n_classes,
+                                const double* eff, uint64_t m, double* alpha, uint32_t* rounds) {
+  const std::string fn("shn_abundance_em");
+  if (m == 0) return shn_fail(SHN_ERR_ARG, fn + ": no transcripts (m is 0)");
+  if (!ctx || !class_off || !eff || !alpha || !rounds || (n_classes && !n_c)) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
+  if (m >= 0xFFFFFFFFULL || n_classes >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many transcripts or classes");
+  if (class_off[0] != 0) return shn_fail(SHN_ERR_ARG, fn + ": class_off[0] is not 0");
+  for (uint64_t c = 0; c < n_classes; c++)
+    if (class_off[c + 1] < class_off[c]) return shn_fail(SHN_ERR_ARG, fn + ": class_off not monotone");
+  const uint64_t n_entries = class_off[n_classes];
+  if (n_entries >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many class members");
+  if (n_entries && !members) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
+  for (uint64_t e = 0; e < n_entries; e++)
+    if (members[e] >= m) return shn_fail(SHN_ERR_ARG, fn + ": a class names transcript " + std::to_string(members[e]) + " of " + std::to_string(m));
+  for (uint64_t j = 0; j < m; j++)
+    if (!(eff[j] > 0.0)) return shn_fail(SHN_ERR_ARG, fn + ": eff of transcript " + std::to_string(j) + " is not above 0");
+  std::vector<double> ncd(n_classes);
+  for (uint64_t c = 0; c < n_classes; c++) ncd[c] = (double)n_c[c];
+  SHN_ENTER(ctx);
+  shn_stage_begin(ctx);
+  hipStream_t s = ctx->stream;
+  ShnDevBufs bufs(s);
+  uint64_t *d_coff = nullptr, *d_key = nullptr, *d_key_tmp = nullptr, *d_troff = nullptr;
+  uint32_t *d_mem = nullptr, *d_val = nullptr, *d_val_tmp = nullptr, *d_cls = nullptr, *d_trcls = nullptr, *d_moved = nullptr;
+  double *d_nc = nullptr, *d_eff = nullptr, *d_alpha = nullptr, *d_w = nullptr, *d_d = nullptr;
+  HIP_TRY(bufs.get(&d_coff, (n_classes + 1) * 8));
+  HIP_TRY(bufs.get(&d_mem, (n_entries + 1) * 4));
+  HIP_TRY(bufs.get(&d_nc, (n_classes + 1) * 8));
+  HIP_TRY(bufs.get(&d_eff, m * 8));
+  HIP_TRY(bufs.get(&d_alpha, m * 8));
+  HIP_TRY(bufs.get(&d_w, m * 8));
+  HIP_TRY(bufs.get(&d_d, (n_classes + 1) * 8));
+  HIP_TRY(bufs.get(&d_key, (n_entries + 1) * 8));
+  HIP_TRY(bufs.get(&d_key_tmp, (n_entries + 1) * 8));
+  HIP_TRY(bufs.get(&d_val, (n_entries + 1) * 4));
+  HIP_TRY(bufs.get(&d_val_tmp, (n_entries + 1) * 4));
+  HIP_TRY(bufs.get(&d_cls, (n_entries + 1) * 4));
+  HIP_TRY(bufs.get(&d_trcls, (n_entries + 1) * 4));
+  HIP_TRY(bufs.get(&d_troff, (m + 1) * 8));
+  HIP_TRY(bufs.get(&d_moved, 4));
+  HIP_TRY(hipMemcpyAsync(d_coff, class_off, (n_classes + 1) * 8, hipMemcpyHostToDevice, s));
+  if (n_entries) HIP_TRY(hipMemcpyAsync(d_mem, members, n_entries * 4, hipMemcpyHostToDevice, s));
+  if (n_classes) HIP_TRY(hipMemcpyAsync(d_nc, ncd.data(), n_classes * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_eff, eff, m * 8, hipMemcpyHostToDevice, s));
+  int key_bits = 1;
+  while (key_bits < 32 && (m >> key_bits)) key_bits++;
+  {
+    TimerRegion treg(ctx, T_ABD_EM);
+    // bytes, transposition: an entry read (4 B + its class's offsets from the caches) and written as key, value, class (16 B), every sort
+    // pass reads and writes the pairs (24 B), the sorted entry's class gathered and written (12 B); 8 B a transcript offset; 24 B a
+    // transcript for alpha, w, eff
+    treg.bytes(n_entries * (32 + 24 * (uint64_t)((key_bits + 7) / 8)) + (m + 1) * 8 + m * 24);
+    if (n_entries) {
+      hipLaunchKernelGGL(abd_entries_kernel, dim3((uint32_t)cdiv(n_entries, 256)), dim3(256), 0, s, n_entries, n_classes, d_coff, d_mem, d_key, d_val, d_cls);
+      int rc = shn_sort_pairs(ctx, d_key, d_val, d_key_tmp, d_val_tmp, n_entries, 0, key_bits);
+      if (rc) return rc;
+    }
+    const uint64_t n_t = n_entries > m + 1 ? n_entries : m + 1;
+    hipLaunchKernelGGL(abd_transpose_kernel, dim3((uint32_t)cdiv(n_t, 256)), dim3(256), 0, s, n_entries, m, d_key, d_val, d_cls, d_troff, d_trcls);
+    hipLaunchKernelGGL(abd_em_init_kernel, dim3((uint32_t)cdiv(m, 256)), dim3(256), 0, s, m, d_eff, d_alpha, d_w);
+  }
+  const uint32_t waves = FFP_BLOCK / 64;
+  uint32_t round = 0;
+  for (;;) {                                                  // a block of 50 rounds, the last of them with the test; one read of the flag
+    HIP_TRY(hipMemsetAsync(d_moved, 0, 4, s));
+    {
+      TimerRegion treg(ctx, T_ABD_EM);
+      // bytes of a round: d pass -- two offsets a class (16 B), a member and its w (12 B an entry), d written (8 B a class); alpha pass
+      // -- two offsets, w, alpha, eff read, alpha and w written (56 B a transcript), class, n_c and d of an entry (20 B)
+      treg.bytes(50 * (n_classes * 24 + n_entries * 32 + m * 56));
+      for (int k = 0; k < 50; k++) {
+        if (n_classes)
+          hipLaunchKernelGGL(abd_em_d_kernel, dim3((uint32_t)cdiv(n_classes, waves)), dim3(FFP_BLOCK), 0, s, n_classes, d_coff, d_mem, d_w, d_d);
+        hipLaunchKernelGGL(abd_em_alpha_kernel, dim3((uint32_t)cdiv(m, waves)), dim3(FFP_BLOCK), 0, s, m, d_troff, d_trcls, d_nc, d_d, d_eff, d_alpha, d_w,
+                           k == 49 ? 1 : 0, d_moved);
+      }
+    }
+    round += 50;
+    uint32_t moved = 0;
+    HIP_TRY(hipMemcpyAsync(&moved, d_moved, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    if (!moved || round >= 10000) break;
+  }
+  HIP_TRY(hipMemcpyAsync(alpha, d_alpha, m * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipGetLastError());
+  for (uint64_t j = 0; j < m; j++)
+    if (alpha[j] < 1e-8) alpha[j] = 0.0;
+  *rounds = round;
+  return SHN_OK;
+}

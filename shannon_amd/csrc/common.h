@@ -57,7 +57,9 @@ enum {
   // records_expand_kernel (record_expand_dev.h) by its record type: the reads of resident sets as base codes (reads_collect.hip),
   T_READS_COLLECT,
   // --inDisk (reads_text.hip): the records of reads*.fasta, of k1mer.dict
-  T_READS_FASTA, T_K1MERS_DICT, T_N = 52
+  T_READS_FASTA, T_K1MERS_DICT,
+  // --kallisto_cutoff (abundance.hip): index of the final transcripts, compatibility lists + span histogram, classes, the EM's rounds
+  T_ABD_INDEX, T_ABD_MAP, T_ABD_CLASSES, T_ABD_EM, T_N = 56
 };
 
 // grow-only device workspace slot (process-wide ones: g_shn_ws below; per-context ones: shn_ctx::cws)

@@ -28,7 +28,8 @@ static const char* kTimerNames[T_N] = {
   // a rank block apart from the re-run rounds (ext_walk_kernel<true> / <false>), the begin pass, the second table size of the buckets
   "extend.walk_fresh", "extend.begin", "count.sk_buckets2",
   "contig.sort", "contig.hits", "contig.cover", "contig.compact", "graph.kp_search", "graph.kp_classify", "graph.seed_scan", "graph.dd_insert", "lp.trials",
-  "extend.audit", "filter_fp.index", "filter_fp.map", "filter_fp.count", "filter_fp.merge", "reads.collect", "reads.fasta", "k1mers.dict"};
+  "extend.audit", "filter_fp.index", "filter_fp.map", "filter_fp.count", "filter_fp.merge", "reads.collect", "reads.fasta", "k1mers.dict",
+  "abundance.index", "abundance.map", "abundance.classes", "abundance.em"};
 extern "C" const char* shn_timer_name(int slot) {
   if (slot < 0 || slot >= T_N || !kTimerNames[slot]) return "";
   return kTimerNames[slot];

@@ -22,109 +22,7 @@
 // The thread-per-route shape trades lane divergence (mates differ in how many candidates their seeds name) for having no
 // intermediate candidate lists at all; DESIGN.md gives the measured time next to the byte models below.
 #include "common.h"
-
-#define FFP_SEED SHN_FILTER_FP_SEED
-#define FFP_NONE 0xFFFFFFFFu
-#define FFP_BLOCK 256
-#define FFP_YSEEDS 9
-
-struct shn_routes;
-int shn_routes_device_arrays(const shn_routes* r, const uint32_t** pid, const uint32_t** ridx, uint64_t* n);   // route.hip
-
-// a read set as the mapping sees it: the set as packed by shn_reads_create / shn_reads_ingest and its reverse complement in the
-// same geometry (every read in its own words, so RC(read i) lies where read i lies)
-struct FfpSet {
-  const uint64_t *words, *mask, *words_rc, *mask_rc, *woff;
-  const uint32_t* len;
-  const uint8_t* bad;          // NULL: no read of the set holds a non-ACGT base
-  uint32_t fixed_len, wpr;
-};
-struct FfpRead { const uint64_t* w; const uint64_t* m; uint32_t L; bool bad; };
-
-struct FfpIndex {
-  const uint64_t* keys; const uint32_t* vals; uint64_t n_rec;
-  const uint64_t* tw;          // the text, 32 bases a word, first base in the top bits; two zero words behind the end
-  const uint64_t* t_off; uint64_t n_tr;
-};
-
-__device__ __forceinline__ FfpRead ffp_read(const FfpSet& S, uint64_t i, bool rc) {
-  FfpRead r;
-  const uint64_t wb = S.woff ? S.woff[i] : i * (uint64_t)S.wpr;
-  r.L = S.len ? S.len[i] : S.fixed_len;
-  r.w = (rc ? S.words_rc : S.words) + wb;
-  r.bad = S.bad != nullptr && S.bad[i] != 0;
-  r.m = r.bad ? (rc ? S.mask_rc : S.mask) + wb / 2 : nullptr;
-  return r;
-}
-
-// 32 bases of the text from base g on (the words behind the text's end are zero)
-__device__ __forceinline__ uint64_t ffp_text32(const uint64_t* __restrict__ tw, uint64_t g) {
-  const uint64_t wi = g >> 5;
-  const uint32_t sh = (uint32_t)(g & 31) * 2;
-  uint64_t v = tw[wi] << sh;
-  if (sh) v |= tw[wi + 1] >> (64 - sh);
-  return v;
-}
-__device__ __forceinline__ uint64_t ffp_text_seed(const uint64_t* __restrict__ tw, uint64_t g) {
-  return ffp_text32(tw, g) >> (64 - 2 * FFP_SEED);
-}
-
-// bit i of a 32-bit word -> bit 2 i (the N mask of 32 bases onto the low bits of their 2-bit fields)
-__device__ __forceinline__ uint64_t ffp_spread(uint32_t n) {
-  uint64_t x = n;
-  x = (x | (x << 16)) & 0x0000FFFF0000FFFFULL;
-  x = (x | (x << 8)) & 0x00FF00FF00FF00FFULL;
-  x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0FULL;
-  x = (x | (x << 2)) & 0x3333333333333333ULL;
-  x = (x | (x << 1)) & 0x5555555555555555ULL;
-  return x;
-}
-
-// Hamming distance between the read and the text at u (a non-ACGT base of the read is a mismatch); gives up above thr
-__device__ __forceinline__ uint32_t ffp_hamming(const FfpRead& x, const uint64_t* __restrict__ tw, uint64_t u, uint32_t thr) {
-  uint32_t mm = 0;
-  const uint32_t nw = (x.L + 31) >> 5;
-  for (uint32_t k = 0; k < nw; k++) {
-    uint64_t d = x.w[k] ^ ffp_text32(tw, u + 32ull * k);
-    d = (d | (d >> 1)) & 0x5555555555555555ULL;
-    if (x.bad) {
-      const uint64_t m = x.m[k >> 1];
-      d |= ffp_spread((k & 1) ? (uint32_t)m : (uint32_t)(m >> 32));
-    }
-    const uint32_t rem = x.L - 32 * k;
-    if (rem < 32) d &= ~0ULL << (64 - 2 * rem);
-    mm += (uint32_t)__popcll(d);
-    if (mm > thr) return mm;
-  }
-  return mm;
-}
-
-__device__ __forceinline__ bool ffp_seed_of(const FfpRead& x, uint32_t s, uint64_t* seed) {
-  if (x.bad && shn_extract_mask(x.m, s * FFP_SEED, FFP_SEED)) return false;
-  *seed = shn_extract(x.w, s * FFP_SEED, FFP_SEED);
-  return true;
-}
-
-// does a seed before s match the text exactly when the read starts at u?  (then that seed has named this start already)
-__device__ __forceinline__ bool ffp_named_before(const FfpRead& x, const uint64_t* __restrict__ tw, uint64_t u, uint32_t s) {
-  for (uint32_t e = 0; e < s; e++) {
-    uint64_t seed;
-    if (ffp_seed_of(x, e, &seed) && ffp_text_seed(tw, u + (uint64_t)e * FFP_SEED) == seed) return true;
-  }
-  return false;
-}
-
-__device__ __forceinline__ uint64_t ffp_lower(const FfpIndex& I, uint64_t key) {
-  uint64_t lo = 0, hi = I.n_rec;
-  while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (I.keys[mid] < key) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-// transcript that holds base g of the text (empty transcripts hold none)
-__device__ __forceinline__ uint64_t ffp_transcript_of(const FfpIndex& I, uint64_t g) {
-  uint64_t lo = 0, hi = I.n_tr;               // largest j with t_off[j] <= g
-  while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (I.t_off[mid] <= g) lo = mid; else hi = mid; }
-  return lo;
-}
+#include "filter_fp_dev.h"
 
 __device__ __forceinline__ void ffp_mark(unsigned long long* __restrict__ cov, uint64_t g0, uint32_t len) {
   const uint64_t g1 = g0 + len;
@@ -136,55 +34,16 @@ __device__ __forceinline__ void ffp_mark(unsigned long long* __restrict__ cov, u
   }
 }
 
-// Every concordant placement of the oriented pair (x, y) in the partition whose key prefix is pkey: x at u, y at v on the same
-// transcript, u <= v, u + |x| <= v + |y|, v + |y| - u <= max_span, each mate within its mismatch bound.  MARK == false: *best
-// becomes the smallest cost seen; MARK == true: the placements of cost *best are marked.
+// MARK == false: *best becomes the smallest cost of a concordant placement of the oriented pair (x, y); MARK == true: the placements
+// of cost *best are marked (the enumeration itself: ffp_each_placement, filter_fp_dev.h)
 template <bool MARK>
 __device__ void ffp_pairs(const FfpIndex& I, uint64_t pkey, const FfpRead& x, const FfpRead& y, uint32_t max_span, uint32_t* best,
                           unsigned long long* __restrict__ cov) {
-  if (x.L < FFP_SEED || y.L < FFP_SEED) return;
-  const uint32_t thrx = x.L / 30, thry = y.L / 30;
-  uint32_t ylo[FFP_YSEEDS];                              // first index record of the second mate's seeds (reads up to 269 bases: all of them)
-  bool have_y = false;
-  for (uint32_t s = 0; s <= thrx; s++) {
-    uint64_t seed;
-    if (!ffp_seed_of(x, s, &seed)) continue;
-    const uint64_t key = pkey | seed;
-    for (uint64_t r = ffp_lower(I, key); r < I.n_rec && I.keys[r] == key; r++) {
-      const uint64_t g = I.vals[r];
-      const uint64_t j = ffp_transcript_of(I, g);
-      const uint64_t a = I.t_off[j], b = I.t_off[j + 1];
-      if (g < a + (uint64_t)s * FFP_SEED) continue;
-      const uint64_t u = g - (uint64_t)s * FFP_SEED;
-      if (u + x.L > b || ffp_named_before(x, I.tw, u, s)) continue;
-      const uint32_t cx = ffp_hamming(x, I.tw, u, thrx);
-      if (cx > thrx || (MARK ? cx > *best : cx >= *best)) continue;
-      if (!have_y) {                                     // (the first verified first mate: where the second mate's seeds start in the index)
-        for (uint32_t t = 0; t <= thry && t < FFP_YSEEDS; t++) {
-          uint64_t seed_y;
-          ylo[t] = ffp_seed_of(y, t, &seed_y) ? (uint32_t)ffp_lower(I, pkey | seed_y) : FFP_NONE;
-        }
-        have_y = true;
-      }
-      for (uint32_t t = 0; t <= thry; t++) {
-        uint64_t seed_y;
-        if (!ffp_seed_of(y, t, &seed_y)) continue;
-        const uint64_t key_y = pkey | seed_y;
-        for (uint64_t q = t < FFP_YSEEDS ? ylo[t] : ffp_lower(I, key_y); q < I.n_rec && I.keys[q] == key_y; q++) {
-          const uint64_t gy = I.vals[q];
-          if (gy < a + (uint64_t)t * FFP_SEED || gy >= b) continue;                 // (another transcript, or y would start before this one)
-          const uint64_t v = gy - (uint64_t)t * FFP_SEED;
-          if (v + y.L > b || v < u || u + x.L > v + y.L || v + y.L - u > max_span) continue;
-          if (ffp_named_before(y, I.tw, v, t)) continue;
-          const uint32_t cy = ffp_hamming(y, I.tw, v, thry);
-          if (cy > thry) continue;
-          const uint32_t c = cx + cy;
-          if (!MARK) { if (c < *best) *best = c; }
-          else if (c == *best) { ffp_mark(cov, u, x.L); ffp_mark(cov, v, y.L); }
-        }
-      }
-    }
-  }
+  if (!MARK) { ffp_min_cost(I, pkey, x, y, max_span, best); return; }
+  const uint32_t lx = x.L, ly = y.L;
+  ffp_each_placement<true>(I, pkey, x, y, max_span, best, [&](uint32_t c, uint64_t, uint64_t u, uint64_t v) {
+    if (c == *best) { ffp_mark(cov, u, lx); ffp_mark(cov, v, ly); }
+  });
 }
 
 // One route a thread: fragment i = the route's read index (strand-specific) or index mod n_pairs (strand-doubled numbering);
@@ -337,7 +196,7 @@ __global__ __launch_bounds__(FFP_BLOCK) void ffp_merge_count_kernel(const unsign
   if (lane == 0) hits[j] = n;
 }
 
-static int ffp_set(shn_ctx* ctx, ShnDevBufs& bufs, const shn_reads* r, bool want_rc, FfpSet* out, uint64_t* rc_bytes) {
+int ffp_set(shn_ctx* ctx, ShnDevBufs& bufs, const shn_reads* r, bool want_rc, FfpSet* out, uint64_t* rc_bytes) {
   hipStream_t s = ctx->stream;
   const bool use_mask = r->n_invalid != 0 && r->d_mask && r->d_bad;
   FfpSet S;
@@ -359,6 +218,54 @@ static int ffp_set(shn_ctx* ctx, ShnDevBufs& bufs, const shn_reads* r, bool want
     *rc_bytes += r->n_words * 16 + (use_mask ? r->n_words * 8 : 0);          // the set read once, its reverse complement written once
   }
   *out = S;
+  return SHN_OK;
+}
+
+// The transcripts' text packed and the sorted index of its 15-mers (the header says what the arguments are).
+int ffp_index_build(const std::string& fn, shn_ctx* ctx, ShnDevBufs& bufs, int slot, const uint8_t* text, const uint64_t* t_off, const uint32_t* t_part,
+                    uint64_t n_tr, uint32_t n_parts, const std::vector<uint64_t>& rec_off, FfpIndex* out, uint64_t* n_tw_out) {
+  hipStream_t s = ctx->stream;
+  const uint64_t total = t_off[n_tr], n_rec = rec_off[n_tr];
+  const uint64_t n_tw = cdiv(total, 32);
+  uint8_t* d_text = nullptr;
+  uint64_t *d_tw = nullptr, *d_toff = nullptr, *d_roff = nullptr, *d_keys = nullptr, *d_keys_tmp = nullptr;
+  uint32_t *d_tpart = nullptr, *d_vals = nullptr, *d_vals_tmp = nullptr, *d_flag = nullptr;
+  HIP_TRY(bufs.get(&d_text, total + 1));
+  HIP_TRY(bufs.get(&d_tw, (n_tw + 2) * 8));
+  HIP_TRY(bufs.get(&d_toff, (n_tr + 1) * 8));
+  HIP_TRY(bufs.get(&d_roff, (n_tr + 1) * 8));
+  HIP_TRY(bufs.get(&d_tpart, n_tr * 4));
+  HIP_TRY(bufs.get(&d_flag, 4));
+  HIP_TRY(bufs.get(&d_keys, (n_rec + 1) * 8));
+  HIP_TRY(bufs.get(&d_keys_tmp, (n_rec + 1) * 8));
+  HIP_TRY(bufs.get(&d_vals, (n_rec + 1) * 4));
+  HIP_TRY(bufs.get(&d_vals_tmp, (n_rec + 1) * 4));
+  HIP_TRY(hipMemcpyAsync(d_text, text, total, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_toff, t_off, (n_tr + 1) * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_roff, rec_off.data(), (n_tr + 1) * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_tpart, t_part, n_tr * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(d_flag, 0, 4, s));
+  HIP_TRY(hipMemsetAsync(d_tw + n_tw, 0, 16, s));
+  {
+    int key_bits = 2 * FFP_SEED;
+    while (key_bits < 62 && ((uint64_t)n_parts >> (key_bits - 2 * FFP_SEED))) key_bits++;
+    const uint64_t passes = (uint64_t)(key_bits + 7) / 8;
+    TimerRegion treg(ctx, slot);
+    // bytes: the text read and written packed (1.25 B a base), a record written (12 B), every sort pass reads and writes the records
+    treg.bytes(total + total / 4 + n_rec * 12 + passes * n_rec * 24);
+    if (n_tw) hipLaunchKernelGGL(ffp_pack_text_kernel, dim3((uint32_t)cdiv(n_tw, 256)), dim3(256), 0, s, d_text, total, d_tw, d_flag);
+    if (n_rec) {
+      hipLaunchKernelGGL(ffp_records_kernel, dim3((uint32_t)cdiv(n_rec, 256)), dim3(256), 0, s, d_tw, d_toff, d_roff, d_tpart, n_tr, n_rec, d_keys, d_vals);
+      int rc = shn_sort_pairs(ctx, d_keys, d_vals, d_keys_tmp, d_vals_tmp, n_rec, 0, key_bits);
+      if (rc) return rc;
+    }
+  }
+  uint32_t flag = 0;
+  HIP_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (flag) return shn_fail(SHN_ERR_ARG, fn + ": a transcript holds a base outside ACGT");
+  out->keys = d_keys; out->vals = d_vals; out->n_rec = n_rec; out->tw = d_tw; out->t_off = d_toff; out->n_tr = n_tr;
+  *n_tw_out = n_tw;
   return SHN_OK;
 }
 
@@ -411,45 +318,15 @@ static int ffp_run(const char* fn_, shn_ctx* ctx, const uint8_t* text, const uin
   if (n_tr == 0) { HIP_TRY(hipStreamSynchronize(s)); return SHN_OK; }
 
   // ---- index
-  const uint64_t n_tw = cdiv(total, 32);
-  uint8_t* d_text = nullptr;
-  uint64_t *d_tw = nullptr, *d_toff = nullptr, *d_roff = nullptr, *d_keys = nullptr, *d_keys_tmp = nullptr;
-  uint32_t *d_tpart = nullptr, *d_vals = nullptr, *d_vals_tmp = nullptr, *d_flag = nullptr, *d_hits = nullptr;
-  unsigned long long *d_cov = nullptr, *d_placed = nullptr;
-  HIP_TRY(bufs.get(&d_text, total + 1));
-  HIP_TRY(bufs.get(&d_tw, (n_tw + 2) * 8));
-  HIP_TRY(bufs.get(&d_toff, (n_tr + 1) * 8));
-  HIP_TRY(bufs.get(&d_roff, (n_tr + 1) * 8));
-  HIP_TRY(bufs.get(&d_tpart, n_tr * 4));
-  HIP_TRY(bufs.get(&d_flag, 4));
-  HIP_TRY(bufs.get(&d_keys, (n_rec + 1) * 8));
-  HIP_TRY(bufs.get(&d_keys_tmp, (n_rec + 1) * 8));
-  HIP_TRY(bufs.get(&d_vals, (n_rec + 1) * 4));
-  HIP_TRY(bufs.get(&d_vals_tmp, (n_rec + 1) * 4));
-  HIP_TRY(hipMemcpyAsync(d_text, text, total, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_toff, t_off, (n_tr + 1) * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_roff, rec_off.data(), (n_tr + 1) * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_tpart, t_part, n_tr * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemsetAsync(d_flag, 0, 4, s));
-  HIP_TRY(hipMemsetAsync(d_tw + n_tw, 0, 16, s));
+  FfpIndex I;
+  uint64_t n_tw = 0;
   {
-    int key_bits = 2 * FFP_SEED;
-    while (key_bits < 62 && ((uint64_t)n_parts >> (key_bits - 2 * FFP_SEED))) key_bits++;
-    const uint64_t passes = (uint64_t)(key_bits + 7) / 8;
-    TimerRegion treg(ctx, T_FFP_INDEX);
-    // bytes: the text read and written packed (1.25 B a base), a record written (12 B), every sort pass reads and writes the records
-    treg.bytes(total + total / 4 + n_rec * 12 + passes * n_rec * 24);
-    if (n_tw) hipLaunchKernelGGL(ffp_pack_text_kernel, dim3((uint32_t)cdiv(n_tw, 256)), dim3(256), 0, s, d_text, total, d_tw, d_flag);
-    if (n_rec) {
-      hipLaunchKernelGGL(ffp_records_kernel, dim3((uint32_t)cdiv(n_rec, 256)), dim3(256), 0, s, d_tw, d_toff, d_roff, d_tpart, n_tr, n_rec, d_keys, d_vals);
-      int rc = shn_sort_pairs(ctx, d_keys, d_vals, d_keys_tmp, d_vals_tmp, n_rec, 0, key_bits);
-      if (rc) return rc;
-    }
+    int rc = ffp_index_build(fn, ctx, bufs, T_FFP_INDEX, text, t_off, t_part, n_tr, n_parts, rec_off, &I, &n_tw);
+    if (rc) return rc;
   }
-  uint32_t flag = 0;
-  HIP_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (flag) return shn_fail(SHN_ERR_ARG, fn + ": a transcript holds a base outside ACGT");
+  const uint64_t* d_toff = I.t_off;
+  uint32_t* d_hits = nullptr;
+  unsigned long long *d_cov = nullptr, *d_placed = nullptr;
 
   // ---- map + mark
   const uint64_t n_cov = cdiv(total, 64) + 1;
@@ -465,8 +342,6 @@ static int ffp_run(const char* fn_, shn_ctx* ctx, const uint8_t* text, const uin
     int rc = ffp_set(ctx, bufs, r1, !strand_specific, &A, &rc_bytes);
     if (!rc) rc = ffp_set(ctx, bufs, r2, true, &B, &rc_bytes);
     if (rc) return rc;
-    FfpIndex I;
-    I.keys = d_keys; I.vals = d_vals; I.n_rec = n_rec; I.tw = d_tw; I.t_off = d_toff; I.n_tr = n_tr;
     // bytes: a route (8 B) and both mates of its fragment in each orientation used (2 bits a base); the index, the text and the
     // bitmap are re-read from the caches and priced once; what the reverse complements cost is added above
     const uint64_t per_pair = n_pairs ? (r1->n_words + r2->n_words) * 8 / n_pairs : 0;

@@ -71,11 +71,11 @@ def n_kmer_nodes(rows, K):
 
 def assemble(ctx, reads1, reads2=None, K=25, partition_size=500, min_weight=3, min_length=75, overload=2, penalty=5,
              sample="shannon", seed=0, double_stranded=True, part_vectors=None, timings=None, hits_factory=None,
-             native_graph=True, kmer_hard_cutoff=1, filter_fp=False, in_disk_dir=None):
+             native_graph=True, kmer_hard_cutoff=1, filter_fp=False, in_disk_dir=None, kallisto_cutoff=None):
     """reads1/reads2: lists of strings or uint8 code matrices (reads2 None = single-end).
     min_weight = the reference's hyp_min_weight (--kmer_soft_cutoff, shannon.py:243-247, 457); kmer_hard_cutoff = its
     jellyfish_kmer_cutoff (--kmer_hard_cutoff, `jellyfish dump -L`, shannon.py:237-241, 441).  filter_fp: --filter_FP, in_disk_dir:
-    --inDisk, see assemble_resident.
+    --inDisk, kallisto_cutoff: --kallisto_cutoff, see assemble_resident.
     Returns Result with .partitions {name: dict}, .all_reconstructed (lines), .final {name: seq}."""
     T = timings if timings is not None else {}
     paired = reads2 is not None
@@ -91,13 +91,13 @@ def assemble(ctx, reads1, reads2=None, K=25, partition_size=500, min_weight=3, m
     tick("upload+pack", t0)
     return assemble_resident(ctx, d1, d2, store, K, partition_size, min_weight, min_length, overload, penalty, sample, seed,
                              double_stranded, part_vectors, T, hits_factory, native_graph, kmer_hard_cutoff=kmer_hard_cutoff, filter_fp=filter_fp,
-                             in_disk_dir=in_disk_dir)
+                             in_disk_dir=in_disk_dir, kallisto_cutoff=kallisto_cutoff)
 
 
 def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3, min_length=75, overload=2, penalty=5,
                       sample="shannon", seed=0, double_stranded=True, part_vectors=None, timings=None, hits_factory=None,
                       native_graph=True, graph_threads=None, keep_partitioning=False, defer_back=False, kmer_hard_cutoff=1, filter_fp=False,
-                      in_disk_dir=None):
+                      in_disk_dir=None, kallisto_cutoff=None):
     """Same as assemble() with the reads already packed in HBM (d1/d2: device.Reads).  graph_threads: partitions whose
     graph stage may run concurrently on host threads.  keep_partitioning: leave the partition stage's tables (partition ->
     contigs, routed read indices) on the result as `.partitioning` (tests/test_fullsize_gpu.py reads them).  defer_back: run count,
@@ -110,7 +110,12 @@ def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3
     in_disk_dir: --inDisk (shannon.py:39-40) -- right behind the routing every partition `name` gets <in_disk_dir>/<sample>_<name>algo_input/
     with reads.fasta (pairs: reads_1.fasta + reads_2.fasta; all routed reads) and k1mer.dict, formatted on the device from the routes
     and the contig text (kfc.write_in_disk); R.in_disk = {name: {file: bytes}}, the time under timings["inDisk"].  None: nothing
-    of this runs."""
+    of this runs.
+    kallisto_cutoff: --kallisto_cutoff C (shannon.py:309-318, 609-614, filter_kallisto.py) -- behind the merge every final transcript
+    is quantified against ALL read pairs (abundance.apply: DESIGN.md 3.10) and stays only if est_counts / eff_length * L >= C;
+    R.final is then the filtered set (a dict), R.final_before_kallisto what the merge gave, R.abundance the table (with the text of
+    abundance.tsv under "tsv" and of rec_before_kallisto.fasta under "before"), the time under timings["abundance"].  Paired-end
+    input only (single-end: R.kallisto_note says so, nothing is filtered).  None: nothing of this runs; works together with filter_fp."""
     # double_stranded=False: -s / --ss / --strand_specific.  shannon.py:394-424 then leaves single-end reads as they are and
     # reverse-complements the second mates, without doubling; from :427 on double_stranded is False in BOTH modes, so only the read
     # set differs: forward counting (d2: its reverse complements), routes of plain read indices, pairs (R1[i], RC(R2[i])) in the
@@ -419,6 +424,21 @@ def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3
             tick("filter_FP", t0)
             return kept
 
+        def apply_kallisto(kctx):
+            """--kallisto_cutoff on R.final (the merge's result)"""
+            if kallisto_cutoff is None:
+                return
+            if not paired or d1 is None or d2 is None:
+                R.kallisto_note = ("--kallisto_cutoff: single-end input is not built (the reference runs kallisto --single -l 200 -s 20, "
+                                   "filter_kallisto.py:25); nothing filtered")
+                return
+            t0 = time.time()
+            from . import abundance
+            kept, table, tsv, before = abundance.apply(kctx, R.final, d1, d2, ss, kallisto_cutoff)
+            table["tsv"], table["before"] = tsv, before
+            R.final_before_kallisto, R.final, R.abundance = R.final, kept, table
+            tick("abundance", t0)
+
         t_graph = time.time()
         results, futs = [], {}
         try:
@@ -502,6 +522,7 @@ def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3
             else:
                 R.final = post.finalize(R.all_reconstructed, double_stranded)
             tick("post", t0)
+            apply_kallisto(ctx_b)
             R.timings = T
             return R
         lines = (single_text if isinstance(single_text, str) else bytes(single_text).decode()).splitlines(True)
@@ -538,6 +559,7 @@ def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3
         R.all_reconstructed = lines
         R.final = post.finalize(lines, double_stranded)
         tick("post", t0)
+        apply_kallisto(ctx_b)
         R.timings = T
         return R
 

@@ -181,6 +181,23 @@ int shn_debug_alloc(shn_ctx* ctx, uint64_t bytes, void** out);
 void shn_debug_free(shn_ctx* ctx, void* p);
 int shn_debug_fill(shn_ctx* ctx, void* p, uint64_t n_words, uint32_t value, uint32_t spin);
 int shn_debug_read(shn_ctx* ctx, const void* p, uint64_t n_words, uint32_t* host_out);
+/* test hooks of the shared device primitives (csrc/debug_hooks.hip, tests/test_primitives_gpu.py): host arrays in, the primitive called
+ * unchanged on the context's stream, host arrays out.  Not part of the path.
+ *   shn_debug_sort_pairs / shn_debug_sort_keys  the stable radix sort of (key, value) pairs / of 64-bit words by the key bits
+ *                         [bit_lo, bit_hi), 0 <= bit_lo, bit_hi <= 64 (csrc/sort.hip; the contract is stated in csrc/common.h)
+ *   shn_debug_scan_u32    exclusive sums of n 32-bit numbers as n + 1 64-bit ones, out[n] = the total; total != NULL: the form that
+ *                         also hands the total to the host (and synchronises), NULL: the device-only form
+ *   shn_debug_table_find  idx_out[i] = index of keys[i] in the table's key array (the order of shn_table_download) or -1, one thread
+ *                         per query; variant 0: shn_table_find (bisection), 1: shn_table_find_k (interpolated first guess, gallop;
+ *                         key width 2 * k of the table), 2: shn_tab_find (by the table's layout).  Variants 0 and 1 know the hashed
+ *                         buckets only: SHN_ERR_ARG for a table of the super-k-mer layout
+ *   shn_debug_table_view  hash bits and layout (0: buckets by hash, 1: by minimizer) of a table, its 2^bits + 1 bucket offsets      */
+int shn_debug_sort_pairs(shn_ctx* ctx, const uint64_t* keys, const uint32_t* vals, uint64_t n, int bit_lo, int bit_hi, uint64_t* keys_out,
+                         uint32_t* vals_out);
+int shn_debug_sort_keys(shn_ctx* ctx, const uint64_t* keys, uint64_t n, int bit_lo, int bit_hi, uint64_t* keys_out);
+int shn_debug_scan_u32(shn_ctx* ctx, const uint32_t* in, uint64_t n, uint64_t* out /* n + 1 */, uint64_t* total /* may be NULL */);
+int shn_debug_table_find(shn_ctx* ctx, const shn_table* table, const uint64_t* keys, uint64_t n, int variant, int64_t* idx_out);
+int shn_debug_table_view(shn_ctx* ctx, const shn_table* table, int* bits, int* layout, uint64_t* bucket_off /* may be NULL */);
 /* per walk (host arrays of shn_ext_n_walks entries): right/left extension lengths (n_right ==
  * 0xFFFFFFFF marks a void walk) and the weight sum including the seed (tot_wt, :351)          */
 int shn_ext_stats(shn_ctx* ctx, const shn_ext* e, uint32_t* n_right, uint32_t* n_left, uint64_t* tot_weight);

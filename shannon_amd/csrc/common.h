@@ -382,7 +382,10 @@ extern "C" int shn_host_cpus(void);
 void shn_lp_census_add(shn_ctx* c, const uint64_t* v8);   // core.hip: LP census of a context or, for a fork, of its parent (under the forks' lock)
 shn_ctx* shn_thread_ctx(shn_ctx* parent);      // core.hip: the calling host thread's own fork (stream) of a context
 int shn_device_scan_u32(shn_ctx* ctx, const uint32_t* d_in, uint64_t n, uint64_t* d_out /* n+1 */, uint64_t* total_host);
-// stable LSD radix sort of (u64 key, u32 value) pairs on bits [bit_lo, bit_hi); result lands in keys/vals
+// Stable LSD radix sort of (u64 key, u32 value) pairs by the bits [bit_lo, bit_hi) of the key and by nothing else: the order is that
+// of (key >> bit_lo) & ((1 << (bit_hi - bit_lo)) - 1) for ANY width (the last pass of a width that is no multiple of 8 takes the
+// bits that are left), pairs equal there keep their input order, and the bits outside the range order nothing -- they travel with
+// the key untouched.  bit_hi <= bit_lo: nothing moves.  0 <= bit_lo, bit_hi <= 64.  The result lands in keys / vals.
 int shn_sort_pairs(shn_ctx* ctx, uint64_t* keys, uint32_t* vals, uint64_t* keys_tmp, uint32_t* vals_tmp, uint64_t n,
                    int bit_lo, int bit_hi);
 

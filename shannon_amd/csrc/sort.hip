@@ -6,13 +6,15 @@
 #define SBLK 256
 #define STILE 4096
 
-__global__ __launch_bounds__(SBLK) void sort_hist_kernel(const uint64_t* __restrict__ keys, uint64_t n, int shift,
+// dmask: the bits of the pass's digit that lie inside the sorted range -- 255, or fewer ones in the last pass of a range whose
+// width is no multiple of 8 (the bits from bit_hi up must not order anything)
+__global__ __launch_bounds__(SBLK) void sort_hist_kernel(const uint64_t* __restrict__ keys, uint64_t n, int shift, uint32_t dmask,
                                                          uint32_t nblocks, uint32_t* __restrict__ gh) {
   __shared__ uint32_t lh[256];
   lh[threadIdx.x] = 0;
   __syncthreads();
   uint64_t t0 = (uint64_t)blockIdx.x * STILE, t1 = min(t0 + STILE, n);
-  for (uint64_t i = t0 + threadIdx.x; i < t1; i += SBLK) atomicAdd(&lh[(keys[i] >> shift) & 255], 1u);
+  for (uint64_t i = t0 + threadIdx.x; i < t1; i += SBLK) atomicAdd(&lh[(uint32_t)(keys[i] >> shift) & dmask], 1u);
   __syncthreads();
   gh[(uint64_t)threadIdx.x * nblocks + blockIdx.x] = lh[threadIdx.x];
 }
@@ -28,7 +30,7 @@ __global__ __launch_bounds__(SBLK) void sort_hist_kernel(const uint64_t* __restr
 // VALS = false: the words alone (a value packed under the key's bits travels inside the word: shn_sort_keys)
 template <bool VALS>
 __global__ __launch_bounds__(SBLK) void sort_scatter_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
-                                                            uint64_t n, int shift, uint32_t nblocks,
+                                                            uint64_t n, int shift, uint32_t dmask, uint32_t nblocks,
                                                             const uint64_t* __restrict__ goff, uint64_t* __restrict__ ok,
                                                             uint32_t* __restrict__ ov) {
   __shared__ uint32_t cnt[SBLK / 64][256];
@@ -50,7 +52,7 @@ __global__ __launch_bounds__(SBLK) void sort_scatter_kernel(const uint64_t* __re
     const bool have = i < n;
     k[row] = have ? keys[i] : 0;
     v[row] = (VALS && have) ? vals[i] : 0;
-    const uint32_t d = (uint32_t)((k[row] >> shift) & 255);
+    const uint32_t d = (uint32_t)(k[row] >> shift) & dmask;
     unsigned long long same = __ballot(have);
 #pragma unroll
     for (int bit = 0; bit < 8; bit++) {
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(SBLK) void sort_scatter_kernel(const uint64_t* __re
   for (int row = 0; row < ROWS; row++) {
     const uint64_t i = t0 + (uint64_t)row * 64 + lane;
     if (i >= n) continue;
-    const uint32_t d = (uint32_t)((k[row] >> shift) & 255);
+    const uint32_t d = (uint32_t)(k[row] >> shift) & dmask;
     const uint32_t lp = dstart[d] + base[wv][d] + rank[row];
     sk[lp] = k[row];
     if (VALS) sv[lp] = v[row];
@@ -95,12 +97,14 @@ __global__ __launch_bounds__(SBLK) void sort_scatter_kernel(const uint64_t* __re
   const uint32_t n_tile = (uint32_t)(tile0 + STILE <= n ? STILE : (n > tile0 ? n - tile0 : 0));
   for (uint32_t i = threadIdx.x; i < n_tile; i += SBLK) {
     const uint64_t key = sk[i];
-    const uint32_t d = (uint32_t)((key >> shift) & 255);
+    const uint32_t d = (uint32_t)(key >> shift) & dmask;
     const uint64_t p = goff[(uint64_t)d * nblocks + blockIdx.x] + (i - dstart[d]);
     ok[p] = key;
     if (VALS) ov[p] = sv[i];
   }
 }
+
+static inline uint32_t digit_mask(int shift, int bit_hi) { return bit_hi - shift >= 8 ? 255u : (1u << (bit_hi - shift)) - 1u; }
 
 int shn_sort_pairs(shn_ctx* ctx, uint64_t* keys, uint32_t* vals, uint64_t* keys_tmp, uint32_t* vals_tmp, uint64_t n,
                    int bit_lo, int bit_hi) {
@@ -117,9 +121,10 @@ int shn_sort_pairs(shn_ctx* ctx, uint64_t* keys, uint32_t* vals, uint64_t* keys_
   uint32_t *vi = vals, *vo = vals_tmp;
   int passes = 0;
   for (int shift = bit_lo; shift < bit_hi; shift += 8) {
-    hipLaunchKernelGGL(sort_hist_kernel, dim3(nblocks), dim3(SBLK), 0, s, ki, n, shift, nblocks, gh);
+    const uint32_t dmask = digit_mask(shift, bit_hi);
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(nblocks), dim3(SBLK), 0, s, ki, n, shift, dmask, nblocks, gh);
     if ((rc = shn_device_scan_u32(ctx, gh, (uint64_t)256 * nblocks, goff, nullptr))) return rc;
-    hipLaunchKernelGGL(sort_scatter_kernel<true>, dim3(nblocks), dim3(SBLK), 0, s, ki, vi, n, shift, nblocks, goff, ko, vo);
+    hipLaunchKernelGGL(sort_scatter_kernel<true>, dim3(nblocks), dim3(SBLK), 0, s, ki, vi, n, shift, dmask, nblocks, goff, ko, vo);
     std::swap(ki, ko);
     std::swap(vi, vo);
     passes++;
@@ -147,9 +152,10 @@ int shn_sort_keys(shn_ctx* ctx, uint64_t* keys, uint64_t* keys_tmp, uint64_t n, 
   uint32_t* gh = (uint32_t*)(goff + (size_t)256 * nblocks + 2);
   uint64_t *ki = keys, *ko = keys_tmp;
   for (int shift = bit_lo; shift < bit_hi; shift += 8) {
-    hipLaunchKernelGGL(sort_hist_kernel, dim3(nblocks), dim3(SBLK), 0, s, ki, n, shift, nblocks, gh);
+    const uint32_t dmask = digit_mask(shift, bit_hi);
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(nblocks), dim3(SBLK), 0, s, ki, n, shift, dmask, nblocks, gh);
     if ((rc = shn_device_scan_u32(ctx, gh, (uint64_t)256 * nblocks, goff, nullptr))) return rc;
-    hipLaunchKernelGGL(sort_scatter_kernel<false>, dim3(nblocks), dim3(SBLK), 0, s, ki, (const uint32_t*)nullptr, n, shift, nblocks, goff, ko, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(sort_scatter_kernel<false>, dim3(nblocks), dim3(SBLK), 0, s, ki, (const uint32_t*)nullptr, n, shift, dmask, nblocks, goff, ko, (uint32_t*)nullptr);
     std::swap(ki, ko);
   }
   *sorted = ki;

@@ -710,6 +710,37 @@ int shn_lp_set_rule(shn_ctx* ctx, int rule);
  * rows + columns (vertex kept), the rule in force }.                                                                            */
 int shn_lp_stats(shn_ctx* ctx, uint64_t* out8, int reset);
 
+/* ---- --quorum: quality-aware read error correction in front of the counting --------------------------------------------------
+ * Replaces the external `quorum` run of the reference's FASTQ path (shannon.py:385-391: run_quorum puts corrected_reads*.fa in the
+ * place of the read files) by the stated rule of DESIGN.md 3.11, run on the device.
+ *
+ * shn_reads_quality_mask (shannon.py:385-391): the quality lines of the FASTQ text `reads` was ingested from as ONE bit per base,
+ * resident: 1 where the base is one of ACGT (as the ingest codes them) and ord(quality) - 33 >= min_quality.  The bits lie in the
+ * word layout of the set's own mask of bases outside ACGT (64 bases per word, MSB first, every read on its own word boundary),
+ * for fixed-length and ragged sets.  format: 0 by the first character, 2 FASTQ; FASTA text (format 1 or a '>' record) is
+ * SHN_ERR_ARG "... needs FASTQ text ...", and so is text whose records are not those of `reads` (their number, the length of every
+ * one: a ragged set's lengths are compared read by read) or a quality
+ * line of another length than its sequence line.  The mask names its set: the set must outlive every call that takes the mask.   */
+typedef struct shn_qmask shn_qmask;
+int shn_reads_quality_mask(shn_ctx* ctx, const shn_reads* reads, const uint8_t* text, uint64_t n_bytes, int format, uint32_t min_quality,
+                           shn_qmask** out);
+void shn_qmask_destroy(shn_qmask* m);
+uint64_t shn_qmask_n_hq(const shn_qmask* m);            /* bases marked */
+uint64_t shn_qmask_n_words(const shn_qmask* m);         /* 64-bit words of the mask */
+int shn_qmask_download(shn_ctx* ctx, const shn_qmask* m, uint64_t* words_out);
+/* shn_quorum_table (shannon.py:385-391; rule 1): the canonical k-mers of all high-quality windows -- all k bases marked in the mask
+ * -- of all reads of the n_sets read sets (both mates of a run in ONE table), with exact 32-bit counts: a table as shn_count_k1mers
+ * makes them (shn_table_*).  SHN_ERR_ARG before any launch: k outside 15 .. 32, a mask that does not belong to its set.
+ * SHN_ERR_OVERFLOW: 2^32 windows or more in one call.                                                                              */
+int shn_quorum_table(shn_ctx* ctx, const shn_reads* const* sets, const shn_qmask* const* masks, int n_sets, int k, shn_table** out);
+/* shn_quorum_correct (shannon.py:385-391; rules 2-5): *out = a NEW read set of the geometry of `reads` (same count, same lengths)
+ * with the substitutions of the rule; `reads` stays resident and unchanged.  anchor_count = A, window = W, max_subs = E.
+ * stats5 = { reads with an anchor, reads changed, substitutions (those that stay), stopped directions, window reverts }.
+ * SHN_ERR_ARG before any launch: k outside 15 .. 32 or not the table's, a table that is not canonical, anchor_count == 0, max_subs
+ * above 4 (what a walk keeps in registers for the revert).                                                                        */
+int shn_quorum_correct(shn_ctx* ctx, const shn_reads* reads, const shn_table* table, int k, uint32_t anchor_count, uint32_t window,
+                       uint32_t max_subs, shn_reads** out, uint64_t* stats5);
+
 #ifdef __cplusplus
 }
 #endif

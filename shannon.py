@@ -3,7 +3,7 @@
 
 Keeps the reference CLI (sreeramkannan/Shannon shannon.py:145-321) for the flags that drive the
 hot path and produces the same products: OUT/shannon.fasta, OUT/log.txt, OUT/TEMP/ (shannon.py:
-634-638).  Flags that only select external tools outside the path (quorum, --compare) are accepted
+634-638).  Flags that only select external tools outside the path (--compare) are accepted
 and reported as not built.
 
     python shannon.py -o OUT --single reads.fasta            [-K 25] [--partition 500]
@@ -24,6 +24,12 @@ and reported as not built.
                                  the rule of DESIGN.md 3.10, run on the GPU); TEMP/<sample>_allalgo_output/ then holds
                                  rec_before_kallisto.fasta and kallisto/abundance.tsv, OUT/shannon.fasta the filtered transcripts
                                  (paired-end, one-process runs; otherwise a NOTE and nothing is filtered)
+    ... [--quorum]               FASTQ input only (the same gate as --kallisto_cutoff): the reads are error-corrected with their quality
+                                 scores before anything is counted, as the reference does for every FASTQ run (shannon.py:289-299, 385-391;
+                                 Quorum itself is the rule of DESIGN.md 3.11, run on the GPU).  Opt-in here: without the flag a FASTQ run is
+                                 what it was.  TEMP/corrected_reads_1.fa + corrected_reads_2.fa (single-end: corrected_reads.fa) hold the
+                                 corrected reads; everything downstream sees them, --kallisto_cutoff the original ones (shannon.py:378, 612)
+                                 (one-process runs; with -p N / --gpus N a NOTE and nothing is corrected)
     python shannon.py -o OUT --left r1.fasta --right r2.fasta -p 8        # one rank per GPU (the reference's -p nJobs, shannon.py:527-566)
 
 -p N / --gpus N: the reference fans its partitions out over nJobs processes (GNU parallel, shannon.py:527-566); here the N jobs
@@ -267,6 +273,7 @@ def parse_args(argv):
     filter_fp = False
     in_disk = False
     fastq_flag, fasta_flag, kallisto_arg, kallisto_at = False, False, None, 0
+    quorum_flag, quorum_at, quorum_i, kallisto_i = False, 0, 0, 0
     while i < len(argv):
         a = argv[i]
         if a in takes_value and i + 1 >= len(argv):
@@ -324,14 +331,34 @@ def parse_args(argv):
             i += 1; continue
         if a == "--kallisto_cutoff":
             # shannon.py:309-318: what the flag means is known once all of argv is read (the read files' names, --fastq, --fasta)
-            kallisto_arg, kallisto_at = argv[i + 1], len(ignored); i += 2; continue
+            kallisto_arg, kallisto_at, kallisto_i = argv[i + 1], len(ignored), i; i += 2; continue
+        if a == "--quorum":
+            # shannon.py:289-299: like --kallisto_cutoff, what the flag means is known once all of argv is read
+            if not quorum_flag:
+                quorum_flag, quorum_at, quorum_i = True, len(ignored), i
+            i += 1; continue
         if a == "--compare":
             ignored.append(a); i += 2; continue
         ignored.append(a); i += 1
     kallisto_cutoff = None
+    # shannon.py:289-307: FASTQ by the first read file's last letter or --fastq; --fasta turns it off
+    fastq = ((bool(reads) and reads[0][-1:] == "q") or fastq_flag) and not fasta_flag
+    quorum = False
+    if quorum_flag:
+        if fastq:
+            print("OPTIONS --quorum: read error correction with quality scores enabled")
+            quorum = True
+            if max(nJobs, n_gpus) > 1:
+                noted.append("--quorum: the read error correction is built for one-process runs only; with -p N / --gpus N nothing is "
+                             "corrected")
+                quorum = False
+        else:
+            print("OPTIONS WARNING: --quorum NOT enabled. Option only works with fastq input.")
+            # (among the ignored flags where it stood in argv; a --kallisto_cutoff that joins them below and stood behind it stays behind it)
+            ignored.insert(quorum_at, "--quorum")
+            if kallisto_arg is not None and kallisto_i > quorum_i:
+                kallisto_at += 1
     if kallisto_arg is not None:
-        # shannon.py:289-307: FASTQ by the first read file's last letter or --fastq; --fasta turns it off
-        fastq = ((bool(reads) and reads[0][-1:] == "q") or fastq_flag) and not fasta_flag
         if fastq:
             try:
                 kallisto_cutoff = float(kallisto_arg)
@@ -367,6 +394,7 @@ def parse_args(argv):
     o.min_weight, o.min_length, o.kmer_hard_cutoff = min_weight, min_length, kmer_hard_cutoff
     o.ignored, o.noted, o.filter_fp = ignored, noted, filter_fp
     o.kallisto_cutoff = kallisto_cutoff
+    o.quorum = quorum
     return o
 
 
@@ -454,17 +482,48 @@ def main(argv):
     T["ingest"] = _t.time() - t0
     avg_len = (sum(len(x) for x in r[0]) / max(1, len(r[0]))) if sets is None else (r[0].total_bases / max(1, len(r[0])) if isinstance(r[0], device.RaggedCodes) else r[0].shape[1])
     say("Processed No of reads:%d, Avg. Read length: %.2f (read files through the %s ingest)" % (len(r[0]), avg_len, T["ingest path"]))
-    if sets is not None:
-        from shannon_amd import kmers_for_component as kfc
-        R = pipeline.assemble_resident(ctx, sets[0], sets[1] if paired else None, kfc.ReadStore(r[0], r[1] if paired else None), K=K,
-                                       partition_size=partition_size, min_weight=min_weight, min_length=min_length, sample=sample, seed=0,
-                                       double_stranded=double_stranded, timings=T, kmer_hard_cutoff=kmer_hard_cutoff,
-                                       filter_fp=filter_fp, in_disk_dir=temp if o.in_disk else None, kallisto_cutoff=o.kallisto_cutoff)
-    else:
-        R = pipeline.assemble(ctx, r[0], r[1] if paired else None, K=K, partition_size=partition_size, min_weight=min_weight,
-                              min_length=min_length, sample=sample, seed=0, double_stranded=double_stranded, timings=T,
-                              kmer_hard_cutoff=kmer_hard_cutoff, filter_fp=filter_fp, in_disk_dir=temp if o.in_disk else None,
-                              kallisto_cutoff=o.kallisto_cutoff)
+    corrected = None
+    if o.quorum and sets is None:
+        say("NOTE: --quorum: the read files did not go through the device ingest (multi-line FASTA, mate files of different sizes); "
+            "nothing is corrected")
+    elif o.quorum:
+        # shannon.py:385-391: corrected_reads*.fa take the place of the read files for everything but kallisto (:378, 612)
+        from shannon_amd import quorum
+        try:
+            corrected, r, qst = quorum.apply(ctx, sets, reads, host=r, timings=T)
+        except _lib.ShannonError as ex:
+            if "needs FASTQ text" not in str(ex):
+                raise
+            say("NOTE: --quorum: the read files hold no quality lines (FASTA text behind --fastq or a name that ends in q); nothing is corrected")
+    try:
+        if corrected is not None:
+            t0 = _t.time()
+            written = quorum.write_fasta(ctx, corrected, temp)
+            T["quorum files"] = _t.time() - t0
+            say("--quorum: k %d, quality %d, anchor count %d, %d substitutions in a window of %d: %d of %d reads anchored, %d changed, %d substitutions, "
+                "%d stopped directions, %d window reverts; table of %d k-mers from %d high-quality windows; %s (%d bytes)"
+                % (quorum.K, quorum.MIN_QUALITY, quorum.ANCHOR_COUNT, quorum.MAX_SUBS, quorum.WINDOW, qst["anchored"], sum(len(c) for c in corrected),
+                   qst["changed"], qst["substitutions"], qst["stopped"], qst["reverts"], qst["table"], qst["windows"], " ".join(sorted(written)),
+                   sum(written.values())))
+            tm, tb = ctx.timers(), ctx.timer_bytes()                        # (HIP events around the launches, the bytes their sites price)
+            say("quorum kernels: " + json.dumps({k: {"ms": round(v[0], 4), "regions": v[1], "bytes": tb.get(k, 0)}
+                                                 for k, v in sorted(tm.items()) if k.startswith("quorum.")}))
+        if sets is not None:
+            from shannon_amd import kmers_for_component as kfc
+            use = corrected if corrected is not None else sets
+            R = pipeline.assemble_resident(ctx, use[0], use[1] if paired else None, kfc.ReadStore(r[0], r[1] if paired else None), K=K,
+                                           partition_size=partition_size, min_weight=min_weight, min_length=min_length, sample=sample, seed=0,
+                                           double_stranded=double_stranded, timings=T, kmer_hard_cutoff=kmer_hard_cutoff,
+                                           filter_fp=filter_fp, in_disk_dir=temp if o.in_disk else None, kallisto_cutoff=o.kallisto_cutoff,
+                                           kallisto_reads=(sets[0], sets[1] if paired else None) if corrected is not None else None)
+        else:
+            R = pipeline.assemble(ctx, r[0], r[1] if paired else None, K=K, partition_size=partition_size, min_weight=min_weight,
+                                  min_length=min_length, sample=sample, seed=0, double_stranded=double_stranded, timings=T,
+                                  kmer_hard_cutoff=kmer_hard_cutoff, filter_fp=filter_fp, in_disk_dir=temp if o.in_disk else None,
+                                  kallisto_cutoff=o.kallisto_cutoff)
+    finally:
+        for c in corrected or ():                       # (nothing behind the pipeline reads the corrected sets)
+            c.close()
     if o.in_disk:
         say("--inDisk: reads*.fasta and k1mer.dict of %d partitions under %s (%d bytes)"
             % (len(R.in_disk), temp, sum(sum(f.values()) for f in R.in_disk.values())))

@@ -176,6 +176,13 @@ SIGNATURES = {
     "shn_devtext_segments": (C.c_int, [vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp]),
     "shn_devtext_destroy": (None, [vp]),
     "shn_ext_weights": (C.c_int, [vp, vp, vp, C.c_uint64, vp]),
+    "shn_reads_quality_mask": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_int, C.c_uint32, vpp]),
+    "shn_qmask_destroy": (None, [vp]),
+    "shn_qmask_n_hq": (C.c_uint64, [vp]),
+    "shn_qmask_n_words": (C.c_uint64, [vp]),
+    "shn_qmask_download": (C.c_int, [vp, vp, vp]),
+    "shn_quorum_table": (C.c_int, [vp, vpp, vpp, C.c_int, C.c_int, vpp]),
+    "shn_quorum_correct": (C.c_int, [vp, vp, vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vpp, vp]),
 }
 
 

@@ -59,7 +59,9 @@ enum {
   // --inDisk (reads_text.hip): the records of reads*.fasta, of k1mer.dict
   T_READS_FASTA, T_K1MERS_DICT,
   // --kallisto_cutoff (abundance.hip): index of the final transcripts, compatibility lists + span histogram, classes, the EM's rounds
-  T_ABD_INDEX, T_ABD_MAP, T_ABD_CLASSES, T_ABD_EM, T_N = 56
+  T_ABD_INDEX, T_ABD_MAP, T_ABD_CLASSES, T_ABD_EM,
+  // --quorum (quorum.hip): can(w) of every high-quality window, the table of them (sort + run lengths), the per-read correction
+  T_QUORUM_COUNT, T_QUORUM_TABLE, T_QUORUM_CORRECT, T_N = 59
 };
 
 // grow-only device workspace slot (process-wide ones: g_shn_ws below; per-context ones: shn_ctx::cws)
@@ -156,6 +158,18 @@ struct shn_reads {
   uint32_t* d_len;         // ragged: length of each read, else NULL
   uint8_t* d_bad;          // per read: 1 if it contains a non-ACGT base (NULL if none)
   bool cached;             // device arrays come from the caching allocator (shn_reads_gather), not hipMalloc
+};
+
+// the high-quality mask of a read set (shn_reads_quality_mask): bit = 1 where the base is one of ACGT and its quality reaches the
+// threshold, in the word geometry of the set's d_mask (n_words / 2 + 2 words, the last two zero)
+struct shn_qmask {
+  shn_ctx* ctx;
+  int device;
+  const shn_reads* owner;  // the set the mask was made for, with the figures that say it is still that set
+  uint64_t n_reads, n_words, total_bases;
+  uint32_t min_quality;
+  uint64_t n_hq;           // bases marked
+  uint64_t* d_hq;
 };
 
 // text on the device (the candidate contigs as shn_ext_emit_device leaves them): n bytes + 64 zeroed

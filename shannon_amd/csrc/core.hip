@@ -29,7 +29,7 @@ static const char* kTimerNames[T_N] = {
   "extend.walk_fresh", "extend.begin", "count.sk_buckets2",
   "contig.sort", "contig.hits", "contig.cover", "contig.compact", "graph.kp_search", "graph.kp_classify", "graph.seed_scan", "graph.dd_insert", "lp.trials",
   "extend.audit", "filter_fp.index", "filter_fp.map", "filter_fp.count", "filter_fp.merge", "reads.collect", "reads.fasta", "k1mers.dict",
-  "abundance.index", "abundance.map", "abundance.classes", "abundance.em"};
+  "abundance.index", "abundance.map", "abundance.classes", "abundance.em", "quorum.count", "quorum.table", "quorum.correct"};
 extern "C" const char* shn_timer_name(int slot) {
   if (slot < 0 || slot >= T_N || !kTimerNames[slot]) return "";
   return kTimerNames[slot];
@@ -680,24 +680,8 @@ int shn_pack_fixed_codes(shn_ctx* ctx, const uint8_t* d_codes, uint64_t n, uint3
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? SHN_OK : shn_fail(SHN_ERR_HIP, std::string("pack_kernel: ") + hipGetErrorString(e));
 }
-int shn_reads_finish_fixed(shn_ctx* ctx, shn_reads* r) {
-  hipStream_t s = ctx->stream; shn_use_stream(s);
-  unsigned long long* d_nbad = nullptr;
-  HIP_TRY(shn_hip_malloc(&d_nbad, 8));
-  hipError_t e = hipMemsetAsync(d_nbad, 0, 8, s);
-  if (e == hipSuccess) e = shn_hip_malloc(&r->d_bad, r->n_reads ? r->n_reads : 1);
-  unsigned long long nb = 0;
-  if (e == hipSuccess && r->n_reads) {
-    hipLaunchKernelGGL(bad_reads_kernel, dim3((uint32_t)cdiv(r->n_reads, 256)), dim3(256), 0, s, r->d_mask, (const uint64_t*)nullptr, r->n_reads, r->wpr,
-                       r->d_bad, d_nbad);
-    e = hipMemcpyAsync(&nb, d_nbad, 8, hipMemcpyDeviceToHost, s);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  hipFree(d_nbad);
-  if (e != hipSuccess) return shn_fail(SHN_ERR_HIP, std::string("shn_reads_finish_fixed: ") + hipGetErrorString(e));
-  r->n_invalid = nb;
-  return SHN_OK;
-}
+int shn_reads_refresh_bad(shn_ctx* ctx, shn_reads* r);
+int shn_reads_finish_fixed(shn_ctx* ctx, shn_reads* r) { return shn_reads_refresh_bad(ctx, r); }
 
 // Rows of resident fixed-length read sets as a new read set, without a trip through the host: read i = row rows[i] of set a
 // (flags[i] bit 0 clear) or b (set), reverse-complemented if bit 1 is set.  The graph stage builds its distinct-read set this
@@ -763,6 +747,53 @@ extern "C" int shn_reads_gather(shn_ctx* ctx, const shn_reads* a, const shn_read
 int shn_reads_gather_dev(shn_ctx* ctx, const shn_reads* a, const shn_reads* b, const uint32_t* d_rows, const uint8_t* d_flags, uint64_t n, shn_reads** out) {
   if (!ctx || !a || !out || (n && (!d_rows || !d_flags))) return shn_fail(SHN_ERR_ARG, "shn_reads_gather_dev: NULL argument");
   return reads_gather_impl(ctx, a, b, nullptr, nullptr, d_rows, d_flags, n, out);
+}
+
+// A read set of the geometry of `src` with copies of its arrays (device to device), for a kernel that rewrites bases in place
+// (quorum.hip); shn_reads_refresh_bad then counts the reads with a base outside ACGT again.
+int shn_reads_clone(shn_ctx* ctx, const shn_reads* src, shn_reads** out) {
+  hipStream_t s = ctx->stream; shn_use_stream(s);
+  shn_reads* r = new shn_reads(*src);
+  r->ctx = ctx; r->device = ctx->device; r->cached = false;
+  r->d_words = nullptr; r->d_mask = nullptr; r->d_woff = nullptr; r->d_len = nullptr; r->d_bad = nullptr;
+  auto fail = [&](hipError_t e) { shn_reads_destroy(r); return shn_fail(SHN_ERR_HIP, std::string("shn_reads_clone: ") + hipGetErrorString(e)); };
+  hipError_t e;
+  const size_t wb = (src->n_words + 2) * 8, mb = (src->n_words / 2 + 2) * 8;
+  if ((e = shn_hip_malloc(&r->d_words, wb)) != hipSuccess) return fail(e);
+  if ((e = shn_hip_malloc(&r->d_mask, mb)) != hipSuccess) return fail(e);
+  if ((e = hipMemcpyAsync(r->d_words, src->d_words, wb, hipMemcpyDeviceToDevice, s)) != hipSuccess) return fail(e);
+  if (src->d_mask) e = hipMemcpyAsync(r->d_mask, src->d_mask, mb, hipMemcpyDeviceToDevice, s);
+  else e = hipMemsetAsync(r->d_mask, 0, mb, s);
+  if (e != hipSuccess) return fail(e);
+  if (src->d_woff) {
+    if ((e = shn_hip_malloc(&r->d_woff, (src->n_reads + 1) * 8)) != hipSuccess) return fail(e);
+    if ((e = hipMemcpyAsync(r->d_woff, src->d_woff, (src->n_reads + 1) * 8, hipMemcpyDeviceToDevice, s)) != hipSuccess) return fail(e);
+  }
+  if (src->d_len) {
+    if ((e = shn_hip_malloc(&r->d_len, (src->n_reads ? src->n_reads : 1) * 4)) != hipSuccess) return fail(e);
+    if (src->n_reads && (e = hipMemcpyAsync(r->d_len, src->d_len, src->n_reads * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess) return fail(e);
+  }
+  *out = r;
+  return SHN_OK;
+}
+// d_bad and n_invalid of a set from its mask as it is now (fixed-length or ragged; d_bad is allocated where the set has none yet)
+int shn_reads_refresh_bad(shn_ctx* ctx, shn_reads* r) {
+  hipStream_t s = ctx->stream; shn_use_stream(s);
+  unsigned long long* d_nbad = nullptr;
+  HIP_TRY(shn_hip_malloc(&d_nbad, 8));
+  hipError_t e = hipMemsetAsync(d_nbad, 0, 8, s);
+  if (e == hipSuccess && !r->d_bad) e = shn_hip_malloc(&r->d_bad, r->n_reads ? r->n_reads : 1);
+  unsigned long long nb = 0;
+  if (e == hipSuccess && r->n_reads) {
+    hipLaunchKernelGGL(bad_reads_kernel, dim3((uint32_t)cdiv(r->n_reads, 256)), dim3(256), 0, s, r->d_mask, (const uint64_t*)r->d_woff, r->n_reads, r->wpr,
+                       r->d_bad, d_nbad);
+    e = hipMemcpyAsync(&nb, d_nbad, 8, hipMemcpyDeviceToHost, s);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  hipFree(d_nbad);
+  if (e != hipSuccess) return shn_fail(SHN_ERR_HIP, std::string("shn_reads_refresh_bad: ") + hipGetErrorString(e));
+  r->n_invalid = nb;
+  return SHN_OK;
 }
 
 extern "C" void shn_reads_destroy(shn_reads* r) {

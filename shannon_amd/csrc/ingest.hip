@@ -59,8 +59,9 @@ uint64_t align_record(const uint8_t* t, uint64_t n, uint64_t pos, bool fastq) {
   return n;
 }
 
-// visits the records of [b0, b1): fn(seq_start, seq_len); returns false on a malformed record
-template <class F> int walk_records(const uint8_t* t, uint64_t n, uint64_t b0, uint64_t b1, bool fastq, F&& fn) {
+// visits the records of [b0, b1): fn(seq_start, seq_len, quality_start, quality_len) -- the last two 0 for FASTA; returns
+// non-zero on a malformed record
+template <class F> int walk_records_q(const uint8_t* t, uint64_t n, uint64_t b0, uint64_t b1, bool fastq, F&& fn) {
   uint64_t p = b0;
   const uint8_t mark = fastq ? '@' : '>';
   while (p < b1) {
@@ -74,17 +75,25 @@ template <class F> int walk_records(const uint8_t* t, uint64_t n, uint64_t b0, u
     e = line_end(t, n, s);
     uint64_t len = e - s;
     if (len && t[s + len - 1] == '\r') len--;
-    fn(s, len);
     p = e + 1;
+    uint64_t qs = 0, qlen = 0;
     if (fastq) {
       if (p >= n || t[p] != '+') return 2;
       e = line_end(t, n, p);
       if (e >= n) return 2;
-      e = line_end(t, n, e + 1);
+      qs = e + 1;
+      e = line_end(t, n, qs);
+      qlen = e - qs;
+      if (qlen && t[qs + qlen - 1] == '\r') qlen--;
       p = e + 1;
     }
+    fn(s, len, qs, qlen);
   }
   return 0;
+}
+// the same for callers that read the sequence lines only: fn(seq_start, seq_len)
+template <class F> int walk_records(const uint8_t* t, uint64_t n, uint64_t b0, uint64_t b1, bool fastq, F&& fn) {
+  return walk_records_q(t, n, b0, b1, fastq, [&](uint64_t s, uint64_t len, uint64_t, uint64_t) { fn(s, len); });
 }
 
 }  // namespace
@@ -412,3 +421,131 @@ extern "C" int shn_reads_ingest_ragged(shn_ctx* ctx, const uint8_t* text, uint64
   if (!out) return SHN_OK;
   return shn_reads_create(ctx, codes_out, offsets_out, N, 0, SHN_ENC_CODES, out);
 }
+
+
+// ---- the quality lines of the same text (--quorum, shannon.py:385-391: the reference hands its FASTQ files to Quorum; here the
+// correction of DESIGN.md 3.11 reads the qualities as ONE bit per base).  Bit = 1 where the base is one of ACGT, as the ingest codes
+// them, and ord(quality) - 33 >= min_quality; the bits lie as the bits of the set's own mask of bases outside ACGT do (64 bases per
+// word, MSB first, every read on the word boundary its packed bases start on), for fixed-length and ragged sets alike.  The text
+// must be the FASTQ text `reads` was ingested from: another number of records or another length of one is SHN_ERR_ARG, and so is
+// FASTA text ("... needs FASTQ text ...") or a quality line of another length than its sequence line.  The words are put together on
+// host threads (the parse is the ingest's) and go up in one copy.
+extern "C" int shn_reads_quality_mask(shn_ctx* ctx, const shn_reads* reads, const uint8_t* text, uint64_t n_bytes, int format, uint32_t min_quality,
+                                      shn_qmask** out) {
+  if (!ctx || !reads || !out || (n_bytes && !text)) return shn_fail(SHN_ERR_ARG, "shn_reads_quality_mask: NULL argument");
+  *out = nullptr;
+  if (format < 0 || format > 2) return shn_fail(SHN_ERR_ARG, "shn_reads_quality_mask: bad format");
+  if (format == 1 || !text_is_fastq(text, n_bytes, format))
+    return shn_fail(SHN_ERR_ARG, "shn_reads_quality_mask: needs FASTQ text (FASTA records carry no quality line)");
+  if (min_quality > 93) return shn_fail(SHN_ERR_ARG, "shn_reads_quality_mask: min_quality above 93 (the largest Phred+33 value of a printable character)");
+  uint64_t lead = 0;
+  while (lead < n_bytes && (text[lead] == '\n' || text[lead] == '\r')) lead++;
+  // ranges of the text cut at record starts, as the ingest cuts them; pass 1 counts a range's records, bases and mask words, pass 2
+  // writes the words of its records -- a read's words are its own, so the ranges' threads never meet
+  const unsigned T = (unsigned)std::max(1, std::min(shn_host_cpus(), 64));
+  const uint64_t range_bytes = std::min<uint64_t>(std::max<uint64_t>(n_bytes / 64, 64u << 10), 16u << 20);
+  const uint64_t n_ranges = std::max<uint64_t>(1, n_bytes / range_bytes + 1);
+  struct QRange { uint64_t b0 = 0, b1 = 0, n_rec = 0, rec0 = 0, bases = 0, words = 0, word0 = 0, n_hq = 0; int bad = 0; bool qlen_bad = false, len_bad = false; };
+  std::vector<QRange> R(n_ranges);
+  auto on_threads = [&](auto&& fn) {
+    std::atomic<uint64_t> next{0};
+    auto work = [&]() { for (uint64_t i; (i = next.fetch_add(1)) < n_ranges;) fn(i); };
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < std::min<uint64_t>(T, n_ranges); t++) th.emplace_back(work);
+    work();
+    for (auto& x : th) x.join();
+  };
+  on_threads([&](uint64_t i) { R[i].b0 = align_record(text, n_bytes, i == 0 ? lead : n_bytes / n_ranges * i, true); });
+  for (uint64_t i = 0; i < n_ranges; i++) R[i].b1 = i + 1 < n_ranges ? R[i + 1].b0 : n_bytes;
+  const uint32_t fixed = reads->fixed_len, fixed_words = reads->wpr / 2;
+  on_threads([&](uint64_t i) {
+    QRange& r = R[i];
+    if (r.b0 >= r.b1) return;
+    r.bad = walk_records_q(text, n_bytes, r.b0, r.b1, true, [&](uint64_t, uint64_t len, uint64_t, uint64_t qlen) {
+      if (qlen != len) r.qlen_bad = true;
+      if (fixed && len != fixed) r.len_bad = true;
+      r.n_rec++; r.bases += len;
+      r.words += fixed ? fixed_words : cdiv(len ? len : 1, 64);
+    });
+  });
+  uint64_t N = 0, bases = 0, words = 0;
+  for (auto& r : R) {
+    if (r.bad) return shn_fail(SHN_ERR_ARG, r.bad == 1 ? "shn_reads_quality_mask: unsupported: a record does not start with its marker"
+                                                       : "shn_reads_quality_mask: unsupported: truncated record");
+    if (r.qlen_bad) return shn_fail(SHN_ERR_ARG, "shn_reads_quality_mask: unsupported: a quality line of another length than its sequence line");
+    r.word0 = words; r.rec0 = N;
+    N += r.n_rec; bases += r.bases; words += r.words;
+  }
+  if (N != reads->n_reads)
+    return shn_fail(SHN_ERR_ARG, "shn_reads_quality_mask: the text holds " + std::to_string(N) + " records, the read set " + std::to_string(reads->n_reads));
+  bool len_bad = false;
+  for (auto& r : R) len_bad = len_bad || r.len_bad;
+  if (len_bad || words * 2 != reads->n_words || bases != reads->total_bases)
+    return shn_fail(SHN_ERR_ARG, "shn_reads_quality_mask: the records' lengths are not those of the read set");
+  const uint64_t n_mw = reads->n_words / 2;
+  std::vector<uint32_t> lens(fixed ? 0 : N);                          // ragged: every record's length, held against the set's below
+  std::vector<uint64_t> hq(n_mw + 2, 0);
+  const uint8_t qmin = (uint8_t)(33 + min_quality);
+  on_threads([&](uint64_t i) {
+    QRange& r = R[i];
+    if (!r.n_rec) return;
+    uint64_t* dst = hq.data() + r.word0;
+    uint64_t marked = 0, k = r.rec0;
+    walk_records_q(text, n_bytes, r.b0, r.b1, true, [&](uint64_t s, uint64_t len, uint64_t qs, uint64_t) {
+      const uint8_t* p = text + s;
+      const uint8_t* q = text + qs;
+      for (uint64_t j0 = 0; j0 < len; j0 += 64) {
+        uint64_t m = 0;
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(64, len - j0);
+        for (uint32_t j = 0; j < nb; j++) {
+          const uint8_t u = (uint8_t)(p[j0 + j] & 0xDF);
+          const uint64_t ok = (uint64_t)(((u == 'A') | (u == 'C') | (u == 'G') | (u == 'T')) & (q[j0 + j] >= qmin));
+          m |= ok << (63 - j);
+        }
+        dst[j0 >> 6] = m;
+        marked += (uint64_t)__builtin_popcountll(m);
+      }
+      dst += fixed ? fixed_words : cdiv(len ? len : 1, 64);
+      if (!fixed) lens[k++] = (uint32_t)len;
+    });
+    r.n_hq = marked;
+  });
+  uint64_t n_hq_total = 0;
+  for (auto& r : R) n_hq_total += r.n_hq;
+  SHN_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  if (!fixed && N) {
+    // a ragged set: the same count, words and bases can be shared out among the reads in another way -- record by record
+    std::vector<uint32_t> have(N);
+    HIP_TRY(hipMemcpyAsync(have.data(), reads->d_len, N * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (uint64_t i = 0; i < N; i++)
+      if (have[i] != lens[i])
+        return shn_fail(SHN_ERR_ARG, "shn_reads_quality_mask: the records' lengths are not those of the read set: record " + std::to_string(i) + " has " +
+                                         std::to_string(lens[i]) + " bases, the set's read " + std::to_string(have[i]));
+  }
+  shn_qmask* m = new shn_qmask();
+  m->ctx = ctx; m->device = ctx->device; m->owner = reads; m->n_reads = N; m->n_words = reads->n_words; m->total_bases = bases;
+  m->min_quality = min_quality; m->n_hq = n_hq_total; m->d_hq = nullptr;
+  hipError_t e = shn_hip_malloc(&m->d_hq, (n_mw + 2) * 8);
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_hq, hq.data(), (n_mw + 2) * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);                 // (hq is this call's vector)
+  if (e != hipSuccess) { shn_qmask_destroy(m); return shn_fail(SHN_ERR_HIP, std::string("shn_reads_quality_mask: ") + hipGetErrorString(e)); }
+  *out = m;
+  return SHN_OK;
+}
+extern "C" void shn_qmask_destroy(shn_qmask* m) {
+  if (!m) return;
+  hipSetDevice(m->device);
+  if (m->d_hq) hipFree(m->d_hq);
+  delete m;
+}
+extern "C" uint64_t shn_qmask_n_hq(const shn_qmask* m) { return m ? m->n_hq : 0; }
+extern "C" int shn_qmask_download(shn_ctx* ctx, const shn_qmask* m, uint64_t* words_out) {
+  if (!ctx || !m || !words_out) return shn_fail(SHN_ERR_ARG, "shn_qmask_download: NULL argument");
+  SHN_ENTER(ctx);
+  HIP_TRY(hipMemcpyAsync(words_out, m->d_hq, (m->n_words / 2) * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return SHN_OK;
+}
+extern "C" uint64_t shn_qmask_n_words(const shn_qmask* m) { return m ? m->n_words / 2 : 0; }

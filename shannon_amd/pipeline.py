@@ -71,11 +71,11 @@ def n_kmer_nodes(rows, K):
 
 def assemble(ctx, reads1, reads2=None, K=25, partition_size=500, min_weight=3, min_length=75, overload=2, penalty=5,
              sample="shannon", seed=0, double_stranded=True, part_vectors=None, timings=None, hits_factory=None,
-             native_graph=True, kmer_hard_cutoff=1, filter_fp=False, in_disk_dir=None, kallisto_cutoff=None):
+             native_graph=True, kmer_hard_cutoff=1, filter_fp=False, in_disk_dir=None, kallisto_cutoff=None, kallisto_reads=None):
     """reads1/reads2: lists of strings or uint8 code matrices (reads2 None = single-end).
     min_weight = the reference's hyp_min_weight (--kmer_soft_cutoff, shannon.py:243-247, 457); kmer_hard_cutoff = its
     jellyfish_kmer_cutoff (--kmer_hard_cutoff, `jellyfish dump -L`, shannon.py:237-241, 441).  filter_fp: --filter_FP, in_disk_dir:
-    --inDisk, kallisto_cutoff: --kallisto_cutoff, see assemble_resident.
+    --inDisk, kallisto_cutoff: --kallisto_cutoff, kallisto_reads: the resident sets it quantifies against, see assemble_resident.
     Returns Result with .partitions {name: dict}, .all_reconstructed (lines), .final {name: seq}."""
     T = timings if timings is not None else {}
     paired = reads2 is not None
@@ -91,13 +91,13 @@ def assemble(ctx, reads1, reads2=None, K=25, partition_size=500, min_weight=3, m
     tick("upload+pack", t0)
     return assemble_resident(ctx, d1, d2, store, K, partition_size, min_weight, min_length, overload, penalty, sample, seed,
                              double_stranded, part_vectors, T, hits_factory, native_graph, kmer_hard_cutoff=kmer_hard_cutoff, filter_fp=filter_fp,
-                             in_disk_dir=in_disk_dir, kallisto_cutoff=kallisto_cutoff)
+                             in_disk_dir=in_disk_dir, kallisto_cutoff=kallisto_cutoff, kallisto_reads=kallisto_reads)
 
 
 def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3, min_length=75, overload=2, penalty=5,
                       sample="shannon", seed=0, double_stranded=True, part_vectors=None, timings=None, hits_factory=None,
                       native_graph=True, graph_threads=None, keep_partitioning=False, defer_back=False, kmer_hard_cutoff=1, filter_fp=False,
-                      in_disk_dir=None, kallisto_cutoff=None):
+                      in_disk_dir=None, kallisto_cutoff=None, kallisto_reads=None):
     """Same as assemble() with the reads already packed in HBM (d1/d2: device.Reads).  graph_threads: partitions whose
     graph stage may run concurrently on host threads.  keep_partitioning: leave the partition stage's tables (partition ->
     contigs, routed read indices) on the result as `.partitioning` (tests/test_fullsize_gpu.py reads them).  defer_back: run count,
@@ -115,7 +115,10 @@ def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3
     is quantified against ALL read pairs (abundance.apply: DESIGN.md 3.10) and stays only if est_counts / eff_length * L >= C;
     R.final is then the filtered set (a dict), R.final_before_kallisto what the merge gave, R.abundance the table (with the text of
     abundance.tsv under "tsv" and of rec_before_kallisto.fasta under "before"), the time under timings["abundance"].  Paired-end
-    input only (single-end: R.kallisto_note says so, nothing is filtered).  None: nothing of this runs; works together with filter_fp."""
+    input only (single-end: R.kallisto_note says so, nothing is filtered).  None: nothing of this runs; works together with filter_fp.
+    kallisto_reads: (reads_1, reads_2), the resident sets --kallisto_cutoff quantifies against where they are not d1 / d2 -- the
+    reference hands kallisto the ORIGINAL read files while everything else sees Quorum's corrected ones (shannon.py:378, 612; --quorum:
+    quorum.apply).  None: d1 / d2."""
     # double_stranded=False: -s / --ss / --strand_specific.  shannon.py:394-424 then leaves single-end reads as they are and
     # reverse-complements the second mates, without doubling; from :427 on double_stranded is False in BOTH modes, so only the read
     # set differs: forward counting (d2: its reverse complements), routes of plain read indices, pairs (R1[i], RC(R2[i])) in the
@@ -428,13 +431,14 @@ def assemble_resident(ctx, d1, d2, store, K=25, partition_size=500, min_weight=3
             """--kallisto_cutoff on R.final (the merge's result)"""
             if kallisto_cutoff is None:
                 return
-            if not paired or d1 is None or d2 is None:
+            k1, k2 = kallisto_reads if kallisto_reads is not None else (d1, d2)
+            if not paired or k1 is None or k2 is None:
                 R.kallisto_note = ("--kallisto_cutoff: single-end input is not built (the reference runs kallisto --single -l 200 -s 20, "
                                    "filter_kallisto.py:25); nothing filtered")
                 return
             t0 = time.time()
             from . import abundance
-            kept, table, tsv, before = abundance.apply(kctx, R.final, d1, d2, ss, kallisto_cutoff)
+            kept, table, tsv, before = abundance.apply(kctx, R.final, k1, k2, ss, kallisto_cutoff)
             table["tsv"], table["before"] = tsv, before
             R.final_before_kallisto, R.final, R.abundance = R.final, kept, table
             tick("abundance", t0)

@@ -100,7 +100,13 @@ struct StringInterner {
   std::string arena;
   size_t mask = 0;
   bool bulk_loaded = false;               // entries were appended without going through the probe table
-  explicit StringInterner(size_t expect = 1024) { size_t c = 1024; while (c < expect * 2) c <<= 1; table.assign(c, -1); mask = c - 1; off.push_back(0); }
+  explicit StringInterner(size_t expect = 1024) { reset(expect); }
+  // empty, as constructed for `expect` strings; the capacity of the arrays and the arena is kept
+  void reset(size_t expect) {
+    size_t c = 1024;
+    while (c < expect * 2) c <<= 1;
+    table.assign(c, -1); mask = c - 1; hashes.clear(); off.assign(1, 0); arena.clear(); bulk_loaded = false;
+  }
   static uint64_t hash(const char* p, size_t n) {
     uint64_t h = 0x9E3779B97F4A7C15ULL ^ n;
     size_t i = 0;

@@ -4,39 +4,21 @@
 // graph surgery in Python was 2/3 of the whole step.  Control logic over small irregular graphs:
 // host code; the order-defining conventions (P1-P3) are identical to the Python mirror,
 // which stays as the readable specification and is cross-checked against this in the tests.
-#include "common.h"
-#include <atomic>
-#include "flatmap.h"
-#include "graph_dev.h"
+// (mbgraph_reads.h brings common.h, flatmap.h and graph_dev.h, and -- beside the reads -- what both sides of the stage share: the
+// host-thread budget ThreadBudget / BudgetGuard / FreeThreads, run_on_threads, the clock tnow, the lap printer lap_line, base_code)
+#include "mbgraph_reads.h"
 #include "unitigs.h"
 #include "graph_result.h"
-#include <thread>
-#include <mutex>
-#include <sys/mman.h>
-#include <condition_variable>
-#include <string>
-#include <vector>
 #include <unordered_map>
 #include <map>
 #include <set>
-#include <algorithm>
-#include <cstring>
 #include <cmath>
 #include <array>
-#include <chrono>
-#include <cstdio>
 #include <cstdlib>
-
-extern "C" int shn_known_paths_scan(shn_ctx* ctx, const shn_reads* reads, int K, const uint8_t* node_bases, const uint64_t* node_off,
-                                    uint64_t n_nodes, uint8_t* state_out, int32_t* node_out, uint32_t* offset_out);
 
 namespace {
 
 typedef std::pair<int, int> RI;   // (read id, index)
-
-static inline int base_code(char c) {
-  switch (c) { case 'A': return 0; case 'C': return 1; case 'G': return 2; case 'T': return 3; default: return -1; }
-}
 
 // unique packed K-mer keys -> groups of occurrences (kept in insertion order inside a group)
 struct SeedIndex {
@@ -58,22 +40,6 @@ struct SeedIndex {
   }
 };
 
-// read string living in the interner arena
-struct RStr {
-  const char* p; size_t n;
-  size_t size() const { return n; }
-  const char& operator[](size_t i) const { return p[i]; }
-  int compare(size_t pos, size_t len, const std::string& o) const {
-    size_t m = std::min(len, n - pos);
-    int c = memcmp(p + pos, o.data(), std::min(m, o.size()));
-    if (c) return c;
-    return m < o.size() ? -1 : (m > o.size() ? 1 : 0);
-  }
-  std::string substr(size_t pos, size_t len) const { return std::string(p + pos, std::min(len, n - pos)); }
-  const char* begin() const { return p; }
-  const char* end() const { return p + n; }
-};
-
 // ascending order for a list that is usually ascending already or two ascending runs one after the other (a bridging step hands a
 // new node the reads of the old one twice, each time in order): a merge instead of a sort
 template <class V> static void sort_runs(V& v) {
@@ -82,73 +48,6 @@ template <class V> static void sort_runs(V& v) {
   if (p == e) return;
   if (std::is_sorted(p, e)) { std::inplace_merge(b, p, e); return; }
   std::sort(b, e);
-}
-
-// several partitions run on host threads at once; every thread has a context / stream of its own (ThreadCtx below), the
-// calls its GPU sections make use per-call or per-context buffers only, so the sections overlap on the device
-
-// Host-thread budget shared by the partitions of a process.  The multi-threaded phases of a partition (read decode, duplicate
-// search, numbering, path classification) take as many tokens as they start threads; with 64 partitions beginning at once and up
-// to 32 threads each the cores were oversubscribed five-fold and every phase ran ten times slower than alone -- the largest
-// partition, which bounds the stage, included.  Partitions are started largest first, so the large ones get their threads first.
-struct ThreadBudget {
-  std::mutex mu; std::condition_variable cv; int avail;
-  ThreadBudget() { const int hw = shn_host_cpus(); avail = (int)shn_env_u64("SHN_GRAPH_HOST_THREADS", (uint64_t)std::max(4, hw), 1, 1u << 20); total = avail; }
-  int total;
-  // large requests (the large partitions, which bound the stage) never wait -- they may overdraw the budget; small ones wait for it
-  void acquire(int n) { n = std::min(n, total); std::unique_lock<std::mutex> lk(mu); if (n < 8) cv.wait(lk, [&] { return avail >= n; }); avail -= n; }
-  void release(int n) { n = std::min(n, total); { std::lock_guard<std::mutex> lk(mu); avail += n; } cv.notify_all(); }
-  // as many of the n wanted as are free right now (at least 1: the caller's own thread), without waiting and without overdrawing:
-  // for phases that are worth spreading only when the machine is otherwise idle (the last, largest partition of a stage)
-  // (the partitions that are running right now each keep a core busy themselves: `others`)
-  int take_free(int n, int others) { std::lock_guard<std::mutex> lk(mu); const int got = std::max(1, std::min(n, avail - others)); avail -= got; return got; }
-};
-static std::atomic<int> g_partitions_running{0};      // partitions inside mbgraph_run_impl right now
-static ThreadBudget g_host_threads;
-struct BudgetGuard {
-  int n; double waited;
-  explicit BudgetGuard(int k) : n(k) {
-    auto t0 = std::chrono::steady_clock::now();
-    g_host_threads.acquire(n);
-    waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  }
-  ~BudgetGuard() { g_host_threads.release(n); }
-};
-
-// a context of its own (same device, own stream) for every graph thread: shn_thread_ctx (core.hip)
-
-// eight 2-bit codes (one per byte, all < 4) -> their letters: 'A' + 2 b0 + 6 b1 + 11 (b0 & b1) = A, C, G, T (no carry leaves a byte)
-static inline uint64_t codes8_to_ascii(uint64_t x) {
-  const uint64_t b0 = x & 0x0101010101010101ULL, b1 = (x >> 1) & 0x0101010101010101ULL;
-  return 0x4141414141414141ULL + 2 * b0 + 6 * b1 + 11 * (b0 & b1);
-}
-static void decode_read(char* s, const uint8_t* p, uint64_t n, int enc, bool rc) {
-  if (enc == SHN_ENC_CODES) {
-    // eight bases at a time where all eight are ACGT (a byte >= 4 anywhere in the word: the word goes base by base)
-    uint64_t i = 0;
-    if (!rc) {
-      for (; i + 8 <= n; i += 8) {
-        uint64_t x; memcpy(&x, p + i, 8);
-        if (x & 0xFCFCFCFCFCFCFCFCULL) { for (uint64_t j = i; j < i + 8; j++) s[j] = p[j] < 4 ? "ACGT"[p[j]] : 'N'; continue; }
-        x = codes8_to_ascii(x); memcpy(s + i, &x, 8);
-      }
-      for (; i < n; i++) s[i] = p[i] < 4 ? "ACGT"[p[i]] : 'N';
-    } else {
-      for (; i + 8 <= n; i += 8) {
-        uint64_t x; memcpy(&x, p + n - 8 - i, 8);
-        if (x & 0xFCFCFCFCFCFCFCFCULL) { for (uint64_t j = i; j < i + 8; j++) { const uint8_t c = p[n - 1 - j]; s[j] = c < 4 ? "TGCA"[c] : 'N'; } continue; }
-        x = codes8_to_ascii(__builtin_bswap64(0x0303030303030303ULL - x)); memcpy(s + i, &x, 8);
-      }
-      for (; i < n; i++) { uint8_t c = p[n - 1 - i]; s[i] = c < 4 ? "TGCA"[c] : 'N'; }
-    }
-  } else {
-    auto up = [](uint8_t c) -> char { return (c >= 'a' && c <= 'z') ? (char)(c - 32) : (char)c; };
-    if (!rc) for (uint64_t i = 0; i < n; i++) s[i] = up(p[i]);
-    else for (uint64_t i = 0; i < n; i++) {
-      char c = up(p[n - 1 - i]);
-      s[i] = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c;
-    }
-  }
 }
 
 struct Graph {
@@ -166,84 +65,12 @@ struct Graph {
   std::vector<int> order;
   std::vector<int> es, ed, ew;
   std::vector<double> ecc;
-  // Lazy read text (reads named by rows of the host code matrices, shn_mbgraph_run_rows): nearly every read is settled on the
-  // device (distinct reads, bridging seeds, the in-node test of known_paths); the text of a read is decoded from its row the first
-  // time host code asks for it -- bridging hits, reads that run past their node: a few per cent of the reads.  Host code that reads
-  // text from several threads calls ensure_all_text() first.
-  const uint8_t *lz_a = nullptr, *lz_b = nullptr;
-  uint32_t lz_L = 0;
-  char* lz_buf = nullptr;
-  mutable std::vector<uint64_t> lz_done;
-  void decode_lazy(int r) const {
-    const uint8_t* p = ((origin_flag[r] & 1) ? lz_b : lz_a) + (uint64_t)origin_row[r] * lz_L;
-    decode_read(lz_buf + (size_t)r * lz_L, p, lz_L, SHN_ENC_CODES, (origin_flag[r] & 2) != 0);
-    // (several threads may ask for text at once -- the X-nodes of a bridging pass: two of them decoding one read write the same
-    // bytes; the bit is set after the text, with release / acquire order)
-    __atomic_fetch_or(&lz_done[(size_t)r >> 6], 1ULL << (r & 63), __ATOMIC_RELEASE);
-  }
-  bool lz_has(size_t r) const { return (__atomic_load_n(&lz_done[r >> 6], __ATOMIC_ACQUIRE) >> (r & 63)) & 1; }
-  void ensure_all_text() const {
-    if (!lz_buf) return;
-    const size_t n = n_rd();
-    const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(std::max(1, shn_host_cpus() / 2), n >> 16));
-    auto work = [&](size_t lo, size_t hi) {                       // (whole 64-read words per thread: the done bits are not shared)
-      for (size_t r = lo; r < hi; r++) if (!lz_has(r)) decode_lazy((int)r);
-    };
-    if (nt <= 1) { work(0, n); return; }
-    std::vector<std::thread> th;
-    const size_t words = (n + 63) / 64;
-    for (unsigned t = 0; t < nt; t++) th.emplace_back(work, std::min(n, words * t / nt * 64), std::min(n, words * (t + 1) / nt * 64));
-    for (auto& x : th) x.join();
-  }
-  RStr rstr(int r) const {
-    if (lz_buf) {
-      if (!lz_has((size_t)r)) decode_lazy(r);
-      return RStr{lz_buf + (size_t)r * lz_L, lz_L};
-    }
-    return RStr{rindex.data(r), rindex.len(r)};
-  }
-  // the text of read r is about to be asked for: its cache lines (or, not yet decoded, the lines of its row) on their way
-  void prefetch_read(int r) const {
-    if (lz_buf) {
-      if (!lz_has((size_t)r)) {
-        const uint8_t* p = ((origin_flag[r] & 1) ? lz_b : lz_a) + (uint64_t)origin_row[r] * lz_L;
-        __builtin_prefetch(p); __builtin_prefetch(p + 64);
-        return;
-      }
-      const char* t = lz_buf + (size_t)r * lz_L;
-      __builtin_prefetch(t); __builtin_prefetch(t + 64);
-      return;
-    }
-    __builtin_prefetch(rindex.data(r));
-  }
-  // device-resident read attributes (graph_dev.h): copies, mates, roles, known-path states stay on the device; the host vectors
-  // rcc / rmate / rmp / rfirst / rlast / rhas are then EMPTY until need_host_attrs() fetches them for a host form that wants them
-  shn_dedup* dd = nullptr;
+  PartitionReads reads;                    // the partition's reads: text, copies, mates, first / last nodes (mbgraph_reads.h)
   shn_kp* kp = nullptr;
-  bool dev_attrs = false;
-  size_t n_rd_dev = 0;
   std::vector<uint32_t> mate_cand;                  // (a, b) node pairs of find_mate_pairs' pass over the reads, made on the device
   bool mate_cand_ready = false;
   int attrs_rc = 0;                                 // a failed fetch of the host arrays (find_known_paths is void)
-  size_t n_rd() const { return dev_attrs || dd ? n_rd_dev : rindex.size(); }
-  int need_host_attrs() {
-    if (!dev_attrs) return 0;
-    const size_t nd = n_rd_dev;
-    std::vector<uint32_t> c(nd); std::vector<int32_t> m(nd); std::vector<uint8_t> ro(nd);
-    int rc = shn_dedup_attrs(dd, c.data(), m.data(), ro.data());
-    if (rc) return rc;
-    rcc.resize(nd); rmate.resize(nd); rmp.resize(nd); rfirst.assign(nd, -1); rlast.assign(nd, -1); rhas.assign(nd, 0);
-    for (size_t i = 0; i < nd; i++) { rcc[i] = (double)c[i]; rmate[i] = m[i]; rmp[i] = ro[i]; }
-    dev_attrs = false;
-    return 0;
-  }
-  void release_dev_attrs() { if (kp) { shn_kp_destroy(kp); kp = nullptr; } if (dd) { shn_dedup_destroy(dd); dd = nullptr; } }
-  ~Graph() { release_dev_attrs(); }
-  std::vector<double> rcc;
-  std::vector<int> rmate, rmp;        // rmp: 0 None, 1, 2
-  std::vector<int> rfirst, rlast;       // first / last node of the read's (last) path: all find_mate_pairs reads of Read.nodes
-  std::vector<char> rhas;
-  StringInterner rindex{1 << 16};
+  ~Graph() { if (kp) shn_kp_destroy(kp); }
   std::set<std::vector<int>> known_paths;
   std::map<std::pair<int, int>, double> known_edges;
   std::vector<int> bridged_log;
@@ -360,13 +187,6 @@ struct Graph {
     sg += "E";
     for (size_t e = 0; e < es.size(); e++) if (es[e] >= 0) { snprintf(buf, sizeof buf, " %d>%d", idx[es[e]], idx[ed[e]]); sg += buf; }
     return sg;
-  }
-  int add_read(const char* b, size_t n, uint64_t h) {
-    bool is_new = false;
-    int r = rindex.intern_hashed(b, n, h, &is_new);
-    if (!is_new) { rcc[r] += 1.0; return r; }
-    rcc.push_back(1.0); rmate.push_back(-1); rmp.push_back(0); rfirst.push_back(-1); rlast.push_back(-1); rhas.push_back(0);
-    return r;
   }
 
   // ---- condensing (mbgraph.py:184-271, 479-498, 1315-1321)
@@ -505,15 +325,14 @@ struct Graph {
   }
 
   // ---- bridging (mbgraph.py:77-111, 450-628)
-  size_t rlen(int r) const { return lz_buf ? (size_t)lz_L : rindex.len(r); }
   // a hit of the device's seed scan (the read holds the node's first K-mer at `index`, bit for bit): for a node that IS one K-mer --
   // nearly every X-node -- the text is matched already and what is left of read_bridges is its bounds, without a look at the read
   bool hit_bridges(int r, int n, int index) const {
-    if ((int)bases[n].size() == K) return index > 0 && (int)rlen(r) > index + K;
+    if ((int)bases[n].size() == K) return index > 0 && (int)reads.len(r) > index + K;
     return read_bridges(r, n, index);
   }
   bool read_bridges(int r, int n, int index) const {
-    const RStr rb = rstr(r); const std::string& nb = bases[n];
+    const RStr rb = reads.rstr(r); const std::string& nb = bases[n];
     if (index <= 0 || (int)rb.size() <= index + (int)nb.size()) return false;
     return rb.compare(index, nb.size(), nb) == 0;
   }
@@ -523,34 +342,23 @@ struct Graph {
     for (int j = 0; j < K; j++) { int c = base_code(s[pos + j]); if (c < 0) return false; key = (key << 2) | (uint64_t)c; }
     return true;
   }
-  int acgt_known = -1;        // set while the reads are loaded (a scan of the arena is 10s of ms at the read cap); -1 = scan
-  bool reads_all_acgt() {
-    if (acgt_known < 0) {
-      acgt_known = 1;
-      for (char c : rindex.arena) if (base_code(c) < 0) { acgt_known = 0; break; }
-    }
-    return acgt_known == 1;
-  }
   // device copy of the distinct reads + pattern table; returns false if the GPU path is not usable
   // the distinct reads on the device: rows of the resident input (device gather; 5 bytes per read cross the bus), else their text
   bool ensure_dreads(shn_reads** dreads) {
-    if (!ctx || n_rd() == 0 || !reads_all_acgt()) return false;
+    if (!ctx || reads.n_rd() == 0 || !reads.text_all_acgt()) return false;
     if (*dreads) return true;
-    if (src_a && dd && dd->n_distinct == n_rd()) return shn_reads_gather_dev(ctx, src_a, src_b, dd->d_row, dd->d_flag, n_rd(), dreads) == 0;
-    if (src_a && origin_row.size() == n_rd()) return shn_reads_gather(ctx, src_a, src_b, origin_row.data(), origin_flag.data(), n_rd(), dreads) == 0;
-    return shn_reads_create(ctx, (const uint8_t*)rindex.arena.data(), rindex.off.data(), n_rd(), 0, SHN_ENC_ASCII, dreads) == 0;
+    if (reads.src_a && reads.dd && reads.dd->n_distinct == reads.n_rd()) return shn_reads_gather_dev(ctx, reads.src_a, reads.src_b, reads.dd->d_row, reads.dd->d_flag, reads.n_rd(), dreads) == 0;
+    if (reads.src_a && reads.origin_row.size() == reads.n_rd()) return shn_reads_gather(ctx, reads.src_a, reads.src_b, reads.origin_row.data(), reads.origin_flag.data(), reads.n_rd(), dreads) == 0;
+    return shn_reads_create(ctx, (const uint8_t*)reads.rindex.arena.data(), reads.rindex.off.data(), reads.n_rd(), 0, SHN_ENC_ASCII, dreads) == 0;
   }
   bool gpu_patterns(const SeedIndex& si, shn_reads** dreads, shn_table** tab) {
-    if (!ctx || K > 32 || n_rd() == 0 || si.keys.empty() || !reads_all_acgt()) return false;
+    if (!ctx || K > 32 || reads.n_rd() == 0 || si.keys.empty() || !reads.text_all_acgt()) return false;
     if (!ensure_dreads(dreads)) return false;
     std::vector<uint32_t> vals(si.keys.size());
     for (size_t i = 0; i < vals.size(); i++) vals[i] = (uint32_t)i + 1;
     return shn_table_create(ctx, si.keys.data(), vals.data(), si.keys.size(), K, 0, tab) == 0;
   }
   shn_reads* d_reads = nullptr;
-  const shn_reads *src_a = nullptr, *src_b = nullptr;      // the resident input read sets the partition's reads are rows of
-  std::vector<uint32_t> origin_row;                        // per distinct read: row in its set, and
-  std::vector<uint8_t> origin_flag;                        // bit 0: set b, bit 1: reverse complement
   void release_gpu() { if (d_reads) { shn_reads_destroy(d_reads); d_reads = nullptr; } }
 
   void find_bridging_reads() {
@@ -587,30 +395,26 @@ struct Graph {
         // on one thread, with the other partitions long done): slices of the hit list in order, each thread's confirmed hits kept in
         // order and appended slice by slice, so every node's list is what the one-thread loop makes
         const unsigned want = nh >= 100000 ? (unsigned)std::min<uint64_t>(8, nh / 50000) : 1u;
-        const unsigned nt = want > 1 ? (unsigned)g_host_threads.take_free((int)want, g_partitions_running.load() - 1) : 1u;
-        struct GiveBackH { unsigned n; ~GiveBackH() { if (n) g_host_threads.release((int)n); } } give_back_h{want > 1 ? nt : 0u};
+        const FreeThreads free_threads(want);
+        const unsigned nt = free_threads.n;
         if (nt > 1) {
           std::vector<std::vector<std::pair<int, RI>>> found(nt);
-          auto slice = [&](unsigned t) {
+          run_on_threads(nt, [&](unsigned t) {
             std::vector<std::pair<int, RI>>& out = found[t];
             const uint64_t h0 = nh * t / nt, h1 = nh * (t + 1) / nt;
             for (uint64_t h = h0; h < h1; h++) {
-              if (h + 12 < h1) prefetch_read((int)hr[h + 12]);
+              if (h + 12 < h1) reads.prefetch_read((int)hr[h + 12]);
               for (uint32_t q = si.goff[hi[h]]; q < si.goff[hi[h] + 1]; q++) {
                 const int x = si.occ[q].first;
                 if (hit_bridges((int)hr[h], x, (int)hs[h])) out.push_back({x, RI((int)hr[h], (int)hs[h])});
               }
             }
-          };
-          std::vector<std::thread> th;
-          for (unsigned t = 1; t < nt; t++) th.emplace_back(slice, t);
-          slice(0);
-          for (auto& x : th) x.join();
+          });
           for (unsigned t = 0; t < nt; t++) for (const auto& xr : found[t]) nreads[xr.first].push_back(xr.second);
           return;
         }
         for (uint64_t h = 0; h < nh; h++) {
-          if (h + 12 < nh) prefetch_read((int)hr[h + 12]);
+          if (h + 12 < nh) reads.prefetch_read((int)hr[h + 12]);
           for (uint32_t q = si.goff[hi[h]]; q < si.goff[hi[h] + 1]; q++) {
             int x = si.occ[q].first;
             if (hit_bridges((int)hr[h], x, (int)hs[h])) nreads[x].push_back(RI((int)hr[h], (int)hs[h]));
@@ -620,8 +424,8 @@ struct Graph {
       }
     }
     const uint64_t mask = K == 32 ? ~0ULL : ((1ULL << (2 * K)) - 1);
-    for (int r = 0; r < (int)n_rd(); r++) {
-      const RStr rb = rstr(r);
+    for (int r = 0; r < (int)reads.n_rd(); r++) {
+      const RStr rb = reads.rstr(r);
       uint64_t key = 0;
       int valid = 0;
       for (int i = 0; i < (int)rb.size(); i++) {
@@ -659,11 +463,11 @@ struct Graph {
     rs.reserve(nreads[n].size());
     const std::vector<RI>& in_list = nreads[n];
     for (size_t q = 0; q < in_list.size(); q++) {
-      if (q + 8 < in_list.size()) prefetch_read(in_list[q + 8].first);
+      if (q + 8 < in_list.size()) reads.prefetch_read(in_list[q + 8].first);
       const RI& x = in_list[q];
       const int r = x.first, i = x.second;
       if (i <= 0) continue;
-      const RStr rb = rstr(r);
+      const RStr rb = reads.rstr(r);
       if ((int)rb.size() > i + lb && in_ch[(unsigned char)rb[i - 1]] && out_ch[(unsigned char)rb[i + lb]] && rb.compare(i, lb, nb) == 0) rs.push_back(x);
     }
     sort_runs(rs);
@@ -691,7 +495,7 @@ struct Graph {
     bool inb[256] = {false}, outb[256] = {false};                  // (the distinct characters before / behind the node in its reads)
     int n_in = 0, n_out = 0;
     for (const RI& x : nreads[n]) {
-      const RStr rb = rstr(x.first);
+      const RStr rb = reads.rstr(x.first);
       const unsigned char a = (unsigned char)rb[x.second - 1], b = (unsigned char)rb[x.second + lb];
       if (!inb[a]) { inb[a] = true; n_in++; }
       if (!outb[b]) { outb[b] = true; n_out++; }
@@ -728,10 +532,10 @@ struct Graph {
       // One pass over the reads for all the u-nodes (each gets the reads with its character, in list order).
       const std::vector<RI>& lst = nreads[node];
       for (size_t q = 0; q < lst.size(); q++) {
-        if (q + 8 < lst.size()) prefetch_read(lst[q + 8].first);
+        if (q + 8 < lst.size()) reads.prefetch_read(lst[q + 8].first);
         const RI& x = lst[q];
         if (x.second - 1 <= 0) continue;
-        const char c = rstr(x.first)[x.second - 1];
+        const char c = reads.rstr(x.first)[x.second - 1];
         for (int u : u_list) if (bases[u][0] == c) nreads[u].push_back(RI(x.first, x.second - 1));
       } }
     if (laps) { const double t = tnow(); t_bs_in += t - tb0; tb0 = t; }
@@ -762,9 +566,9 @@ struct Graph {
     for (size_t a = 0; a < u_list.size(); a++) u_ch[a] = (int)bases[u_list[a]].size() == lb + 1 ? bases[u_list[a]][0] : '\0';
     for (size_t a = 0; a < w_list.size(); a++) w_ch[a] = (int)bases[w_list[a]].size() == lb + 1 ? bases[w_list[a]][lb] : '\0';
     for (size_t q = 0; q < rl.size(); q++) {
-      if (q + 8 < rl.size()) prefetch_read(rl[q + 8].first);
+      if (q + 8 < rl.size()) reads.prefetch_read(rl[q + 8].first);
       const RI& y = rl[q];
-      const RStr rb = rstr(y.first);
+      const RStr rb = reads.rstr(y.first);
       int i = y.second;
       // exactly one u-node spelling the read from i - 1 and one w-node spelling it from i
       int u = -1, x = -1, nu = 0, nw = 0;
@@ -789,26 +593,24 @@ struct Graph {
     std::vector<int> all = u_list;
     all.insert(all.end(), w_list.begin(), w_list.end());
     for (int n : all) prev[n] = ((double)links[n] / (double)link_count) * prev[node];
-    const double tc0 = laps ? std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() : 0.0;
+    const double tc0 = laps ? tnow() : 0.0;
     for (int n : all) {
       std::vector<int> t = ine[n];
       t.insert(t.end(), oute[n].begin(), oute[n].end());
       for (int e : t) local_condense_edge(e);
     }
-    if (laps) t_condense += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - tc0;
+    if (laps) t_condense += tnow() - tc0;
     kill_node(node);
     return 0;
   }
   double t_condense = 0, t_refresh = 0, t_bs_in = 0, t_bs_out = 0, t_bs_rl = 0, t_cond_sort = 0;
   size_t n_refresh = 0, v_refresh = 0, v_bs = 0, v_cond = 0, n_steps = 0;
-  static double tnow() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
   int bridge_all() {
-    auto nowb = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t_ask = 0, t_step = 0;
     size_t n_ask = 0;
     while (true) {
       std::vector<int> todo;
-      double t0 = nowb();
+      double t0 = tnow();
       {
         // the X-nodes whose last answer does not stand any more: each one's question touches its own read list and memo only (and
         // read text, see decode_lazy), so they are asked on the host threads that are free right now -- late in the stage, when the
@@ -822,21 +624,16 @@ struct Graph {
         size_t work = 0;
         for (int n : stale) work += nreads[n].size();
         const unsigned want = work >= 50000 && stale.size() >= 8 ? (unsigned)std::min<size_t>(8, stale.size() / 4) : 1u;
-        const unsigned nt = want > 1 ? (unsigned)g_host_threads.take_free((int)want, g_partitions_running.load() - 1) : 1u;
-        struct GiveBackA { unsigned n; ~GiveBackA() { if (n) g_host_threads.release((int)n); } } give_back_a{want > 1 ? nt : 0u};
-        if (nt > 1) {
+        const FreeThreads free_threads(want);
+        if (free_threads.n > 1) {
           std::atomic<size_t> next{0};
-          auto ask = [&]() { for (size_t i; (i = next.fetch_add(1)) < stale.size();) (void)is_bridged_xnode(stale[i]); };
-          std::vector<std::thread> th;
-          for (unsigned t = 1; t < nt; t++) th.emplace_back(ask);
-          ask();
-          for (auto& x : th) x.join();
+          run_on_threads(free_threads.n, [&](unsigned) { for (size_t i; (i = next.fetch_add(1)) < stale.size();) (void)is_bridged_xnode(stale[i]); });
         }
       }
       for (int n : order) if (is_xnode(n)) { n_ask++; if (is_bridged_xnode(n)) todo.push_back(n); }
-      double t1 = nowb();
+      double t1 = tnow();
       for (int n : todo) { int rc = bridging_step(n); if (rc) return rc; }
-      t_ask += t1 - t0; t_step += nowb() - t1;
+      t_ask += t1 - t0; t_step += tnow() - t1;
       bridged_log.push_back((int)todo.size());
       remove_destroyed();
       if (todo.empty()) {
@@ -912,21 +709,19 @@ struct Graph {
   }
   void find_known_paths() {
     known_paths.clear();
-    const bool dbgk = laps;
-    auto nowk = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double tk0 = nowk(), tk1 = 0, tk2 = 0, tk3 = 0;
+    double tk0 = tnow(), tk1 = 0, tk2 = 0, tk3 = 0;
     const uint64_t mask = K == 32 ? ~0ULL : ((1ULL << (2 * K)) - 1);
     // ---- device path (kpaths_gpu.hip): every read is classified where the reads are; the host searches only the reads that run
     // past the end of the node they start in, against an index of just their first K-mers
     {
-      if (ctx && K <= 31 && shn_env_flag("SHN_GRAPH_KP_GPU", true) && n_rd() && ensure_dreads(&d_reads)) {
+      if (ctx && K <= 31 && shn_env_flag("SHN_GRAPH_KP_GPU", true) && reads.n_rd() && ensure_dreads(&d_reads)) {
         std::string nb;
         std::vector<uint64_t> noff(1, 0);
         { size_t tot = 0; for (int n : order) tot += bases[n].size(); nb.reserve(tot); noff.reserve(order.size() + 1); }
         for (int n : order) { nb += bases[n]; noff.push_back(nb.size()); }
-        std::vector<uint8_t> st(n_rd());
-        std::vector<int32_t> nd(n_rd());
-        std::vector<uint32_t> no(n_rd());
+        std::vector<uint8_t> st(reads.n_rd());
+        std::vector<int32_t> nd(reads.n_rd());
+        std::vector<uint32_t> no(reads.n_rd());
         // the out-edges of the nodes in list order, for the device's search of the reads that run past their first node (kp_search):
         // destination as an index into `order`, and the offset into the destination at which it continues the source
         std::vector<uint32_t> eoff(order.size() + 1, 0), edst, eov;
@@ -940,20 +735,20 @@ struct Graph {
           }
         }
         // room for the records [read, length, nodes ...] of the searched reads: a few words per read that runs on (4 % of the reads do)
-        std::vector<int32_t> precs(std::max<size_t>(1u << 16, n_rd() / 2 + 4096));
+        std::vector<int32_t> precs(std::max<size_t>(1u << 16, reads.n_rd() / 2 + 4096));
         uint64_t precs_used = 0;
-        tk1 = nowk();
-        if (dev_attrs) {
+        tk1 = tnow();
+        if (reads.dev_attrs) {
           // everything per read stays on the device: the host gets the reads left to search, the records of the reads searched
           // there and (below, after its own searches) the node pairs of find_mate_pairs
           std::vector<KpSlow> left;
           std::vector<int32_t> recs;
           std::vector<uint32_t> rec_cnt;
           if (kp) { shn_kp_destroy(kp); kp = nullptr; }
-          const int rcf = shn_known_paths_dev(ctx, d_reads, K, (const uint8_t*)nb.data(), noff.data(), order.size(), eoff.data(), edst.data(), eov.data(), dd, &left,
+          const int rcf = shn_known_paths_dev(ctx, d_reads, K, (const uint8_t*)nb.data(), noff.data(), order.size(), eoff.data(), edst.data(), eov.data(), reads.dd, &left,
                                               &recs, &rec_cnt, &kp);
           release_gpu();
-          tk2 = nowk();
+          tk2 = tnow();
           if (rcf == 0) {
             std::unordered_map<int, int> pos_in_order;
             FlatSum cnt_of(rec_cnt.size() / 2 + 16);                 // (a searched read's copies: every read has one entry)
@@ -982,7 +777,7 @@ struct Graph {
               at += 2 + (uint64_t)len;
               add_path(pth, cnt_of.get((uint64_t)(uint32_t)r));
             }
-            tk3 = nowk();
+            tk3 = tnow();
             // the reads the device left (a search deeper than its stack, no room for the records): the host's search, one by one
             std::vector<int32_t> patches;
             if (!left.empty()) {
@@ -990,7 +785,7 @@ struct Graph {
               std::sort(left.begin(), left.end(), [](const KpSlow& a, const KpSlow& b) { return a.read < b.read; });
               // occurrences (node, offset), in index order, of the first K-mers of the reads of state 2
               std::unordered_map<uint64_t, std::vector<std::pair<int, int>>> occ_of;
-              for (const KpSlow& sl : left) if (sl.state == 2) { uint64_t key; if (key_at(rstr((int)sl.read), 0, key)) occ_of[key]; }
+              for (const KpSlow& sl : left) if (sl.state == 2) { uint64_t key; if (key_at(reads.rstr((int)sl.read), 0, key)) occ_of[key]; }
               if (!occ_of.empty())
                 for (int n : order) {
                   const std::string& b = bases[n];
@@ -1008,7 +803,7 @@ struct Graph {
               static const std::vector<std::pair<int, int>> none;
               for (const KpSlow& sl : left) {
                 const int r = (int)sl.read;
-                const RStr rb = rstr(r);
+                const RStr rb = reads.rstr(r);
                 uint64_t key;
                 if (!key_at(rb, 0, key)) continue;
                 const std::vector<std::pair<int, int>>* occs = &one;
@@ -1030,21 +825,21 @@ struct Graph {
             n_known = cntp;
             // find_mate_pairs' pass over the reads, where their first / last nodes are (the graph does not change in between)
             mate_cand.clear();
-            mate_cand_ready = shn_kp_mate_pairs(kp, dd, patches.data(), patches.size() / 3, &mate_cand) == 0;
+            mate_cand_ready = shn_kp_mate_pairs(kp, reads.dd, patches.data(), patches.size() / 3, &mate_cand) == 0;
             if (mate_cand_ready) {
               for (uint32_t& x : mate_cand) x = (uint32_t)order[x];
               shn_kp_destroy(kp); kp = nullptr;
-              if (dbgk) fprintf(stderr, "[mbgraph]   kp (device, resident) node text %.3f s scan + search %.3f s records %.3f s left to the host + mate pairs %.3f s  (%zu bases, %zu reads, %zu with records, %zu left, %zu node pairs)\n",
-                                tk1 - tk0, tk2 - tk1, tk3 - tk2, nowk() - tk3, nb.size(), n_rd(), rec_cnt.size() / 2, left.size(), mate_cand.size() / 2);
+              if (laps) fprintf(stderr, "[mbgraph]   kp (device, resident) node text %.3f s scan + search %.3f s records %.3f s left to the host + mate pairs %.3f s  (%zu bases, %zu reads, %zu with records, %zu left, %zu node pairs)\n",
+                                tk1 - tk0, tk2 - tk1, tk3 - tk2, tnow() - tk3, nb.size(), reads.n_rd(), rec_cnt.size() / 2, left.size(), mate_cand.size() / 2);
               return;
             }
             // (the pairs could not be made on the device: the host's pass needs first / last per read -- start over with host arrays)
             known_paths.clear(); known_edges.clear(); n_known = 0;
           }
           if (kp) { shn_kp_destroy(kp); kp = nullptr; }
-          if ((attrs_rc = need_host_attrs())) return;
+          if ((attrs_rc = reads.need_host_attrs())) return;
           if (!ensure_dreads(&d_reads)) { attrs_rc = shn_fail(SHN_ERR_INTERNAL, "find_known_paths: the distinct reads could not be gathered again"); return; }
-          tk1 = nowk();
+          tk1 = tnow();
         }
         const bool kp_dev_search = shn_env_flag("SHN_GRAPH_KP_SEARCH", true);
         const int rcs = kp_dev_search
@@ -1052,7 +847,7 @@ struct Graph {
                                      nd.data(), no.data(), precs.data(), precs.size(), &precs_used)
             : shn_known_paths_scan(ctx, d_reads, K, (const uint8_t*)nb.data(), noff.data(), order.size(), st.data(), nd.data(), no.data());
         release_gpu();
-        tk2 = nowk();
+        tk2 = tnow();
         if (rcs == 0) {
           // occurrences (node, offset), in index order, of the first K-mers of the reads left to search whose K-mer occurs more
           // than once (state 2: none in most partitions -- the K-mers of a de Bruijn graph are distinct until bridging copies nodes)
@@ -1061,34 +856,28 @@ struct Graph {
           size_t n_slow = 0, n_multi = 0;
           {
             // the reads inside one node get that node as first / last (a pass over every read: on the threads that are free right now)
-            const size_t nr = n_rd();
+            const size_t nr = reads.n_rd();
             const unsigned want0 = (unsigned)std::max<size_t>(1, std::min<size_t>(8, nr >> 19));
-            const unsigned nt0 = want0 > 1 ? (unsigned)g_host_threads.take_free((int)want0, g_partitions_running.load() - 1) : 1u;
-            struct GiveBack0 { unsigned n; ~GiveBack0() { if (n) g_host_threads.release((int)n); } } give_back0{want0 > 1 ? nt0 : 0u};
+            const FreeThreads free_threads(want0);
+            const unsigned nt0 = free_threads.n;
             std::vector<size_t> slow_of(nt0, 0);
             std::vector<std::vector<uint32_t>> multi_of(nt0);
-            auto settle = [&](unsigned t, size_t lo, size_t hi) {
+            run_on_threads(nt0, [&](unsigned t) {
               size_t ns = 0;
-              for (size_t r = lo; r < hi; r++) {
+              for (size_t r = nr * t / nt0; r < nr * (t + 1) / nt0; r++) {
                 const uint8_t v = st[r];
-                if (v == 1) { const int n = order[nd[r]]; rfirst[r] = n; rlast[r] = n; rhas[r] = 1; }
+                if (v == 1) { const int n = order[nd[r]]; reads.rfirst[r] = n; reads.rlast[r] = n; reads.rhas[r] = 1; }
                 else if (v == 3) ns++;
                 else if (v == 2) { ns++; multi_of[t].push_back((uint32_t)r); }
               }
               slow_of[t] = ns;
-            };
-            if (nt0 <= 1) settle(0, 0, nr);
-            else {
-              std::vector<std::thread> th;
-              for (unsigned t = 0; t < nt0; t++) th.emplace_back(settle, t, nr * t / nt0, nr * (t + 1) / nt0);
-              for (auto& x : th) x.join();
-            }
+            });
             for (unsigned t = 0; t < nt0; t++) {
               n_slow += slow_of[t];
               for (uint32_t r : multi_of[t]) {
                 uint64_t key;
                 n_multi++;
-                if (key_at(rstr((int)r), 0, key)) { occ_of[key]; const uint64_t h = fm_mix(key) >> 46; bits[h >> 6] |= 1ULL << (h & 63); }
+                if (key_at(reads.rstr((int)r), 0, key)) { occ_of[key]; const uint64_t h = fm_mix(key) >> 46; bits[h >> 6] |= 1ULL << (h & 63); }
               }
             }
           }
@@ -1105,7 +894,7 @@ struct Graph {
                 if (it != occ_of.end()) it->second.push_back({n, i - K + 1});
               }
             }
-          tk3 = nowk();
+          tk3 = tnow();
           // The reads left to search, on host threads (slices of whole 64-read words: the lazily decoded text keeps one done bit per
           // read).  Per thread: the sums per edge and the paths seen go through hash tables while the reads go by (10^5 reads of a highly
           // expressed transcript name the same few edges and paths) and are merged afterwards; the copy counts of reads are whole
@@ -1123,7 +912,7 @@ struct Graph {
             static const std::vector<std::pair<int, int>> none;
             for (size_t r = lo; r < hi; r++) {
               if (st[r] < 2 || st[r] == 4) continue;            // (4: searched on the device, its paths come in the records)
-              const RStr rb = rstr((int)r);
+              const RStr rb = reads.rstr((int)r);
               uint64_t key;
               if (!key_at(rb, 0, key)) continue;
               const std::vector<std::pair<int, int>>* occs = &one;
@@ -1132,12 +921,12 @@ struct Graph {
               for (const auto& oc : *occs) {
                 const int sn = oc.first, so = oc.second;
                 if (!compare(rb, 0, bases[sn], so)) continue;
-                if (rb.size() <= bases[sn].size() - (size_t)so) { rfirst[r] = sn; rlast[r] = sn; rhas[r] = 1; continue; }
+                if (rb.size() <= bases[sn].size() - (size_t)so) { reads.rfirst[r] = sn; reads.rlast[r] = sn; reads.rhas[r] = 1; continue; }
                 paths.clear(); cur.clear();
                 search_sequence(rb, 0, sn, so, 30, cur, paths);
                 for (auto& p : paths) {
-                  rfirst[r] = p.front(); rlast[r] = p.back(); rhas[r] = 1;
-                  for (size_t j = 0; j + 1 < p.size(); j++) L.edge_sum.add(((uint64_t)(uint32_t)p[j] << 32) | (uint32_t)p[j + 1], rcc[r]);
+                  reads.rfirst[r] = p.front(); reads.rlast[r] = p.back(); reads.rhas[r] = 1;
+                  for (size_t j = 0; j + 1 < p.size(); j++) L.edge_sum.add(((uint64_t)(uint32_t)p[j] << 32) | (uint32_t)p[j + 1], reads.rcc[r]);
                   if (p.size() > 2) {
                     L.cntp++;
                     uint64_t h = 0xcbf29ce484222325ULL;
@@ -1151,18 +940,12 @@ struct Graph {
               }
             }
           };
-          const size_t words = (n_rd() + 63) / 64;
           const unsigned want = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(16, std::max(1, shn_host_cpus())), n_slow >> 12));
-          const unsigned nts = want > 1 ? (unsigned)g_host_threads.take_free((int)want, g_partitions_running.load() - 1) : 1u;      // (what is free right now: no waiting, no overdraft)
-          struct GiveBack { unsigned n; ~GiveBack() { if (n) g_host_threads.release((int)n); } } give_back{want > 1 ? nts : 0u};
+          const FreeThreads free_threads(want);                              // (what is free right now: no waiting, no overdraft)
+          const unsigned nts = free_threads.n;
+          const size_t nr = reads.n_rd(), words = (nr + 63) / 64;
           std::vector<Local> locals(nts);
-          if (nts <= 1) search_slice(0, n_rd(), locals[0]);
-          else {
-            std::vector<std::thread> th;
-            for (unsigned t = 0; t < nts; t++)
-              th.emplace_back(search_slice, std::min(n_rd(), words * t / nts * 64), std::min(n_rd(), words * (t + 1) / nts * 64), std::ref(locals[t]));
-            for (auto& x : th) x.join();
-          }
+          run_on_threads(nts, [&](unsigned t) { search_slice(std::min(nr, words * t / nts * 64), std::min(nr, words * (t + 1) / nts * 64), locals[t]); });
           int cntp = 0;
           for (Local& L : locals) {
             cntp += L.cntp;
@@ -1181,8 +964,8 @@ struct Graph {
               pth.resize((size_t)len);
               for (int32_t j = 0; j < len; j++) pth[(size_t)j] = order[(size_t)precs[at + 2 + (uint64_t)j]];
               at += 2 + (uint64_t)len;
-              rfirst[r] = pth.front(); rlast[r] = pth.back(); rhas[r] = 1;
-              for (size_t j = 0; j + 1 < pth.size(); j++) edge_sum.add(((uint64_t)(uint32_t)pth[j] << 32) | (uint32_t)pth[j + 1], rcc[r]);
+              reads.rfirst[r] = pth.front(); reads.rlast[r] = pth.back(); reads.rhas[r] = 1;
+              for (size_t j = 0; j + 1 < pth.size(); j++) edge_sum.add(((uint64_t)(uint32_t)pth[j] << 32) | (uint32_t)pth[j + 1], reads.rcc[r]);
               if (pth.size() > 2) {
                 cntp++;
                 // (the 10^4-10^5 reads of a highly expressed transcript name the same few paths: a hash table in front of the ordered set)
@@ -1197,14 +980,14 @@ struct Graph {
             edge_sum.each([&](uint64_t k, double v) { known_edges[{(int)(uint32_t)(k >> 32), (int)(uint32_t)k}] += v; });
           }
           n_known = cntp;
-          if (dbgk) fprintf(stderr, "[mbgraph]   kp (device) node text %.3f s scan %.3f s slow index %.3f s search %.3f s  (%zu bases, %zu reads, %zu slow)\n", tk1 - tk0,
-                            tk2 - tk1, tk3 - tk2, nowk() - tk3, nb.size(), n_rd(), n_slow);
+          if (laps) fprintf(stderr, "[mbgraph]   kp (device) node text %.3f s scan %.3f s slow index %.3f s search %.3f s  (%zu bases, %zu reads, %zu slow)\n", tk1 - tk0,
+                            tk2 - tk1, tk3 - tk2, tnow() - tk3, nb.size(), reads.n_rd(), n_slow);
           return;
         }
       } }
-    tk0 = nowk();
-    if ((attrs_rc = need_host_attrs())) return;          // (the host form works on per-read arrays of its own)
-    ensure_all_text();                                   // (the host form reads every read's text, on several threads)
+    tk0 = tnow();
+    if ((attrs_rc = reads.need_host_attrs())) return;          // (the host form works on per-read arrays of its own)
+    reads.ensure_all_text();                                   // (the host form reads every read's text, on several threads)
     std::vector<std::pair<uint64_t, std::pair<int, int>>> items;
     for (int n : order) {
       const std::string& b = bases[n];
@@ -1219,10 +1002,10 @@ struct Graph {
     }
     SeedIndex si;
     si.build(items);
-    std::vector<uint32_t> first(n_rd(), 0), last(n_rd(), 0);     // group id + 1, 0 = absent
+    std::vector<uint32_t> first(reads.n_rd(), 0), last(reads.n_rd(), 0);     // group id + 1, 0 = absent
     shn_table* tab = nullptr;
     bool done = false;
-    tk1 = nowk();
+    tk1 = tnow();
     {
       if (gpu_patterns(si, &d_reads, &tab)) {
         done = shn_seed_ends(ctx, d_reads, K, tab, first.data(), last.data()) == 0;
@@ -1230,28 +1013,28 @@ struct Graph {
       }
     }
     if (!done)
-      for (int r = 0; r < (int)n_rd(); r++) {
-        const RStr rb = rstr(r);
+      for (int r = 0; r < (int)reads.n_rd(); r++) {
+        const RStr rb = reads.rstr(r);
         uint64_t key;
         if ((int)rb.size() < K) continue;
         if (key_at(rb, 0, key)) first[r] = (uint32_t)(si.find(key) + 1);
         if (key_at(rb, rb.size() - K, key)) last[r] = (uint32_t)(si.find(key) + 1);
       }
     release_gpu();
-    tk2 = nowk();
+    tk2 = tnow();
     int cntp = 0;
     std::vector<std::vector<int>> paths;
     std::vector<int> cur;
     // Nearly every read lies inside one node: its only path is that node, it adds no known edge and no known path.  Those reads
     // are settled on host threads; the reads that cross node boundaries (`slow`) go through search_sequence one after the
     // other in read order, as the sums of known_edges require.
-    std::vector<char> slow(n_rd(), 0);
+    std::vector<char> slow(reads.n_rd(), 0);
     {
-      const unsigned ntp = (unsigned)std::min<size_t>(std::min<size_t>(16, std::max(1, shn_host_cpus() / 2)), std::max<size_t>(1, n_rd() >> 18));
+      const unsigned ntp = (unsigned)std::min<size_t>(std::min<size_t>(16, std::max(1, shn_host_cpus() / 2)), std::max<size_t>(1, reads.n_rd() >> 18));
       auto classify = [&](size_t lo, size_t hi) {
         for (size_t r = lo; r < hi; r++) {
           if (!first[r] || !last[r]) continue;
-          const RStr rb = rstr((int)r);
+          const RStr rb = reads.rstr((int)r);
           const uint32_t gi = first[r] - 1;
           int fn = -1;
           bool any = false, need = false;
@@ -1262,44 +1045,39 @@ struct Graph {
             else need = true;
           }
           if (need) slow[r] = 1;
-          else if (any) { rfirst[r] = fn; rlast[r] = fn; rhas[r] = 1; }
+          else if (any) { reads.rfirst[r] = fn; reads.rlast[r] = fn; reads.rhas[r] = 1; }
         }
       };
       BudgetGuard budget((int)ntp);
-      if (ntp <= 1) classify(0, n_rd());
-      else {
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < ntp; t++) th.emplace_back(classify, n_rd() * t / ntp, n_rd() * (t + 1) / ntp);
-        for (auto& x : th) x.join();
-      }
+      run_on_threads(ntp, reads.n_rd(), classify);
     }
-    tk3 = nowk();
+    tk3 = tnow();
     size_t n_slow = 0;
-    for (int r = 0; r < (int)n_rd(); r++) {
+    for (int r = 0; r < (int)reads.n_rd(); r++) {
       if (!slow[r]) continue;
       n_slow++;
-      const RStr rb = rstr(r);
+      const RStr rb = reads.rstr(r);
       uint32_t gi = first[r] - 1;
       for (uint32_t q = si.goff[gi]; q < si.goff[gi + 1]; q++) {
         int sn = si.occ[q].first, so = si.occ[q].second;
         if (!compare(rb, 0, bases[sn], so)) continue;
         if (rb.size() <= bases[sn].size() - (size_t)so) {
           // the read lies inside this node (nearly all reads do): its only path is [sn] -- no edges, no known path
-          rfirst[r] = sn; rlast[r] = sn; rhas[r] = 1;
+          reads.rfirst[r] = sn; reads.rlast[r] = sn; reads.rhas[r] = 1;
           continue;
         }
         paths.clear(); cur.clear();
         search_sequence(rb, 0, sn, so, 30, cur, paths);
         for (auto& p : paths) {
-          rfirst[r] = p.front(); rlast[r] = p.back(); rhas[r] = 1;
-          for (size_t j = 0; j + 1 < p.size(); j++) known_edges[{p[j], p[j + 1]}] += rcc[r];
+          reads.rfirst[r] = p.front(); reads.rlast[r] = p.back(); reads.rhas[r] = 1;
+          for (size_t j = 0; j + 1 < p.size(); j++) known_edges[{p[j], p[j + 1]}] += reads.rcc[r];
           if (p.size() > 2) { known_paths.insert(p); cntp++; }
         }
       }
     }
     n_known = cntp;
-    if (dbgk) fprintf(stderr, "[mbgraph]   kp index %.3f s gpu %.3f s classify %.3f s slow %.3f s  (%zu patterns, %zu reads, %zu slow)\n", tk1 - tk0, tk2 - tk1, tk3 - tk2,
-                      nowk() - tk3, items.size(), n_rd(), n_slow);
+    if (laps) fprintf(stderr, "[mbgraph]   kp index %.3f s gpu %.3f s classify %.3f s slow %.3f s  (%zu patterns, %zu reads, %zu slow)\n", tk1 - tk0, tk2 - tk1, tk3 - tk2,
+                      tnow() - tk3, items.size(), reads.n_rd(), n_slow);
   }
   void find_copy_counts() {
     for (int n : order) {
@@ -1329,16 +1107,16 @@ struct Graph {
   void find_mate_pairs() {
     std::vector<std::pair<int, int>> pairs;
     std::set<std::pair<int, int>> seen;
-    if (dev_attrs && mate_cand_ready) {
+    if (reads.dev_attrs && mate_cand_ready) {
       // (made on the device right after the known-paths search, kpaths_gpu.hip: distinct (a, b), not adjacent, in no particular
       // order -- the loop below only counts and fills a set)
       for (size_t i = 0; i + 1 < mate_cand.size(); i += 2) if (seen.insert({(int)mate_cand[i], (int)mate_cand[i + 1]}).second) pairs.push_back({(int)mate_cand[i], (int)mate_cand[i + 1]});
     } else
-    for (int r = 0; r < (int)n_rd(); r++) {
-      if (rmp[r] != 1 || rmate[r] < 0) continue;
-      int m = rmate[r];
-      if (!rhas[r] || !rhas[m]) continue;
-      int a = rlast[r], b = rfirst[m];
+    for (int r = 0; r < (int)reads.n_rd(); r++) {
+      if (reads.rmp[r] != 1 || reads.rmate[r] < 0) continue;
+      int m = reads.rmate[r];
+      if (!reads.rhas[r] || !reads.rhas[m]) continue;
+      int a = reads.rlast[r], b = reads.rfirst[m];
       if (a == b) continue;
       bool adj = false;
       for (int e : oute[a]) if (ed[e] == b) adj = true;
@@ -1360,10 +1138,8 @@ struct Graph {
   }
 
   int run() {
-    const bool dbg = laps;
-    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t0 = now();
-    auto lap = [&](const char* what) { if (dbg) { double t = now(); fprintf(stderr, "[mbgraph] %-22s %8.3f s  nodes=%zu reads=%zu\n", what, t - t0, order.size(), n_rd()); t0 = t; } };
+    double t0 = tnow();
+    auto lap = [&](const char* what) { const double t = tnow(); lap_line(laps, what, t - t0, "nodes=%zu reads=%zu", order.size(), reads.n_rd()); t0 = t; };
     if (!precondensed) condense_all();
     nodes_after[0] = (int)order.size();
     lap("condense_all");
@@ -1392,7 +1168,7 @@ struct Graph {
     if (attrs_rc) return attrs_rc;
     lap("find_known_paths");
     find_copy_counts();
-    if (dev_attrs && !mate_cand_ready && (rc = need_host_attrs())) return rc;
+    if (reads.dev_attrs && !mate_cand_ready && (rc = reads.need_host_attrs())) return rc;
     find_mate_pairs();
     lap("copy counts+mates");
     final_nodes = (int)order.size();
@@ -1405,487 +1181,46 @@ struct Graph {
 extern "C" void shn_graph_destroy(shn_graph* g) { delete g; }
 int shn_graph_partitions_running() { return g_partitions_running.load(); }      // (sflow_host.hip: how many cores a sparse-flow call beside the graph stage may take)
 
-// rows: n_rows k1-mers of K+1 bytes each (file order of component{c}k1mers_allowed.dict); reads: ASCII,
-// r_off[n_reads+1]; paired: second mate file r2/r2_off with the same count.  Read.L = length of the first read.
-// enc: SHN_ENC_ASCII or SHN_ENC_CODES (0..3); rc1/rc2 (optional, one byte per read): 1 = take the reverse
-// complement of that read (the strand-doubled view of the packed input, shannon.py:396-424)
+// ---- what the entry points hand the driver: the partition's K-mer graph (KmerGraphSource) and its reads (ReadSource, mbgraph_reads.h)
+// rows: n_rows k1-mers of K+1 bytes each (file order of component{c}k1mers_allowed.dict), and / or the partition's K-mer graph
+// already contracted on the GPU (shn_unitigs_build, partition `part` of `ug`).  With ug the rows are needed when the partition holds
+// a cycle of condensable edges (left to the sequential code) and for the development check SHN_GRAPH_CHECK=1 (both ways, compared).
+struct KmerGraphSource { const uint8_t* rows = nullptr; uint64_t n_rows = 0; const shn_unitigs* ug = nullptr; uint32_t part = 0; };
 
-static int mbgraph_run_impl(shn_ctx* ctx, int K, const uint8_t* rows, uint64_t n_rows, const shn_unitigs* ug, uint32_t part, const uint8_t* r1,
-                           const uint64_t* r1_off, const uint8_t* r2, const uint64_t* r2_off, uint64_t n_reads, int paired, int enc,
-                           const uint8_t* rc1, const uint8_t* rc2, shn_graph** out, const shn_reads* src_a = nullptr, const shn_reads* src_b = nullptr,
-                           const uint32_t* didx = nullptr, const uint8_t* host_a = nullptr, const uint8_t* host_b = nullptr, const uint32_t* d_didx = nullptr);
-extern "C" int shn_reads_dedup(shn_ctx* ctx, const shn_reads* a, const shn_reads* b, const uint32_t* didx, uint64_t n, int paired,
-                               uint64_t* n_distinct, uint32_t* slot_out, uint32_t* count_out, int32_t* mate_out, uint8_t* role_out);
-
-
-extern "C" int shn_mbgraph_run(shn_ctx* ctx, int K, const uint8_t* rows, uint64_t n_rows, const uint8_t* r1, const uint64_t* r1_off,
-                               const uint8_t* r2, const uint64_t* r2_off, uint64_t n_reads, int paired, int enc, const uint8_t* rc1,
-                               const uint8_t* rc2, shn_graph** out) {
-  return mbgraph_run_impl(ctx, K, rows, n_rows, nullptr, 0, r1, r1_off, r2, r2_off, n_reads, paired, enc, rc1, rc2, out);
-}
-// The same with the partition's K-mer graph already contracted on the GPU (shn_unitigs_build, partition `part` of `ug`).
-// rows / n_rows (optional): the partition's k1-mers as for shn_mbgraph_run -- needed when the partition holds a cycle of
-// condensable edges (left to the sequential code) and for the development check SHN_GRAPH_CHECK=1 (both ways, compared).
-extern "C" int shn_mbgraph_run_unitigs(shn_ctx* ctx, const shn_unitigs* ug, uint32_t part, const uint8_t* rows, uint64_t n_rows, const uint8_t* r1,
-                                       const uint64_t* r1_off, const uint8_t* r2, const uint64_t* r2_off, uint64_t n_reads, int paired, int enc,
-                                       const uint8_t* rc1, const uint8_t* rc2, shn_graph** out) {
-  if (!ug || part >= ug->n_parts) return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run_unitigs: bad unitigs / partition");
-  return mbgraph_run_impl(ctx, ug->K, rows, n_rows, ug, part, r1, r1_off, r2, r2_off, n_reads, paired, enc, rc1, rc2, out);
-}
-
-// The same again with the partition's reads known as rows of the resident input: src_a / src_b = the packed read sets of the run
-// (src_b NULL for single-end), didx[i] = doubled read index of read i (shn_route_reads' numbering: SE d < N -> R[d], d >= N ->
-// RC(R[d-N]); PE d < N -> (R1[d], RC(R1[d])), d >= N -> (RC(R2[d-N]), R2[d-N])).  The read text (r1 / r2) is still what the host
-// side of the stage works on; the device copy of the distinct reads is gathered from the resident sets instead of uploaded.
-extern "C" int shn_mbgraph_run_resident(shn_ctx* ctx, const shn_unitigs* ug, uint32_t part, const uint8_t* rows, uint64_t n_rows, const shn_reads* src_a,
-                                        const shn_reads* src_b, const uint32_t* didx, const uint8_t* r1, const uint64_t* r1_off, const uint8_t* r2,
-                                        const uint64_t* r2_off, uint64_t n_reads, int paired, int enc, const uint8_t* rc1, const uint8_t* rc2,
-                                        shn_graph** out) {
-  if (!ug || part >= ug->n_parts) return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run_resident: bad unitigs / partition");
-  return mbgraph_run_impl(ctx, ug->K, rows, n_rows, ug, part, r1, r1_off, r2, r2_off, n_reads, paired, enc, rc1, rc2, out, src_a, src_b, didx);
-}
-
-// The partition's reads named only by their rows: host_a / host_b = the run's reads as host code matrices (uint8 codes 0-3,
-// [n_reads of the set][read length], the same reads as src_a / src_b hold packed on the device), didx as above.  The distinct
-// reads are found on the device (shn_reads_dedup) and only their text is decoded on the host, straight from the matrices: no
-// per-partition copy of the routed reads exists anywhere.
-static int mbgraph_run_rows_impl(shn_ctx* ctx, const shn_unitigs* ug, uint32_t part, const uint8_t* rows, uint64_t n_rows, const shn_reads* src_a,
-                                 const shn_reads* src_b, const uint8_t* host_a, const uint8_t* host_b, const uint32_t* didx, const uint32_t* d_didx,
-                                 uint64_t n_reads, int paired, shn_graph** out) {
-  if (!ug || part >= ug->n_parts) return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run_rows: bad unitigs / partition");
-  if (!ctx || !src_a || !host_a || (n_reads && !didx && !d_didx) || (paired && (!src_b || !host_b)) || !src_a->fixed_len ||
-      (paired && src_b->fixed_len != src_a->fixed_len))
-    return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run_rows: needs a context, fixed-length resident read sets and their host matrices");
-  const bool dbg = shn_env_set("SHN_GRAPH_LAPS") && n_reads >= shn_env_u64("SHN_GRAPH_LAPS", 0);
-  const double t0 = dbg ? Graph::tnow() : 0.0;
-  const int rc = mbgraph_run_impl(ctx, ug->K, rows, n_rows, ug, part, nullptr, nullptr, nullptr, nullptr, n_reads, paired, SHN_ENC_CODES, nullptr, nullptr, out,
-                                  src_a, src_b, didx, host_a, host_b, d_didx);
-  if (dbg) fprintf(stderr, "[mbgraph] the call (partition %u), its clean-up included %8.3f s\n", part, Graph::tnow() - t0);
-  return rc;
-}
-extern "C" int shn_mbgraph_run_rows(shn_ctx* ctx, const shn_unitigs* ug, uint32_t part, const uint8_t* rows, uint64_t n_rows, const shn_reads* src_a,
-                                    const shn_reads* src_b, const uint8_t* host_a, const uint8_t* host_b, const uint32_t* didx, uint64_t n_reads,
-                                    int paired, shn_graph** out) {
-  return mbgraph_run_rows_impl(ctx, ug, part, rows, n_rows, src_a, src_b, host_a, host_b, didx, nullptr, n_reads, paired, out);
-}
-// The same with the partition's routed reads named a second time by where they already lie on the device: entries [route_lo,
-// route_lo + n_reads) of the routes shn_route_reads left there (didx = the same indices on the host) -- the duplicate search then
-// reads them in place instead of uploading the list again (0.5 GB per step at BASELINE configs[2], in 111 pieces).
-extern "C" int shn_mbgraph_run_routes(shn_ctx* ctx, const shn_unitigs* ug, uint32_t part, const uint8_t* rows, uint64_t n_rows, const shn_reads* src_a,
-                                      const shn_reads* src_b, const uint8_t* host_a, const uint8_t* host_b, const uint32_t* didx, const shn_routes* routes,
-                                      uint64_t route_lo, uint64_t n_reads, int paired, shn_graph** out) {
-  if (!routes) return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run_routes: routes is NULL");
-  const uint32_t* d = nullptr;
-  int rc = shn_routes_device_slice(routes, route_lo, n_reads, &d);
-  if (rc) return rc;
-  return mbgraph_run_rows_impl(ctx, ug, part, rows, n_rows, src_a, src_b, host_a, host_b, didx, d, n_reads, paired, out);
-}
-
-static int mbgraph_run_impl(shn_ctx* ctx, int K, const uint8_t* rows, uint64_t n_rows, const shn_unitigs* ug, uint32_t part, const uint8_t* r1,
-                           const uint64_t* r1_off, const uint8_t* r2, const uint64_t* r2_off, uint64_t n_reads, int paired, int enc,
-                           const uint8_t* rc1, const uint8_t* rc2, shn_graph** out, const shn_reads* src_a, const shn_reads* src_b,
-                           const uint32_t* didx, const uint8_t* host_a, const uint8_t* host_b, const uint32_t* d_didx) {
-  if (!out || (n_rows && !rows) || (!host_a && ((n_reads && (!r1 || !r1_off)) || (paired && n_reads && (!r2 || !r2_off)))))
-    return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run: NULL argument");
-  struct Running { Running() { g_partitions_running.fetch_add(1); } ~Running() { g_partitions_running.fetch_sub(1); } } running;
-  Graph g;
-  g.ctx = shn_thread_ctx(ctx);
-  g.K = K;
-  const uint64_t read_len0 = !n_reads ? 0 : host_a ? src_a->fixed_len : (uint64_t)(r1_off[1] - r1_off[0]);
-  g.L = n_reads ? (int)read_len0 : -1;
-  g.SIZE_THRESHOLD = g.L;
-  // SHN_DEBUG: the laps of every partition; SHN_GRAPH_LAPS=n: of the partitions with at least n routed reads
-  const bool dbg = shn_env_set("SHN_DEBUG") || (shn_env_set("SHN_GRAPH_LAPS") && n_reads >= shn_env_u64("SHN_GRAPH_LAPS", 0));
-  g.laps = dbg;
-  auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double tt = now();
-  // origin of read slot j = i * nm + mate (mate 0 / 1) in the resident input, for the device gather of the distinct reads
-  // (the routed list may be given by its place on the device only: a form that wants it on the host fetches it first)
-  std::vector<uint32_t> didx_fetched;
-  auto need_didx = [&]() -> int {
-    if (didx || !d_didx || !n_reads) return 0;
-    didx_fetched.resize(n_reads);
-    hipError_t e_ = hipSetDevice(ctx->device);
-    if (e_ == hipSuccess) e_ = hipMemcpy(didx_fetched.data(), d_didx, n_reads * 4, hipMemcpyDeviceToHost);
-    if (e_ != hipSuccess) return shn_fail(SHN_ERR_HIP, std::string("shn_mbgraph_run_routes: ") + hipGetErrorString(e_));
-    didx = didx_fetched.data();
-    return 0;
-  };
-  const bool resident = ctx && src_a && (didx || d_didx) && src_a->fixed_len && (!paired || (src_b && src_b->fixed_len == src_a->fixed_len)) &&
-                        n_reads && read_len0 == src_a->fixed_len && (host_a || !shn_env_set("SHN_GRAPH_RESIDENT_READS"));
-  if (resident) { g.src_a = src_a; g.src_b = paired ? src_b : nullptr; }
-  const uint64_t N_in = src_a ? src_a->n_reads : 0;
-  auto origin_of = [&](uint64_t j, uint32_t& row, uint8_t& flag) {
-    const int nm_ = paired ? 2 : 1;
-    const uint64_t i = j / nm_;
-    const int mate = (int)(j % nm_);
-    const uint64_t d = didx[i];
-    const bool second = d >= N_in;
-    row = (uint32_t)(second ? d - N_in : d);
-    if (!paired) flag = second ? 2 : 0;
-    else if (mate == 0) flag = second ? (1 | 2) : 0;              // R1[d] / RC(R2[d-N])
-    else flag = second ? 1 : 2;                                     // RC(R1[d]) / R2[d-N]
-  };
-  uint64_t n_kmer_nodes = 0;
-  if (ug && !ug->cyclic[part]) {
-    const uint64_t n0 = ug->node_off[part], n1 = ug->node_off[part + 1], e0 = ug->edge_off[part], e1 = ug->edge_off[part + 1];
-    g.load_unitigs(ug->bases.data(), ug->base_off.data() + n0, ug->n_len.data() + n0, ug->n_tail_out.data() + n0, n1 - n0,
-                   ug->e_src.data() + e0, ug->e_dst.data() + e0, ug->e_out_rank.data() + e0, ug->e_in_rank.data() + e0, e1 - e0);
-    g.precondensed = true;
-    n_kmer_nodes = ug->n_kmers[part];
-    if (shn_env_set("SHN_GRAPH_CHECK")) {
-      if (!rows && n_rows == 0 && n1 != n0) return shn_fail(SHN_ERR_ARG, "SHN_GRAPH_CHECK needs the k1-mer rows");
-      Graph h;
-      h.K = K;
-      h.load_k1mers(rows, n_rows);
-      const uint64_t hk = h.order.size();
-      h.condense_all();
-      if (hk != n_kmer_nodes || h.signature() != g.signature()) {
-        if (const char* dump = shn_env_str("SHN_GRAPH_CHECK_DUMP")) {
-          FILE* fa = fopen((std::string(dump) + ".host").c_str(), "w"); if (fa) { fputs(h.signature().c_str(), fa); fclose(fa); }
-          FILE* fb = fopen((std::string(dump) + ".gpu").c_str(), "w"); if (fb) { fputs(g.signature().c_str(), fb); fclose(fb); }
-        }
-        return shn_fail(SHN_ERR_INTERNAL, "SHN_GRAPH_CHECK: GPU unitigs differ from load_k1mers + condense_all (partition " + std::to_string(part) + ": " +
-                        std::to_string(n_kmer_nodes) + " / " + std::to_string(hk) + " K-mers, " + std::to_string(g.order.size()) + " / " +
-                        std::to_string(h.order.size()) + " nodes)");
-      }
-    }
-  } else {
+// the graph before any read is looked at; n_kmer_nodes = its K-mers (the read cap is ten times that)
+static int load_kmer_graph(Graph& g, const KmerGraphSource& ks, uint64_t& n_kmer_nodes) {
+  const shn_unitigs* ug = ks.ug; const uint32_t part = ks.part;
+  if (!ug || ug->cyclic[part]) {
     // (asked by the K-mers, not by the stored nodes: a partition that is nothing but cycles stores no node at all)
-    if (ug && !rows && ug->n_kmers[part] != 0) return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run_unitigs: cyclic partition needs the k1-mer rows");
-    g.load_k1mers(rows, n_rows);
+    if (ug && !ks.rows && ug->n_kmers[part] != 0) return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run_unitigs: cyclic partition needs the k1-mer rows");
+    g.load_k1mers(ks.rows, ks.n_rows);
     n_kmer_nodes = g.order.size();
+    return 0;
   }
-  if (dbg) { fprintf(stderr, "[mbgraph] load_k1mers            %8.3f s  rows=%llu\n", now() - tt, (unsigned long long)n_rows); tt = now(); }
-  uint64_t cutoff = n_kmer_nodes * 10;
-  // Scratch kept between calls (at the read cap these buffers are 100s of MB, and fresh pages cost more than the work done
-  // in them): decode buffers and the read arena.  A free list, not thread_local: Python's partition workers are short-lived.
-  // (also the per-read arrays of the graph: a partition at the read cap touches ~1.5 GB here, and with 64 partitions starting at
-  // once the page faults of fresh memory were most of the largest partition's "load reads".)  The list keeps one object per
-  // partition thread; a call takes the smallest one that is large enough, else the largest.
-  struct Scratch {
-    std::vector<uint64_t> doff, hashes; std::vector<char> text; std::string arena; std::vector<uint32_t> first, cnt, last; std::vector<int32_t> idmap;
-    std::vector<double> rcc; std::vector<int> rmate, rmp, rfirst, rlast; std::vector<char> rhas; std::vector<uint64_t> r_hashes, r_off;
-    std::vector<uint8_t> role;
-    std::vector<uint32_t> origin_row; std::vector<uint8_t> origin_flag;      // (the graph's, kept from call to call like the arrays above)
-    // the buffer of the lazily decoded read text: NOT a vector -- it is written piecemeal (a few per cent of the reads are ever
-    // decoded), and a vector's resize zero-filled all of it: 0.1 s for the 354 MB of the largest partition whenever it got a
-    // scratch object that had served a smaller one (the spread of the graph stage from step to step)
-    char* lz_raw = nullptr; size_t lz_cap = 0;
-    char* lazy_text(size_t bytes) {
-      if (bytes > lz_cap) { free(lz_raw); lz_raw = (char*)malloc(bytes + bytes / 8); lz_cap = lz_raw ? bytes + bytes / 8 : 0; }
-      return lz_raw;
-    }
-    ~Scratch() { free(lz_raw); }
-    size_t room() const { return std::max(std::max(text.capacity(), arena.capacity()), lz_cap); }
-  };
-  static std::mutex scratch_mu;
-  static std::vector<Scratch*> scratch_free;
-  Scratch* sc = nullptr;
-  // the distinct reads found on the device: with the host matrices always, with gathered rows for large sets
-  uint64_t bulk_min = 1u << 17;                         // reads from which the duplicates are found in parallel (tests lower it)
-  bulk_min = shn_env_u64("SHN_GRAPH_BULK_MIN", bulk_min);
-  const bool dev_dedup = resident && (host_a || (shn_env_flag("SHN_GRAPH_DEVICE_DEDUP", true) && enc == SHN_ENC_CODES &&
-                                                 std::min<uint64_t>(n_reads, cutoff + 1) * (paired ? 2 : 1) >= bulk_min));
-  const size_t need_text = (size_t)std::min<uint64_t>(n_reads, cutoff + 1) * (paired ? 2 : 1) * (size_t)read_len0 / (dev_dedup ? 2 : 1);
-  { std::lock_guard<std::mutex> lk(scratch_mu);
-    int pick = -1;
-    for (size_t i = 0; i < scratch_free.size(); i++) {
-      const size_t c = scratch_free[i]->room();
-      if (pick < 0) { pick = (int)i; continue; }
-      const size_t pc = scratch_free[pick]->room();
-      if (pc >= need_text ? (c >= need_text && c < pc) : c > pc) pick = (int)i;
-    }
-    if (pick >= 0) { sc = scratch_free[pick]; scratch_free.erase(scratch_free.begin() + pick); } }
-  if (!sc) sc = new Scratch();
-  struct Giveback {
-    Scratch* s; Graph* g;
-    ~Giveback() {
-      g->rindex.arena.clear(); s->arena.swap(g->rindex.arena);
-      s->rcc.swap(g->rcc); s->rmate.swap(g->rmate); s->rmp.swap(g->rmp); s->rfirst.swap(g->rfirst); s->rlast.swap(g->rlast); s->rhas.swap(g->rhas);
-      s->r_hashes.swap(g->rindex.hashes); s->r_off.swap(g->rindex.off);
-      s->origin_row.swap(g->origin_row); s->origin_flag.swap(g->origin_flag);
-      std::lock_guard<std::mutex> lk(scratch_mu);
-      if (scratch_free.size() < 192) scratch_free.push_back(s); else delete s;
-    }
-  } giveback{sc, &g};
-  g.rindex.arena.swap(sc->arena);
-  g.rindex.arena.clear();
-  sc->rcc.clear(); sc->rmate.clear(); sc->rmp.clear(); sc->rfirst.clear(); sc->rlast.clear(); sc->rhas.clear(); sc->r_hashes.clear(); sc->r_off.assign(1, 0);
-  g.rcc.swap(sc->rcc); g.rmate.swap(sc->rmate); g.rmp.swap(sc->rmp); g.rfirst.swap(sc->rfirst); g.rlast.swap(sc->rlast); g.rhas.swap(sc->rhas);
-  g.rindex.hashes.swap(sc->r_hashes); g.rindex.off.swap(sc->r_off);
-  g.origin_row.swap(sc->origin_row); g.origin_flag.swap(sc->origin_flag);
-  g.origin_row.resize(0); g.origin_flag.resize(0);                      // (capacity kept; empty until a path fills them)
-  // the fast form of the rows mode (graph_dev.h): the duplicate search leaves its arrays on the device, the host gets rows + strands
-  // (for the lazily decoded text) and nothing else per read.  SHN_GRAPH_DEV_ATTRS=0: the host-array form below.
-  const bool lazy_ok = host_a && shn_env_flag("SHN_GRAPH_LAZY_TEXT", true) && src_a && src_a->n_invalid == 0 &&
-                       (!paired || (src_b && src_b->n_invalid == 0));
-  if (dev_dedup && lazy_ok && g.ctx && K <= 31 && shn_env_flag("SHN_GRAPH_DEV_ATTRS", true)) {
-    const uint64_t used = std::min<uint64_t>(n_reads, cutoff + 1);
-    const uint64_t Lr = read_len0;
-    double t_dec = now();
-    int rcd = shn_reads_dedup_dev(g.ctx, src_a, paired ? src_b : nullptr, didx, d_didx, used, paired, &g.dd);
-    if (rcd) return rcd;
-    const uint64_t nd = g.dd->n_distinct;
-    g.n_rd_dev = nd; g.dev_attrs = true;
-    if (dbg) fprintf(stderr, "[mbgraph]   distinct reads (GPU)   %8.3f s  used=%llu distinct=%llu (attributes stay on the device)\n", now() - t_dec, (unsigned long long)used, (unsigned long long)nd);
-    g.lz_a = host_a; g.lz_b = host_b; g.lz_L = (uint32_t)Lr; g.lz_buf = sc->lazy_text(nd * Lr + 1);
-    if (!g.lz_buf) return shn_fail(SHN_ERR_NOMEM, "shn_mbgraph_run: out of host memory for the reads' text");
-    g.lz_done.assign((nd + 63) / 64, 0);
-    g.origin_row.resize(nd); g.origin_flag.resize(nd);
-    if ((rcd = shn_dedup_origin(g.dd, g.origin_row.data(), g.origin_flag.data()))) return rcd;
-    g.acgt_known = 1;
-    if (dbg) fprintf(stderr, "[mbgraph]   + rows of the distinct  %8.3f s\n", now() - t_dec);
-  } else if (dev_dedup) {
-    { const int rcf = need_didx(); if (rcf) return rcf; }
-    const uint64_t used = std::min<uint64_t>(n_reads, cutoff + 1);
-    const int nm = paired ? 2 : 1;
-    const uint64_t nh = used * nm, Lr = read_len0;
-    double t_dec = now();
-    std::vector<uint32_t>&slot = sc->first, &cnt = sc->cnt;
-    std::vector<int32_t>& mate = sc->idmap;
-    std::vector<uint8_t>& role = sc->role;
-    slot.resize(nh); cnt.resize(nh); mate.resize(nh); role.resize(nh);
-    uint64_t nd = 0;
-    int rcd = shn_reads_dedup(g.ctx, src_a, paired ? src_b : nullptr, didx, used, paired, &nd, slot.data(), cnt.data(), mate.data(), role.data());
-    if (rcd) return rcd;
-    if (dbg) fprintf(stderr, "[mbgraph]   distinct reads (GPU)   %8.3f s  used=%llu distinct=%llu\n", now() - t_dec, (unsigned long long)used, (unsigned long long)nd);
-    StringInterner& R = g.rindex;
-    R.hashes.assign(nd, 0);
-    const bool lazy = host_a && shn_env_flag("SHN_GRAPH_LAZY_TEXT", true) && src_a->n_invalid == 0 && (!paired || src_b->n_invalid == 0);
-    if (lazy) {
-      g.lz_a = host_a; g.lz_b = host_b; g.lz_L = (uint32_t)Lr; g.lz_buf = sc->lazy_text(nd * Lr + 1);
-      if (!g.lz_buf) return shn_fail(SHN_ERR_NOMEM, "shn_mbgraph_run: out of host memory for the reads' text");
-      g.lz_done.assign((nd + 63) / 64, 0);
-    }
-    R.off.resize(nd + 1);
-    if (!lazy && R.arena.capacity() < nd * Lr) { R.arena.reserve(nd * Lr); if (nd * Lr >= (8u << 20)) { const uintptr_t a = ((uintptr_t)R.arena.data() + 4095) & ~(uintptr_t)4095; madvise((void*)a, (nd * Lr) & ~(size_t)4095, MADV_HUGEPAGE); } }
-    if (!lazy) R.arena.resize(nd * Lr);
-    g.rcc.resize(nd); g.rmate.resize(nd); g.rmp.resize(nd); g.rfirst.assign(nd, -1); g.rlast.assign(nd, -1); g.rhas.assign(nd, 0);
-    g.origin_row.resize(nd); g.origin_flag.resize(nd);
-    const unsigned hwc = (unsigned)shn_host_cpus();
-    unsigned nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(32, std::max(1u, hwc / 2)), nd >> 15));
-    BudgetGuard budget((int)nt);
-    std::atomic<int> non_acgt{0};
-    char* arena = lazy ? nullptr : &R.arena[0];
-    auto work = [&](uint64_t lo, uint64_t hi) {
-      bool bad = false;
-      for (uint64_t id = lo; id < hi; id++) {
-        const uint64_t j = slot[id];
-        uint32_t row; uint8_t fl;
-        origin_of(j, row, fl);
-        g.origin_row[id] = row; g.origin_flag[id] = fl;
-        if (lazy) { g.rcc[id] = (double)cnt[id]; g.rmate[id] = mate[id]; g.rmp[id] = role[id]; continue; }
-        const uint8_t* p; bool rc; int e = enc;
-        if (host_a) { p = ((fl & 1) ? host_b : host_a) + (uint64_t)row * Lr; rc = (fl & 2) != 0; e = SHN_ENC_CODES; }
-        else { const uint64_t i = j / nm; if (j % nm == 0) { p = r1 + r1_off[i]; rc = rc1 && rc1[i]; } else { p = r2 + r2_off[i]; rc = rc2 && rc2[i]; } }
-        char* d = arena + id * Lr;
-        decode_read(d, p, Lr, e, rc);
-        for (uint64_t q = 0; q < Lr; q++) bad |= !(d[q] == 'A' || d[q] == 'C' || d[q] == 'G' || d[q] == 'T');
-        R.off[id + 1] = (id + 1) * Lr;
-        g.rcc[id] = (double)cnt[id];
-        g.rmate[id] = mate[id];
-        g.rmp[id] = role[id];
-      }
-      if (bad) non_acgt.store(1);
-    };
-    R.off[0] = 0;
-    if (nt <= 1) work(0, nd);
-    else {
-      std::vector<std::thread> th;
-      for (unsigned t = 0; t < nt; t++) th.emplace_back(work, nd * t / nt, nd * (t + 1) / nt);
-      for (auto& t : th) t.join();
-    }
-    if (non_acgt.load()) return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run: a routed read holds a base outside ACGT (the packed rows cannot tell such reads apart)");
-    g.acgt_known = 1;
-    R.bulk_loaded = true;
-    if (dbg) fprintf(stderr, "[mbgraph]   + text of the distinct %8.3f s  nt=%u (waited %.3f s for threads)\n", now() - t_dec, nt, budget.waited);
-  } else {
-    uint64_t used = std::min<uint64_t>(n_reads, cutoff + 1);
-    size_t bytes = used ? (size_t)(r1_off[used] - r1_off[0]) + (paired ? (size_t)(r2_off[used] - r2_off[0]) : 0) : 0;
-    g.rindex.arena.reserve(bytes);
-    size_t nr = (size_t)used * (paired ? 2 : 1);
-    if (nr < (1u << 17)) g.rindex.reserve(nr);          // (large sets are numbered in bulk and never use the interner's probe table)
-    g.rcc.reserve(nr); g.rmate.reserve(nr); g.rmp.reserve(nr); g.rfirst.reserve(nr); g.rlast.reserve(nr); g.rhas.reserve(nr);
+  const uint64_t n0 = ug->node_off[part], n1 = ug->node_off[part + 1], e0 = ug->edge_off[part], e1 = ug->edge_off[part + 1];
+  g.load_unitigs(ug->bases.data(), ug->base_off.data() + n0, ug->n_len.data() + n0, ug->n_tail_out.data() + n0, n1 - n0,
+                 ug->e_src.data() + e0, ug->e_dst.data() + e0, ug->e_out_rank.data() + e0, ug->e_in_rank.data() + e0, e1 - e0);
+  g.precondensed = true;
+  n_kmer_nodes = ug->n_kmers[part];
+  if (!shn_env_set("SHN_GRAPH_CHECK")) return 0;
+  if (!ks.rows && ks.n_rows == 0 && n1 != n0) return shn_fail(SHN_ERR_ARG, "SHN_GRAPH_CHECK needs the k1-mer rows");
+  Graph h;
+  h.K = g.K;
+  h.load_k1mers(ks.rows, ks.n_rows);
+  const uint64_t hk = h.order.size();
+  h.condense_all();
+  if (hk == n_kmer_nodes && h.signature() == g.signature()) return 0;
+  if (const char* dump = shn_env_str("SHN_GRAPH_CHECK_DUMP")) {
+    FILE* fa = fopen((std::string(dump) + ".host").c_str(), "w"); if (fa) { fputs(h.signature().c_str(), fa); fclose(fa); }
+    FILE* fb = fopen((std::string(dump) + ".gpu").c_str(), "w"); if (fb) { fputs(g.signature().c_str(), fb); fclose(fb); }
   }
-  if (!dev_dedup) {
-    { const int rcf = need_didx(); if (rcf) return rcf; }
-    // decode + hash on several host threads (independent per read), then intern sequentially in file order
-    const uint64_t used = std::min<uint64_t>(n_reads, cutoff + 1);
-    const int nm = paired ? 2 : 1;
-    // (scratch kept per host thread between calls: at the read cap these are 100s of MB, and fresh pages cost more than the decode)
-    std::vector<uint64_t>&doff = sc->doff, &hashes = sc->hashes;
-    std::vector<char>& text = sc->text;
-    doff.resize((size_t)used * nm + 1);
-    doff[0] = 0;
-    for (uint64_t i = 0; i < used; i++) {
-      doff[i * nm + 1] = doff[i * nm] + (r1_off[i + 1] - r1_off[i]);
-      if (paired) doff[i * nm + 2] = doff[i * nm + 1] + (r2_off[i + 1] - r2_off[i]);
-    }
-    auto huge = [](const void* p, size_t bytes) {                 // transparent huge pages for the large scratch buffers (THP in madvise mode)
-      if (bytes < (8u << 20)) return;
-      const uintptr_t a = ((uintptr_t)p + 4095) & ~(uintptr_t)4095, e = ((uintptr_t)p + bytes) & ~(uintptr_t)4095;
-      if (e > a) madvise((void*)a, e - a, MADV_HUGEPAGE);
-    };
-    if (text.size() < doff.back() + 1) { text.clear(); text.reserve(doff.back() + 1); huge(text.data(), text.capacity()); text.resize(doff.back() + 1); }
-    if (hashes.capacity() < (size_t)used * nm) { hashes.clear(); hashes.reserve((size_t)used * nm); huge(hashes.data(), hashes.capacity() * 8); }
-    hashes.resize((size_t)used * nm);
-    if (g.rindex.arena.capacity() >= (8u << 20)) huge(g.rindex.arena.data(), g.rindex.arena.capacity());
-    double t_dec = now();
-    std::atomic<int> non_acgt{0};
-    auto work = [&](uint64_t lo, uint64_t hi) {
-      bool bad = false;
-      auto check = [&](const char* d, uint64_t n) { for (uint64_t j = 0; j < n; j++) bad |= !(d[j] == 'A' || d[j] == 'C' || d[j] == 'G' || d[j] == 'T'); };
-      for (uint64_t i = lo; i < hi; i++) {
-        char* d1 = text.data() + doff[i * nm];
-        const uint64_t n1 = r1_off[i + 1] - r1_off[i];
-        decode_read(d1, r1 + r1_off[i], n1, enc, rc1 && rc1[i]);
-        check(d1, n1);
-        hashes[i * nm] = StringInterner::hash(d1, n1);
-        if (paired) {
-          char* d2 = text.data() + doff[i * nm + 1];
-          const uint64_t n2 = r2_off[i + 1] - r2_off[i];
-          decode_read(d2, r2 + r2_off[i], n2, enc, rc2 && rc2[i]);
-          check(d2, n2);
-          hashes[i * nm + 1] = StringInterner::hash(d2, n2);
-        }
-      }
-      if (bad) non_acgt.store(1);
-    };
-    // (8 ranks share a node's cores; partitions running at the same time in this process share this rank's part)
-    static std::atomic<int> active_calls{0};
-    struct Active { std::atomic<int>& a; int n; Active(std::atomic<int>& x) : a(x), n(++x) {} ~Active() { --a; } } active(active_calls);
-    // The partitions of a run differ in size by an order of magnitude and the largest ones are started first (pipeline.py): the
-    // stage ends when the largest partition does, so its read set gets threads in proportion to its size (one per 256 Ki
-    // reads, at most 32 and at most a quarter of the cores), whatever else is running; small sets share what is left.
-    const unsigned hwc = (unsigned)shn_host_cpus();
-    unsigned nt = std::min<unsigned>(32, std::max<unsigned>(1, hwc / 8 / (unsigned)std::max(1, active.n / 2)));
-    nt = std::max<unsigned>(nt, (unsigned)std::min<uint64_t>(std::min<uint64_t>(32, std::max(1u, hwc / 2)), (used * (paired ? 2 : 1)) >> 18));
-    if (shn_env_set("SHN_GRAPH_BULK_MIN")) nt = std::max(nt, 4u);
-    if (used * nm < bulk_min) nt = used < 4096 ? 1 : std::min<unsigned>(nt, (unsigned)(used / 2048));   // small sets: a few threads for the decode only
-    BudgetGuard budget((int)nt);                          // held until the reads are numbered
-    if (nt <= 1) work(0, used);
-    else {
-      std::vector<std::thread> th;
-      const uint64_t per = (used + nt - 1) / nt;
-      for (unsigned t = 0; t < nt; t++) { uint64_t lo = t * per, hi = std::min<uint64_t>(used, lo + per); if (lo < hi) th.emplace_back(work, lo, hi); }
-      for (auto& t : th) t.join();
-    }
-    g.acgt_known = non_acgt.load() ? 0 : 1;
-    if (dbg) fprintf(stderr, "[mbgraph]   offsets+decode+hash   %8.3f s  used=%llu nt=%u (waited %.3f s for threads)\n", now() - t_dec, (unsigned long long)used, nt, budget.waited);
-    const uint64_t nh = used * nm;
-    if (nt > 1 && nh >= bulk_min && g.rindex.size() == 0) {
-      // Large read sets, all on `nt` host threads: (1) the duplicates -- every thread owns the strings whose hash falls into
-      // its shard (private open-addressing table: string -> index of its first occurrence, with its number of occurrences
-      // and its last occurrence); (2) ids in file order of first occurrence = a prefix sum over the "first occurrence"
-      // flags, the strings copied to their place in the arena in parallel; (3) every read's id; (4) mates: interning one
-      // pair after the other leaves every read with the role and mate of its LAST occurrence.  Same ids, counts and mates
-      // as reading one read at a time (test_native_graph_stage_parallel_read_dedup).
-      std::vector<uint32_t>&first = sc->first, &cnt = sc->cnt, &last = sc->last;
-      first.resize(nh); cnt.resize(nh); last.resize(nh);
-      auto run_threads = [&](auto&& fn) {
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < nt; t++) th.emplace_back(fn, t);
-        for (auto& t : th) t.join();
-      };
-      run_threads([&](unsigned t) {
-        size_t cap = 1024;                                      // shards of a hash are even: 2.5x the mean share is ample
-        while (cap < (nh / nt + 1) * 5 / 2) cap <<= 1;
-        std::vector<uint32_t> tab(cap, 0xFFFFFFFFu);
-        uint64_t used_slots = 0;
-        for (uint64_t j = 0; j < nh; j++) {
-          const uint64_t h = hashes[j];
-          if (((h >> 40) % nt) != t) continue;
-          if (used_slots * 10 > cap * 8) {                       // (a pathological hash distribution: grow and re-insert)
-            std::vector<uint32_t> old;
-            old.swap(tab);
-            cap <<= 1;
-            tab.assign(cap, 0xFFFFFFFFu);
-            for (uint32_t q : old) if (q != 0xFFFFFFFFu) { size_t sl = (size_t)hashes[q] & (cap - 1); while (tab[sl] != 0xFFFFFFFFu) sl = (sl + 1) & (cap - 1); tab[sl] = q; }
-          }
-          const size_t m = cap - 1;
-          const char* p = text.data() + doff[j];
-          const uint64_t n = doff[j + 1] - doff[j];
-          size_t sl = (size_t)h & m;
-          while (true) {
-            const uint32_t q = tab[sl];
-            if (q == 0xFFFFFFFFu) { tab[sl] = (uint32_t)j; first[j] = (uint32_t)j; cnt[j] = 1; last[j] = (uint32_t)j; used_slots++; break; }
-            if (hashes[q] == h && doff[q + 1] - doff[q] == n && memcmp(text.data() + doff[q], p, n) == 0) { first[j] = q; cnt[q]++; last[q] = (uint32_t)j; break; }
-            sl = (sl + 1) & m;
-          }
-        }
-      });
-      if (dbg) fprintf(stderr, "[mbgraph]   + duplicates found     %8.3f s  used=%llu\n", now() - t_dec, (unsigned long long)used);
-      std::vector<int32_t>& idmap = sc->idmap;
-      idmap.resize(nh);
-      StringInterner& R = g.rindex;
-      // (2) chunk c of the reads: how many first occurrences, how many bytes
-      std::vector<uint64_t> nf(nt + 1, 0), nbytes(nt + 1, 0);
-      auto lo_of = [&](unsigned c) { return nh * c / nt; };
-      run_threads([&](unsigned c) {
-        uint64_t f = 0, by = 0;
-        for (uint64_t j = lo_of(c); j < lo_of(c + 1); j++) if (first[j] == (uint32_t)j) { f++; by += doff[j + 1] - doff[j]; }
-        nf[c + 1] = f; nbytes[c + 1] = by;
-      });
-      for (unsigned c = 0; c < nt; c++) { nf[c + 1] += nf[c]; nbytes[c + 1] += nbytes[c]; }
-      const uint64_t nd = nf[nt];
-      R.hashes.resize(nd);
-      R.off.resize(nd + 1);
-      R.off[0] = 0;
-      R.arena.resize(nbytes[nt]);
-      g.rcc.resize(nd); g.rmate.resize(nd, -1); g.rmp.resize(nd, 0); g.rfirst.resize(nd, -1); g.rlast.resize(nd, -1); g.rhas.resize(nd, 0);
-      if (resident) { g.origin_row.resize(nd); g.origin_flag.resize(nd); }
-      char* arena = &R.arena[0];
-      run_threads([&](unsigned c) {
-        uint64_t id = nf[c], at = nbytes[c];
-        for (uint64_t j = lo_of(c); j < lo_of(c + 1); j++) {
-          if (first[j] != (uint32_t)j) continue;
-          const uint64_t n = doff[j + 1] - doff[j];
-          memcpy(arena + at, text.data() + doff[j], n);
-          at += n;
-          R.hashes[id] = hashes[j];
-          R.off[id + 1] = at;
-          g.rcc[id] = (double)cnt[j];
-          idmap[j] = (int32_t)id;
-          if (resident) origin_of(j, g.origin_row[id], g.origin_flag[id]);
-          id++;
-        }
-      });
-      run_threads([&](unsigned c) {                                  // (3) (a first occurrence precedes its duplicates, all are numbered by now)
-        for (uint64_t j = lo_of(c); j < lo_of(c + 1); j++) if (first[j] != (uint32_t)j) idmap[j] = idmap[first[j]];
-      });
-      if (paired)
-        run_threads([&](unsigned c) {                                // (4)
-          for (uint64_t j = lo_of(c); j < lo_of(c + 1); j++) {
-            if (first[j] != (uint32_t)j) continue;
-            const uint32_t l = last[j];
-            const int32_t id = idmap[j];
-            g.rmp[id] = (l & 1) ? 2 : 1;
-            g.rmate[id] = idmap[l ^ 1u];
-          }
-        });
-      R.bulk_loaded = true;                 // (its probe table was bypassed: no interning by string after this)
-      if (dbg) fprintf(stderr, "[mbgraph]   + numbered in order    %8.3f s  used=%llu\n", now() - t_dec, (unsigned long long)used);
-    } else
-    for (uint64_t i = 0; i < used; i++) {
-      auto note = [&](int r, uint64_t j) {
-        if (resident && (size_t)r == g.origin_row.size()) { uint32_t row; uint8_t fl; origin_of(j, row, fl); g.origin_row.push_back(row); g.origin_flag.push_back(fl); }
-      };
-      int a = g.add_read(text.data() + doff[i * nm], doff[i * nm + 1] - doff[i * nm], hashes[i * nm]);
-      note(a, i * nm);
-      if (paired) {
-        int b = g.add_read(text.data() + doff[i * nm + 1], doff[i * nm + 2] - doff[i * nm + 1], hashes[i * nm + 1]);
-        note(b, i * nm + 1);
-        g.rmp[a] = 1; g.rmp[b] = 2; g.rmate[a] = b; g.rmate[b] = a;
-      }
-    }
-  }
-  if (dbg) { fprintf(stderr, "[mbgraph] load reads             %8.3f s  reads=%llu distinct=%zu\n", now() - tt, (unsigned long long)n_reads, g.n_rd()); tt = now(); }
-  int rc = g.run();
-  g.release_gpu();
-  tt = now();
-  if (rc) return rc;
-  // ---- output_components (add_component mbgraph.py:691-709, topological_sort :711-732, P2)
+  return shn_fail(SHN_ERR_INTERNAL, "SHN_GRAPH_CHECK: GPU unitigs differ from load_k1mers + condense_all (partition " + std::to_string(part) + ": " +
+                  std::to_string(n_kmer_nodes) + " / " + std::to_string(hk) + " K-mers, " + std::to_string(g.order.size()) + " / " +
+                  std::to_string(h.order.size()) + " nodes)");
+}
+
+// ---- output_components (add_component mbgraph.py:691-709, topological_sort :711-732, P2)
+static shn_graph* export_components(Graph& g) {
   shn_graph* o = new shn_graph();
   o->s_off.push_back(0); o->n_off.push_back(0); o->p_off.push_back(0);
   o->comp_node_off.push_back(0); o->comp_edge_off.push_back(0); o->comp_path_off.push_back(0);
@@ -1954,13 +1289,120 @@ static int mbgraph_run_impl(shn_ctx* ctx, int K, const uint8_t* rows, uint64_t n
     for (auto& x : el) { o->e_in.push_back((int)x[0]); o->e_out.push_back((int)x[1]); o->e_w.push_back((int)x[2]); o->e_cc.push_back(x[3]); o->e_norm.push_back(x[4]); }
     o->comp_edge_off.push_back(o->e_in.size());
   }
-  if (dbg) fprintf(stderr, "[mbgraph] output_components      %8.3f s\n", now() - tt);
   for (int i = 0; i < 4; i++) o->info.push_back(g.nodes_after[i]);
   o->info.push_back(g.final_nodes); o->info.push_back(g.n_known); o->info.push_back(g.n_mate);
   o->info.push_back((int)g.bridged_log.size());
   for (int b : g.bridged_log) o->info.push_back(b);
-  *out = o;
+  return o;
+}
+
+// ---- the driver of one partition: every entry point below ends here
+static int mbgraph_run(shn_ctx* ctx, int K, const KmerGraphSource& ks, ReadSource& rs, shn_graph** out) {
+  if (!out || (ks.n_rows && !ks.rows) || (!rs.host_a && ((rs.n_reads && (!rs.r1 || !rs.r1_off)) || (rs.paired && rs.n_reads && (!rs.r2 || !rs.r2_off)))))
+    return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run: NULL argument");
+  struct Running { Running() { g_partitions_running.fetch_add(1); } ~Running() { g_partitions_running.fetch_sub(1); } } running;
+  Graph g;
+  g.ctx = shn_thread_ctx(ctx); g.K = K;
+  g.L = rs.n_reads ? (int)rs.read_len() : -1;            // Read.L = length of the first read
+  g.SIZE_THRESHOLD = g.L;
+  // SHN_DEBUG: the laps of every partition; SHN_GRAPH_LAPS=n: of the partitions with at least n routed reads
+  g.laps = g.reads.laps = shn_env_set("SHN_DEBUG") || (shn_env_set("SHN_GRAPH_LAPS") && rs.n_reads >= shn_env_u64("SHN_GRAPH_LAPS", 0));
+  double tt = tnow();
+  auto lapse = [&]() { const double t = tnow(), d = t - tt; tt = t; return d; };
+  uint64_t n_kmer_nodes = 0;
+  int rc = load_kmer_graph(g, ks, n_kmer_nodes);
+  if (rc) return rc;
+  lap_line(g.laps, "load_k1mers", lapse(), "rows=%llu", (unsigned long long)ks.n_rows);
+  const uint64_t cutoff = n_kmer_nodes * 10, used = std::min<uint64_t>(rs.n_reads, cutoff + 1);      // the read cap
+  HostIntakeSlot slot;                                   // (choosing a host form takes the slot -- it counts this call among the host intakes -- until leave() below)
+  const IntakePlan plan = choose_intake(rs, g.ctx, K, cutoff, slot);
+  const bool on_device = plan.form == IntakeForm::DeviceAttrs || plan.form == IntakeForm::DeviceDedup;
+  ScratchLease lease(g.reads, (size_t)used * rs.nm() * (size_t)rs.read_len() / (on_device ? 2 : 1));
+  if ((rc = g.reads.load(g.ctx, rs, used, plan))) return rc;
+  slot.leave();
+  lap_line(g.laps, "load reads", lapse(), "reads=%llu distinct=%zu", (unsigned long long)rs.n_reads, g.reads.n_rd());
+  rc = g.run();
+  g.release_gpu();
+  if (rc) return rc;
+  tt = tnow();
+  *out = export_components(g);
+  lap_line(g.laps, "output_components", lapse(), "%s", "");
   return SHN_OK;
+}
+
+// reads: ASCII or codes (enc: SHN_ENC_ASCII or SHN_ENC_CODES, 0..3) with r_off[n_reads+1]; paired: second mate file r2 / r2_off
+// with the same count; rc1 / rc2: the strand-doubled view of the packed input, shannon.py:396-424
+static ReadSource text_reads(const uint8_t* r1, const uint64_t* r1_off, const uint8_t* r2, const uint64_t* r2_off, uint64_t n_reads, int paired, int enc,
+                             const uint8_t* rc1, const uint8_t* rc2) {
+  ReadSource rs;
+  rs.r1 = r1; rs.r1_off = r1_off; rs.r2 = r2; rs.r2_off = r2_off; rs.n_reads = n_reads; rs.paired = paired; rs.enc = enc; rs.rc1 = rc1; rs.rc2 = rc2;
+  return rs;
+}
+
+extern "C" int shn_mbgraph_run(shn_ctx* ctx, int K, const uint8_t* rows, uint64_t n_rows, const uint8_t* r1, const uint64_t* r1_off,
+                               const uint8_t* r2, const uint64_t* r2_off, uint64_t n_reads, int paired, int enc, const uint8_t* rc1,
+                               const uint8_t* rc2, shn_graph** out) {
+  ReadSource rs = text_reads(r1, r1_off, r2, r2_off, n_reads, paired, enc, rc1, rc2);
+  return mbgraph_run(ctx, K, KmerGraphSource{rows, n_rows, nullptr, 0}, rs, out);
+}
+// The same with the partition's K-mer graph already contracted on the GPU (see KmerGraphSource).
+extern "C" int shn_mbgraph_run_unitigs(shn_ctx* ctx, const shn_unitigs* ug, uint32_t part, const uint8_t* rows, uint64_t n_rows, const uint8_t* r1,
+                                       const uint64_t* r1_off, const uint8_t* r2, const uint64_t* r2_off, uint64_t n_reads, int paired, int enc,
+                                       const uint8_t* rc1, const uint8_t* rc2, shn_graph** out) {
+  if (!ug || part >= ug->n_parts) return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run_unitigs: bad unitigs / partition");
+  ReadSource rs = text_reads(r1, r1_off, r2, r2_off, n_reads, paired, enc, rc1, rc2);
+  return mbgraph_run(ctx, ug->K, KmerGraphSource{rows, n_rows, ug, part}, rs, out);
+}
+
+// The same again with the partition's reads known as rows of the resident input (src_a / src_b / didx, see ReadSource).  The read
+// text (r1 / r2) is still what the host side of the stage works on; the device copy of the distinct reads is gathered from the
+// resident sets instead of uploaded.
+extern "C" int shn_mbgraph_run_resident(shn_ctx* ctx, const shn_unitigs* ug, uint32_t part, const uint8_t* rows, uint64_t n_rows, const shn_reads* src_a,
+                                        const shn_reads* src_b, const uint32_t* didx, const uint8_t* r1, const uint64_t* r1_off, const uint8_t* r2,
+                                        const uint64_t* r2_off, uint64_t n_reads, int paired, int enc, const uint8_t* rc1, const uint8_t* rc2,
+                                        shn_graph** out) {
+  if (!ug || part >= ug->n_parts) return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run_resident: bad unitigs / partition");
+  ReadSource rs = text_reads(r1, r1_off, r2, r2_off, n_reads, paired, enc, rc1, rc2);
+  rs.src_a = src_a; rs.src_b = src_b; rs.didx = didx;
+  return mbgraph_run(ctx, ug->K, KmerGraphSource{rows, n_rows, ug, part}, rs, out);
+}
+
+// The partition's reads named only by their rows: host_a / host_b = the run's reads as host code matrices (uint8 codes 0-3,
+// [n_reads of the set][read length], the same reads as src_a / src_b hold packed on the device), didx as above.  The distinct
+// reads are found on the device (shn_reads_dedup) and only their text is decoded on the host, straight from the matrices: no
+// per-partition copy of the routed reads exists anywhere.
+static int mbgraph_run_rows(shn_ctx* ctx, const shn_unitigs* ug, uint32_t part, const uint8_t* rows, uint64_t n_rows, const shn_reads* src_a,
+                            const shn_reads* src_b, const uint8_t* host_a, const uint8_t* host_b, const uint32_t* didx, const uint32_t* d_didx,
+                            uint64_t n_reads, int paired, shn_graph** out) {
+  if (!ug || part >= ug->n_parts) return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run_rows: bad unitigs / partition");
+  if (!ctx || !src_a || !host_a || (n_reads && !didx && !d_didx) || (paired && (!src_b || !host_b)) || !src_a->fixed_len ||
+      (paired && src_b->fixed_len != src_a->fixed_len))
+    return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run_rows: needs a context, fixed-length resident read sets and their host matrices");
+  const bool dbg = shn_env_set("SHN_GRAPH_LAPS") && n_reads >= shn_env_u64("SHN_GRAPH_LAPS", 0);
+  const double t0 = dbg ? tnow() : 0.0;
+  ReadSource rs;
+  rs.src_a = src_a; rs.src_b = src_b; rs.host_a = host_a; rs.host_b = host_b; rs.didx = didx; rs.d_didx = d_didx;
+  rs.n_reads = n_reads; rs.paired = paired; rs.enc = SHN_ENC_CODES;
+  const int rc = mbgraph_run(ctx, ug->K, KmerGraphSource{rows, n_rows, ug, part}, rs, out);
+  if (dbg) fprintf(stderr, "[mbgraph] the call (partition %u), its clean-up included %8.3f s\n", part, tnow() - t0);
+  return rc;
+}
+extern "C" int shn_mbgraph_run_rows(shn_ctx* ctx, const shn_unitigs* ug, uint32_t part, const uint8_t* rows, uint64_t n_rows, const shn_reads* src_a,
+                                    const shn_reads* src_b, const uint8_t* host_a, const uint8_t* host_b, const uint32_t* didx, uint64_t n_reads,
+                                    int paired, shn_graph** out) {
+  return mbgraph_run_rows(ctx, ug, part, rows, n_rows, src_a, src_b, host_a, host_b, didx, nullptr, n_reads, paired, out);
+}
+// The same with the partition's routed reads named a second time by where they already lie on the device: entries [route_lo,
+// route_lo + n_reads) of the routes shn_route_reads left there (didx = the same indices on the host) -- the duplicate search then
+// reads them in place instead of uploading the list again (0.5 GB per step at BASELINE configs[2], in 111 pieces).
+extern "C" int shn_mbgraph_run_routes(shn_ctx* ctx, const shn_unitigs* ug, uint32_t part, const uint8_t* rows, uint64_t n_rows, const shn_reads* src_a,
+                                      const shn_reads* src_b, const uint8_t* host_a, const uint8_t* host_b, const uint32_t* didx, const shn_routes* routes,
+                                      uint64_t route_lo, uint64_t n_reads, int paired, shn_graph** out) {
+  if (!routes) return shn_fail(SHN_ERR_ARG, "shn_mbgraph_run_routes: routes is NULL");
+  const uint32_t* d = nullptr;
+  int rc = shn_routes_device_slice(routes, route_lo, n_reads, &d);
+  if (rc) return rc;
+  return mbgraph_run_rows(ctx, ug, part, rows, n_rows, src_a, src_b, host_a, host_b, didx, d, n_reads, paired, out);
 }
 
 // sizes: [n_singles, s_bases, n_comps, n_nodes, n_bases, n_edges, n_paths, n_path_ids, n_info]

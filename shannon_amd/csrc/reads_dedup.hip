@@ -13,7 +13,7 @@
 //   dd_tally    count and last occurrence per first occurrence; flag = "is a first occurrence"
 //   (scan)      id = number of first occurrences before the slot = the sequential numbering
 //   dd_emit     per distinct read: its first slot, count, and (pairs) role + mate id of its last occurrence
-// Output order and values equal the host code they replace (mbgraph_host.hip, bulk numbering) and the one-at-a-time interner
+// Output order and values equal the host code they replace (mbgraph_reads.h, number_in_parallel) and the one-at-a-time interner
 // (tests/test_host_graph.py, tests/test_e2e_gpu.py).
 #include "common.h"
 #include "graph_dev.h"
@@ -137,7 +137,7 @@ __global__ void dd_emit(uint64_t nh, int paired, const uint32_t* __restrict__ fi
       o_mate[id] = (int32_t)pos[first[l ^ 1u]];
     } else { o_role[id] = 0; o_mate[id] = -1; }
     if (o_row) {
-      // the slot's place in the resident input (mbgraph_run_impl's origin_of): row, bit 0 = set b, bit 1 = reverse complement
+      // the slot's place in the resident input (ReadSource::origin_of, mbgraph_reads.h): row, bit 0 = set b, bit 1 = reverse complement
       const uint64_t i = S.paired ? (j >> 1) : j;
       const uint64_t d = S.didx[i];
       const bool second = d >= S.n_in;

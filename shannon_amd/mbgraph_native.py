@@ -97,7 +97,12 @@ class GraphHandle(object):
             pass
 
 
-def _export(h):
+EXPORT_NAMES = ("s_off", "s_bases", "s_cc", "s_norm", "comp_node_off", "comp_edge_off", "comp_path_off", "n_off", "n_bases", "n_cc", "n_cc_int",
+                "n_norm", "e_in", "e_out", "e_w", "e_cc", "e_norm", "p_off", "p_ids", "info")
+
+
+def export_arrays(h):
+    """the flat arrays of shn_graph_export by name (EXPORT_NAMES), each cut to its length"""
     L = _lib.lib()
     sz = np.zeros(9, dtype=np.uint64)
     _lib.check(L.shn_graph_sizes(h, sz.ctypes.data_as(_lib.u64p)))
@@ -113,6 +118,14 @@ def _export(h):
     arrs = [s_off, s_bases, s_cc, s_norm, cno, ceo, cpo, n_off, n_bases, n_cc, n_cci, n_norm, e_in, e_out, e_w, e_cc, e_norm,
             p_off, p_ids, info]
     _lib.check(L.shn_graph_export(h, *[a.ctypes.data for a in arrs]))
+    lens = [ns + 1, sb, ns, ns, nc + 1, nc + 1, nc + 1, nn + 1, nb, nn, nn, nn, ne, ne, ne, ne, ne, npth + 1, npid, ninfo]
+    return {k: a[:n] for k, a, n in zip(EXPORT_NAMES, arrs, lens)}
+
+
+def _export(h):
+    x = export_arrays(h)
+    s_off, s_bases, s_cc, s_norm, cno, ceo, cpo, n_off, n_bases, n_cc, n_cci, n_norm, e_in, e_out, e_w, e_cc, e_norm, p_off, p_ids, info = [x[k] for k in EXPORT_NAMES]
+    ns, nc, ne, ninfo = len(s_cc), len(cno) - 1, len(e_in), len(info)
     sbs = s_bases.tobytes().decode()
     singles = [(-1, sbs[int(s_off[i]):int(s_off[i + 1])], 0 if s_cc[i] == 0 else float(s_cc[i]), int(s_norm[i])) for i in range(ns)]
     nbs = n_bases.tobytes().decode()

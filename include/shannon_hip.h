@@ -741,6 +741,31 @@ int shn_quorum_table(shn_ctx* ctx, const shn_reads* const* sets, const shn_qmask
 int shn_quorum_correct(shn_ctx* ctx, const shn_reads* reads, const shn_table* table, int k, uint32_t anchor_count, uint32_t window,
                        uint32_t max_subs, shn_reads** out, uint64_t* stats5);
 
+/* ---- --compare: a finished assembly against a reference transcriptome ------------------------------------------------------------
+ * Replaces the BLAT run of the reference's comparison (shannon.py:620-622 starts run_MB_SF_fn.py --compare; run_MB_SF_fn.py:299 runs
+ * parallel_blat_python.py, whose PSL lines tester.py:135-167, 269-317 read) by the stated rule of DESIGN.md 3.12, run on the device.
+ *
+ * shn_compare_rows (run_MB_SF_fn.py:299): queries q_text / q_off[n_q + 1] (the reference transcripts) and targets t_text /
+ * t_off[n_t + 1] (the reconstructed ones), each set one sequence after the other as ASCII; letters of either case, anything but
+ * ACGT matches nothing.  Every target is taken forward and -- unless strand_specific -- as its reverse complement.  For every
+ * (query, target) pair that shares a 16-mer (SHN_COMPARE_SEED) the best ungapped segment over the diagonals the shared 16-mers
+ * name (score = matches - 2 mismatches; the tie rules are DESIGN.md's) gives one row if it holds min_matches matches or more
+ * (SHN_COMPARE_MIN_MATCHES is BLAT's default).  Rows are ordered by query, then target.  Nothing is capped: candidates and rows
+ * are counted, scanned and filled.  SHN_ERR_ARG before any launch: offsets that do not start at 0 or are not monotone;
+ * SHN_ERR_OVERFLOW: a sequence of 2^20 bases or more, 2^31 target bases or more, more queries times targets than the 64-bit
+ * candidate key holds (bits(n_q) + bits(2 n_t) > 43), 2^32 seed hits or more.
+ * shn_cmprows_sizes: { rows, candidate diagonals, seed hits at the start of a run, index records }.
+ * shn_cmprows_export: rows_out[f * rows + r], f = query, target, strand (0 '+', 1 '-'), matches, mismatches, qStart, qEnd, tStart
+ * (on the target's forward strand; tEnd = tStart + qEnd - qStart).                                                                 */
+#define SHN_COMPARE_SEED 16
+#define SHN_COMPARE_MIN_MATCHES 30
+typedef struct shn_cmprows shn_cmprows;
+int shn_compare_rows(shn_ctx* ctx, const uint8_t* q_text, const uint64_t* q_off, uint64_t n_q, const uint8_t* t_text, const uint64_t* t_off,
+                     uint64_t n_t, int strand_specific, uint32_t min_matches, shn_cmprows** out);
+int shn_cmprows_sizes(const shn_cmprows* r, uint64_t* sizes4);
+int shn_cmprows_export(const shn_cmprows* r, uint32_t* rows_out);
+void shn_cmprows_destroy(shn_cmprows* r);
+
 #ifdef __cplusplus
 }
 #endif

@@ -183,6 +183,10 @@ SIGNATURES = {
     "shn_qmask_download": (C.c_int, [vp, vp, vp]),
     "shn_quorum_table": (C.c_int, [vp, vpp, vpp, C.c_int, C.c_int, vpp]),
     "shn_quorum_correct": (C.c_int, [vp, vp, vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vpp, vp]),
+    "shn_compare_rows": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_int, C.c_uint32, vpp]),
+    "shn_cmprows_sizes": (C.c_int, [vp, vp]),
+    "shn_cmprows_export": (C.c_int, [vp, vp]),
+    "shn_cmprows_destroy": (None, [vp]),
 }
 
 

@@ -61,7 +61,10 @@ enum {
   // --kallisto_cutoff (abundance.hip): index of the final transcripts, compatibility lists + span histogram, classes, the EM's rounds
   T_ABD_INDEX, T_ABD_MAP, T_ABD_CLASSES, T_ABD_EM,
   // --quorum (quorum.hip): can(w) of every high-quality window, the table of them (sort + run lengths), the per-read correction
-  T_QUORUM_COUNT, T_QUORUM_TABLE, T_QUORUM_CORRECT, T_N = 59
+  T_QUORUM_COUNT, T_QUORUM_TABLE, T_QUORUM_CORRECT,
+  // --compare (compare.hip): both texts packed + the index of the oriented targets' 16-mers, the candidate diagonals (count, scan,
+  // fill, sort, unique), the wave-per-diagonal scoring, best per pair + the rows
+  T_CMP_INDEX, T_CMP_SEEDS, T_CMP_SCORE, T_CMP_ROWS, T_N = 63
 };
 
 // grow-only device workspace slot (process-wide ones: g_shn_ws below; per-context ones: shn_ctx::cws)

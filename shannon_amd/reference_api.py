@@ -8,6 +8,7 @@ modules of the same names:
     algorithm_sf(comp, prefix)                                   algorithm_SF.py:39-63, 858-934 (the script)
     path_decompose(a, b, a_true, b_true, overwrite_norm, P, use_GLPK, sparsity)   path_decompose_sparse.py:15
     filter_FP(rec_fasta, read_1, read_2, out_dir, flags)         filter_FP.py:29
+    run_MB_SF_compare(dir_base, strand_specific)                 run_MB_SF_fn.py:283-302 (`run_MB_SF_fn.py <dir_base> --compare`)
 
 They read and write the reference's files (k1mer.dict_org / *_contig / component*.txt / remaining_contigs*.txt /
 reads{comp}.fasta / component{comp}k1mers_allowed.dict / nodes, edges, paths{c}.txt / reconstructed*.fasta).  The pipeline
@@ -299,3 +300,25 @@ def filter_FP(rec_fasta, read_1, read_2, out_dir, flags="-f --ff", ctx=None):
         f.write(log)
     with open(os.path.join(out_dir, "reconstructed.fasta"), "w") as f:
         f.write(kept)
+
+
+def run_MB_SF_compare(dir_base, strand_specific=False, ctx=None):
+    """`run_MB_SF_fn.py <dir_base> --compare` (run_MB_SF_fn.py:283-302, as shannon.py:622 starts it on <sample>_all): the known
+    transcripts <dir_base>algo_output/reference.fasta against <dir_base>algo_output/reconstructed.fasta.  The BLAT run
+    (parallel_blat_python.py, :299) is the rule of DESIGN.md 3.12 on the device; tester.analyzer_blat_noExp (:300) and
+    tester.false_positive (:302) are applied to its lines.  Writes reconstr_per.txt, reconstr_log.txt and reconstr_rev_log.txt into
+    <dir_base>algo_output/ and prints `rec,tot` (tester.py:313).  dir_base is a prefix, as there: it ends where `algo_output` begins.
+    strand_specific: the reconstructed transcripts are taken forward only (BLAT always looks at both strands)."""
+    from . import compare
+    ctx = ctx or default_context()
+    out = dir_base + "algo_output"
+    with open(os.path.join(out, "reference.fasta")) as f:
+        ref_text = f.read()
+    with open(os.path.join(out, "reconstructed.fasta")) as f:
+        rec_text = f.read()
+    texts, st = compare.compare_texts(ctx, ref_text, rec_text, strand_specific)
+    for name, text in sorted(texts.items()):
+        with open(os.path.join(out, name), "w") as f:
+            f.write(text)
+    print("%d,%d" % (st["rec"], st["tot"]))
+    return st

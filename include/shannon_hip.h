@@ -766,6 +766,23 @@ int shn_cmprows_sizes(const shn_cmprows* r, uint64_t* sizes4);
 int shn_cmprows_export(const shn_cmprows* r, uint32_t* rows_out);
 void shn_cmprows_destroy(shn_cmprows* r);
 
+/* shn_compare_chains: the chained form of the rule ("Chained rows").  The arguments, refusals and limits are
+ * shn_compare_rows' (the messages name that call); index, seeds and score are the same launches.  Every candidate diagonal of a
+ * (query, target, orientation) gives one block, its best segment; a block may follow another on a different diagonal if it keeps
+ * at least one position once it is trimmed to start behind the other in both sequences; the chain of greatest (sum of scores, sum
+ * of matches, fewest blocks) over both orientations gives the pair's row if it holds min_matches matches or more.  The object
+ * answers shn_cmprows_sizes / shn_cmprows_export as above with matches and mismatches summed over the blocks, qStart of the first
+ * block, qEnd of the last and tStart of the whole chain on the forward strand (tEnd is NOT tStart + qEnd - qStart: take it from the
+ * blocks), and two calls of its own, which refuse an object of shn_compare_rows with SHN_ERR_ARG:
+ * shn_cmprows_chain_sizes: { blocks of all rows, (query, target, orientation) groups chained, rows of more than one block }.
+ * shn_cmprows_chain_export: gaps_out[f * rows + r], f = qNumInsert, qBaseInsert, tNumInsert, tBaseInsert, blockCount;
+ * block_off_out[rows + 1]: row r's blocks are block_off_out[r] .. block_off_out[r + 1] - 1, in chain order;
+ * blocks_out[f * blocks + k], f = size, qStart, tStart (on the target's forward strand).                                          */
+int shn_compare_chains(shn_ctx* ctx, const uint8_t* q_text, const uint64_t* q_off, uint64_t n_q, const uint8_t* t_text, const uint64_t* t_off,
+                       uint64_t n_t, int strand_specific, uint32_t min_matches, shn_cmprows** out);
+int shn_cmprows_chain_sizes(const shn_cmprows* r, uint64_t* sizes3);
+int shn_cmprows_chain_export(const shn_cmprows* r, uint32_t* gaps_out, uint64_t* block_off_out, uint32_t* blocks_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,9 @@ SIGNATURES = {
     "shn_cmprows_sizes": (C.c_int, [vp, vp]),
     "shn_cmprows_export": (C.c_int, [vp, vp]),
     "shn_cmprows_destroy": (None, [vp]),
+    "shn_compare_chains": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_int, C.c_uint32, vpp]),
+    "shn_cmprows_chain_sizes": (C.c_int, [vp, vp]),
+    "shn_cmprows_chain_export": (C.c_int, [vp, vp, vp, vp]),
 }
 
 

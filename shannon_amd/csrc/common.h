@@ -63,8 +63,9 @@ enum {
   // --quorum (quorum.hip): can(w) of every high-quality window, the table of them (sort + run lengths), the per-read correction
   T_QUORUM_COUNT, T_QUORUM_TABLE, T_QUORUM_CORRECT,
   // --compare (compare.hip): both texts packed + the index of the oriented targets' 16-mers, the candidate diagonals (count, scan,
-  // fill, sort, unique), the wave-per-diagonal scoring, best per pair + the rows
-  T_CMP_INDEX, T_CMP_SEEDS, T_CMP_SCORE, T_CMP_ROWS, T_N = 63
+  // fill, sort, unique), the wave-per-diagonal scoring, best per pair + the rows; the chained rows (block order, the wave-per-group
+  // chaining, the pair's orientation, rows and blocks)
+  T_CMP_INDEX, T_CMP_SEEDS, T_CMP_SCORE, T_CMP_ROWS, T_CMP_CHAIN, T_N = 64
 };
 
 // grow-only device workspace slot (process-wide ones: g_shn_ws below; per-context ones: shn_ctx::cws)

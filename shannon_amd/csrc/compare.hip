@@ -14,6 +14,11 @@
 //           in order through shuffles, a carry across passes of 2,048 bases (compare_dev.h holds the summary).
 //   rows    the first candidate of a pair walks the pair's candidates for the best; pairs of 30 matches or more are counted,
 //           scanned and filled into the row arrays.
+//   chain   (shn_compare_chains, in place of rows) every scored diagonal of a (query, target, orientation) is a block; one stable
+//           sort puts a group's blocks in the order (qEnd, diagonal); a wave per group chains them -- per block the lanes stride over
+//           its possible predecessors, trim it against each (compare_dev.h: the join and the trim count) and reduce to the best
+//           link through shuffles; the pair's better orientation is picked, rows and blocks are counted, scanned and a thread per
+//           row walks its chain back and writes the row and its blocks.
 #include "common.h"
 #include "filter_fp_dev.h"
 #include "compare_dev.h"
@@ -235,6 +240,166 @@ __global__ void cmp_rows_kernel(CmpText T, const uint64_t* __restrict__ cand, ui
   }
 }
 
+// ---- the chained form: a pair's diagonals joined into one multi-block row ("Chained rows")
+constexpr int CMP_QBITS = 20;                       // a qEnd (sequences are shorter than 2^20 bases)
+
+// block order: key = (query, 2 target + orientation, qEnd), value = the candidate; the candidates come sorted by diagonal inside
+// an oriented pair, which a stable sort by this key keeps as the tie
+__global__ void cmp_chain_keys_kernel(const uint64_t* __restrict__ cand, const uint32_t* __restrict__ len, const uint32_t* __restrict__ q0, uint64_t n_cand,
+                                      uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  CMP_FOR(c, n_cand) {
+    keys[c] = ((cand[c] >> CMP_DBITS) << CMP_QBITS) | (uint64_t)(q0[c] + len[c]);
+    vals[c] = (uint32_t)c;
+  }
+}
+// block p of the order = candidate perm[p]; head[p]: the first block of its (query, target, orientation)
+__global__ void cmp_blocks_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ perm, uint64_t n_cand, const uint64_t* __restrict__ cand,
+                                  const int32_t* __restrict__ s, const uint32_t* __restrict__ len, const uint32_t* __restrict__ q0, CmpBlock* __restrict__ blk,
+                                  uint32_t* __restrict__ head) {
+  CMP_FOR(p, n_cand) {
+    const uint32_t c = perm[p];
+    CmpBlock b;
+    b.d = (int32_t)((int64_t)(cand[c] & ((1ULL << CMP_DBITS) - 1)) - (int64_t)CMP_DBIAS);
+    b.q0 = q0[c]; b.len = len[c]; b.s = s[c];
+    blk[p] = b;
+    head[p] = (p == 0 || (keys[p] >> CMP_QBITS) != (keys[p - 1] >> CMP_QBITS)) ? 1u : 0u;
+  }
+}
+__global__ void cmp_group_starts_kernel(const uint32_t* __restrict__ head, const uint64_t* __restrict__ gpos, uint64_t n_cand, uint64_t n_groups,
+                                        uint32_t* __restrict__ gstart) {
+  CMP_FOR(p, n_cand) {
+    if (head[p]) gstart[gpos[p]] = (uint32_t)p;
+    if (p == 0) gstart[n_groups] = (uint32_t)n_cand;
+  }
+}
+
+struct CmpGroup { uint64_t i, j, t; uint32_t o; };
+__device__ __forceinline__ CmpGroup cmp_group_of(uint64_t key, int jo_bits, uint64_t m) {
+  CmpGroup g;
+  const uint64_t k = key >> CMP_QBITS, jo = k & ((1ULL << jo_bits) - 1);
+  g.i = k >> jo_bits; g.j = jo >> 1; g.o = (uint32_t)(jo & 1);
+  g.t = g.o ? m + g.j : g.j;
+  return g;
+}
+__device__ __forceinline__ CmpLink cmp_shfl_down(const CmpLink& x, int off) {
+  CmpLink y;
+  y.S = __shfl_down(x.S, off, 64); y.M = __shfl_down(x.M, off, 64); y.R = __shfl_down(x.R, off, 64);
+  y.pred = __shfl_down(x.pred, off, 64); y.v = __shfl_down(x.v, off, 64); y.m = __shfl_down(x.m, off, 64);
+  return y;
+}
+
+// One wave a (query, target, orientation) group: its blocks b0 .. b1 - 1 one after the other; for block b the lanes stride over
+// the blocks in front of it (lane l takes b0 + l, b0 + l + 64, ..), each forms the overlap v, the trimmed block and the value of
+// the best chain into a followed by it (cmp_link_after), keeps its best, and the wave reduces through __shfl_down at strides
+// 1, 2, .. 32 under cmp_link_before -- a total order, so lane 0 ends with the greatest value and of equals the smallest
+// predecessor.  Lane 0 writes st[b]; the lanes read it in later rounds, so a fence stands between the rounds (st is neither
+// const nor restrict).  A group of one block is a copy.  top[g]: the best chain of the group, its pred field naming its LAST
+// block (the first of equals: the smallest index).  A group of r blocks takes about r^2 / 64 steps of its wave.
+__global__ __launch_bounds__(CMP_BLK) void cmp_chain_kernel(CmpText Q, CmpText T, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ gstart,
+                                                            uint64_t n_groups, uint64_t m, int jo_bits, const CmpBlock* __restrict__ blk, CmpLink* st,
+                                                            CmpLink* __restrict__ top) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t n_waves = (uint64_t)gridDim.x * (CMP_BLK / 64);
+  for (uint64_t g = (uint64_t)blockIdx.x * (CMP_BLK / 64) + (threadIdx.x >> 6); g < n_groups; g += n_waves) {
+    const uint32_t b0 = gstart[g], b1 = gstart[g + 1];
+    const CmpGroup G = cmp_group_of(keys[b0], jo_bits, m);
+    const uint64_t qo = Q.off[G.i], to = T.off[G.t];
+    CmpLink best = cmp_link_none();
+    for (uint32_t b = b0; b < b1; b++) {
+      const CmpBlock B = blk[b];
+      CmpLink x = cmp_link_none();
+      if (b > b0) {
+        for (uint32_t a = b0 + lane; a < b; a += 64) {
+          uint32_t v;
+          if (!cmp_joins(blk[a], B, &v)) continue;
+          const uint32_t mt = v ? cmp_trim_matches(Q.w, Q.nm, T.w, T.nm, qo + B.q0, to + (uint64_t)((int64_t)B.q0 + B.d), v) : 0u;
+          const CmpLink y = cmp_link_after(st[a], a, B, v, mt);
+          if (cmp_link_before(y, x)) x = y;
+        }
+        for (int off = 1; off < 64; off <<= 1) {
+          const CmpLink y = cmp_shfl_down(x, off);
+          if (cmp_link_before(y, x)) x = y;
+        }
+      }
+      if (lane == 0) {
+        const CmpLink own = cmp_link_alone(B);
+        if (!cmp_value_greater(x, own)) x = own;              // (their block counts differ: never equal)
+        st[b] = x;
+        if (cmp_value_greater(x, best)) { best = x; best.pred = b; }
+      }
+      if (b + 1 < b1) __threadfence();
+    }
+    if (lane == 0) top[g] = best;
+  }
+}
+
+// The first group of a (query, target) pair picks the pair's orientation: the greater value, '+' of equals.  keep: the chain
+// holds min_matches matches or more; nblk: its blocks (0 where no row is written).
+__global__ void cmp_chain_pick_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ gstart, uint64_t n_groups, const CmpLink* __restrict__ top,
+                                      uint32_t min_matches, uint32_t* __restrict__ keep, uint32_t* __restrict__ nblk, uint32_t* __restrict__ win) {
+  CMP_FOR(g, n_groups) {
+    const uint64_t pair = keys[gstart[g]] >> (CMP_QBITS + 1);
+    uint32_t k = 0, nb = 0;
+    if (g == 0 || (keys[gstart[g - 1]] >> (CMP_QBITS + 1)) != pair) {
+      uint64_t w = g;
+      if (g + 1 < n_groups && (keys[gstart[g + 1]] >> (CMP_QBITS + 1)) == pair && cmp_value_greater(top[g + 1], top[g])) w = g + 1;
+      win[g] = (uint32_t)w;
+      if (top[w].M >= min_matches) { k = 1; nb = top[w].R; }
+    }
+    keep[g] = k;
+    nblk[g] = nb;
+  }
+}
+
+// A thread per row: walks the winning chain back from its last block and writes the blocks in chain order.
+// rows[f * n_rows + r]: the eight columns of cmp_rows_kernel (matches and mismatches summed over the blocks, qStart of the first
+// block, qEnd of the last, tStart of the whole on the forward strand); gaps[f * n_rows + r], f = qNumInsert, qBaseInsert,
+// tNumInsert, tBaseInsert, blockCount; blocks[f * n_blocks + k], f = size, qStart, tStart (forward strand)
+__global__ void cmp_chain_rows_kernel(CmpText T, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ gstart, uint64_t n_groups, uint64_t m, int jo_bits,
+                                      const CmpBlock* __restrict__ blk, const CmpLink* __restrict__ st, const CmpLink* __restrict__ top,
+                                      const uint32_t* __restrict__ keep, const uint32_t* __restrict__ win, const uint64_t* __restrict__ rpos,
+                                      const uint64_t* __restrict__ bpos, uint64_t n_rows, uint64_t n_blocks, uint32_t* __restrict__ rows,
+                                      uint32_t* __restrict__ gaps, uint32_t* __restrict__ blocks) {
+  CMP_FOR(g, n_groups) {
+    if (!keep[g]) continue;
+    const uint32_t w = win[g];
+    const CmpLink C = top[w];
+    const CmpGroup G = cmp_group_of(keys[gstart[w]], jo_bits, m);
+    const int64_t Lt = (int64_t)(T.off[G.t + 1] - T.off[G.t]);
+    const uint64_t r = rpos[g], bp = bpos[g];
+    uint32_t e = C.pred, k = C.R, qn = 0, qb = 0, tn = 0, tb = 0, q_first = 0;
+    const uint32_t q_end = blk[e].q0 + blk[e].len;
+    const int64_t t_end = (int64_t)q_end + blk[e].d;
+    int64_t t_first = 0;
+    while (k) {
+      k--;
+      const CmpBlock B = blk[e];
+      const CmpLink L = st[e];
+      const uint32_t size = B.len - L.v, qs = B.q0 + L.v;
+      const int64_t ts = (int64_t)qs + B.d;
+      blocks[bp + k] = size;
+      blocks[n_blocks + bp + k] = qs;
+      blocks[2 * n_blocks + bp + k] = (uint32_t)(G.o ? Lt - (ts + (int64_t)size) : ts);
+      if (L.pred == CMP_NONE) { q_first = qs; t_first = ts; break; }
+      const CmpBlock A = blk[L.pred];
+      const int64_t qg = (int64_t)qs - ((int64_t)A.q0 + A.len), tg = ts - ((int64_t)A.q0 + A.len + A.d);
+      if (qg > 0) { qn++; qb += (uint32_t)qg; }
+      if (tg > 0) { tn++; tb += (uint32_t)tg; }
+      e = L.pred;
+    }
+    rows[r] = (uint32_t)G.i;
+    rows[n_rows + r] = (uint32_t)G.j;
+    rows[2 * n_rows + r] = G.o;
+    rows[3 * n_rows + r] = C.M;
+    rows[4 * n_rows + r] = (uint32_t)((int32_t)C.M - C.S) / 2u;
+    rows[5 * n_rows + r] = q_first;
+    rows[6 * n_rows + r] = q_end;
+    rows[7 * n_rows + r] = (uint32_t)(G.o ? Lt - t_end : t_first);
+    gaps[r] = qn; gaps[n_rows + r] = qb; gaps[2 * n_rows + r] = tn; gaps[3 * n_rows + r] = tb; gaps[4 * n_rows + r] = C.R;
+  }
+}
+
+
 int bits_for(uint64_t n) { int b = 1; while (b < 63 && (n - 1) >> b) b++; return b; }          // bits that hold 0 .. n - 1 (n >= 1)
 
 int check_offsets(const char* what, const uint64_t* off, uint64_t n) {
@@ -277,10 +442,74 @@ int pack_text(shn_ctx* ctx, ShnDevBufs& B, const uint8_t* text, const uint64_t* 
 struct shn_cmprows {
   uint64_t n_rows = 0, n_hits = 0, n_cand = 0, n_rec = 0;
   std::vector<uint32_t> rows;          // 8 columns of n_rows
+  // shn_compare_chains alone
+  bool chained = false;
+  uint64_t n_blocks = 0, n_groups = 0;
+  std::vector<uint32_t> gaps;          // 5 columns of n_rows: qNumInsert, qBaseInsert, tNumInsert, tBaseInsert, blockCount
+  std::vector<uint32_t> blocks;        // 3 columns of n_blocks: size, qStart, tStart; a row's blocks lie together, rows in order
 };
 
-extern "C" int shn_compare_rows(shn_ctx* ctx, const uint8_t* q_text, const uint64_t* q_off, uint64_t n_q, const uint8_t* t_text, const uint64_t* t_off,
-                                uint64_t n_t, int strand_specific, uint32_t min_matches, shn_cmprows** out) {
+namespace {
+
+// The chained rows from the scored candidates: block order (one stable sort), groups, the chain kernel, the pair's orientation,
+// two scans and the rows with their blocks.
+int chain_rows(shn_ctx* ctx, ShnDevBufs& B, const CmpText& Q, const CmpText& T, const uint64_t* d_ucand, uint64_t n_cand, uint64_t n_t, int i_shift, int i_bits,
+               const int32_t* d_s, const uint32_t* d_len, const uint32_t* d_q0, uint32_t min_matches, shn_cmprows* R) {
+  hipStream_t s = ctx->stream;
+  int rc;
+  const int jo_bits = i_shift - CMP_DBITS, key_bits = CMP_QBITS + jo_bits + i_bits;
+  uint64_t *d_keys = nullptr, *d_keys_tmp = nullptr, *d_gpos = nullptr, *d_rpos = nullptr, *d_bpos = nullptr;
+  uint32_t *d_perm = nullptr, *d_perm_tmp = nullptr, *d_head = nullptr, *d_gstart = nullptr, *d_keep = nullptr, *d_nblk = nullptr, *d_win = nullptr;
+  uint32_t *d_rows = nullptr, *d_gaps = nullptr, *d_blocks = nullptr;
+  CmpBlock* d_blk = nullptr;
+  CmpLink *d_st = nullptr, *d_top = nullptr;
+  uint64_t n_groups = 0, n_rows = 0, n_blocks = 0;
+  HIP_TRY(B.get(&d_keys, (n_cand + 1) * 8)); HIP_TRY(B.get(&d_keys_tmp, (n_cand + 1) * 8));
+  HIP_TRY(B.get(&d_perm, (n_cand + 1) * 4)); HIP_TRY(B.get(&d_perm_tmp, (n_cand + 1) * 4));
+  HIP_TRY(B.get(&d_head, (n_cand + 1) * 4)); HIP_TRY(B.get(&d_gpos, (n_cand + 2) * 8));
+  HIP_TRY(B.get(&d_blk, n_cand * sizeof(CmpBlock))); HIP_TRY(B.get(&d_st, n_cand * sizeof(CmpLink)));
+  TimerRegion treg(ctx, T_CMP_CHAIN);
+  hipLaunchKernelGGL(cmp_chain_keys_kernel, dim3(cmp_grid(n_cand)), dim3(CMP_BLK), 0, s, d_ucand, d_len, d_q0, n_cand, d_keys, d_perm);
+  if ((rc = shn_sort_pairs(ctx, d_keys, d_perm, d_keys_tmp, d_perm_tmp, n_cand, 0, key_bits))) return rc;
+  hipLaunchKernelGGL(cmp_blocks_kernel, dim3(cmp_grid(n_cand)), dim3(CMP_BLK), 0, s, (const uint64_t*)d_keys, (const uint32_t*)d_perm, n_cand, d_ucand, d_s, d_len, d_q0,
+                     d_blk, d_head);
+  if ((rc = shn_device_scan_u32(ctx, d_head, n_cand, d_gpos, &n_groups))) return rc;
+  HIP_TRY(B.get(&d_gstart, (n_groups + 1) * 4)); HIP_TRY(B.get(&d_top, n_groups * sizeof(CmpLink)));
+  HIP_TRY(B.get(&d_keep, (n_groups + 1) * 4)); HIP_TRY(B.get(&d_nblk, (n_groups + 1) * 4)); HIP_TRY(B.get(&d_win, n_groups * 4));
+  HIP_TRY(B.get(&d_rpos, (n_groups + 2) * 8)); HIP_TRY(B.get(&d_bpos, (n_groups + 2) * 8));
+  hipLaunchKernelGGL(cmp_group_starts_kernel, dim3(cmp_grid(n_cand)), dim3(CMP_BLK), 0, s, (const uint32_t*)d_head, (const uint64_t*)d_gpos, n_cand, n_groups, d_gstart);
+  hipLaunchKernelGGL(cmp_chain_kernel, dim3((uint32_t)std::min<uint64_t>(cdiv(n_groups, CMP_BLK / 64), 1u << 20)), dim3(CMP_BLK), 0, s, Q, T, (const uint64_t*)d_keys,
+                     (const uint32_t*)d_gstart, n_groups, n_t, jo_bits, (const CmpBlock*)d_blk, d_st, d_top);
+  hipLaunchKernelGGL(cmp_chain_pick_kernel, dim3(cmp_grid(n_groups)), dim3(CMP_BLK), 0, s, (const uint64_t*)d_keys, (const uint32_t*)d_gstart, n_groups,
+                     (const CmpLink*)d_top, min_matches, d_keep, d_nblk, d_win);
+  HIP_TRY(hipGetLastError());
+  if ((rc = shn_device_scan_u32(ctx, d_keep, n_groups, d_rpos, &n_rows))) return rc;
+  if ((rc = shn_device_scan_u32(ctx, d_nblk, n_groups, d_bpos, &n_blocks))) return rc;
+  // bytes: per candidate its key, length and start read and the sort pair written (16 + 12 B), the sort's passes (24 B a pass), the
+  // pair, key and three results read and the block and its head flag written, scanned and read (36 + 20 + 20 B), a block read and
+  // its link written by the chain kernel (16 + 24 B; the blocks in front of it and the trimmed stretches of the packed texts come
+  // from the caches); per group its start, best chain, three flags and two scans (4 + 24 + 12 + 40 B); per row 13 values and per
+  // block 3 written with the block and link they are made of (52 B, 12 + 40 B)
+  treg.bytes(n_cand * (28 + 76 + 40) + (uint64_t)((key_bits + 7) / 8) * n_cand * 24 + n_groups * 80 + n_rows * 52 + n_blocks * 52);
+  R->n_rows = n_rows; R->n_blocks = n_blocks; R->n_groups = n_groups;
+  R->rows.resize(n_rows * 8); R->gaps.resize(n_rows * 5); R->blocks.resize(n_blocks * 3);
+  if (n_rows) {
+    HIP_TRY(B.get(&d_rows, n_rows * 8 * 4)); HIP_TRY(B.get(&d_gaps, n_rows * 5 * 4)); HIP_TRY(B.get(&d_blocks, n_blocks * 3 * 4));
+    hipLaunchKernelGGL(cmp_chain_rows_kernel, dim3(cmp_grid(n_groups)), dim3(CMP_BLK), 0, s, T, (const uint64_t*)d_keys, (const uint32_t*)d_gstart, n_groups, n_t, jo_bits,
+                       (const CmpBlock*)d_blk, (const CmpLink*)d_st, (const CmpLink*)d_top, (const uint32_t*)d_keep, (const uint32_t*)d_win, (const uint64_t*)d_rpos,
+                       (const uint64_t*)d_bpos, n_rows, n_blocks, d_rows, d_gaps, d_blocks);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(R->rows.data(), d_rows, n_rows * 8 * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(R->gaps.data(), d_gaps, n_rows * 5 * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(R->blocks.data(), d_blocks, n_blocks * 3 * 4, hipMemcpyDeviceToHost, s));
+  }
+  return SHN_OK;
+}
+
+
+// shn_compare_rows (chain == false) and shn_compare_chains: one path up to the scored candidates
+int compare_rows(shn_ctx* ctx, const uint8_t* q_text, const uint64_t* q_off, uint64_t n_q, const uint8_t* t_text, const uint64_t* t_off, uint64_t n_t,
+                 int strand_specific, uint32_t min_matches, bool chain, shn_cmprows** out) {
   if (!ctx || !q_off || !t_off || !out) return shn_fail(SHN_ERR_ARG, "shn_compare_rows: NULL argument");
   *out = nullptr;
   int rc;
@@ -298,6 +527,7 @@ extern "C" int shn_compare_rows(shn_ctx* ctx, const uint8_t* q_text, const uint6
   const uint64_t n_rec = rec_off[n_o];
   shn_cmprows* R = new shn_cmprows();
   R->n_rec = n_rec;
+  R->chained = chain;
   *out = R;
   if (n_q == 0 || q_off[n_q] < CMP_SEED || n_rec == 0) return SHN_OK;
   struct Guard { shn_cmprows** o; bool ok = false; ~Guard() { if (!ok) { delete *o; *o = nullptr; } } } guard{out};
@@ -363,7 +593,7 @@ extern "C" int shn_compare_rows(shn_ctx* ctx, const uint8_t* q_text, const uint6
   uint32_t *d_len = nullptr, *d_q0 = nullptr, *d_keep = nullptr, *d_best = nullptr, *d_rows = nullptr;
   uint64_t* d_rpos = nullptr;
   HIP_TRY(B.get(&d_s, n_cand * 4)); HIP_TRY(B.get(&d_len, n_cand * 4)); HIP_TRY(B.get(&d_q0, n_cand * 4));
-  HIP_TRY(B.get(&d_keep, (n_cand + 1) * 4)); HIP_TRY(B.get(&d_best, n_cand * 4)); HIP_TRY(B.get(&d_rpos, (n_cand + 2) * 8));
+  if (!chain) { HIP_TRY(B.get(&d_keep, (n_cand + 1) * 4)); HIP_TRY(B.get(&d_best, n_cand * 4)); HIP_TRY(B.get(&d_rpos, (n_cand + 2) * 8)); }
   {
     TimerRegion treg(ctx, T_CMP_SCORE);
     // bytes: a candidate read (8 B), four offsets (32 B), three results written (12 B); the diagonals' bases come from the packed
@@ -372,6 +602,15 @@ extern "C" int shn_compare_rows(shn_ctx* ctx, const uint8_t* q_text, const uint6
     hipLaunchKernelGGL(cmp_score_kernel, dim3((uint32_t)std::min<uint64_t>(cdiv(n_cand, CMP_BLK / 64), 1u << 20)), dim3(CMP_BLK), 0, s, Q, T, (const uint64_t*)d_ucand, n_cand,
                        n_t, i_shift, d_s, d_len, d_q0);
     HIP_TRY(hipGetLastError());
+  }
+
+  // ---- chained rows
+  if (chain) {
+    if ((rc = chain_rows(ctx, B, Q, T, d_ucand, n_cand, n_t, i_shift, i_bits, d_s, d_len, d_q0, min_matches, R))) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    guard.ok = true;
+    return SHN_OK;
   }
 
   // ---- rows
@@ -397,6 +636,37 @@ extern "C" int shn_compare_rows(shn_ctx* ctx, const uint8_t* q_text, const uint6
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipGetLastError());
   guard.ok = true;
+  return SHN_OK;
+}
+
+}  // namespace
+
+extern "C" int shn_compare_rows(shn_ctx* ctx, const uint8_t* q_text, const uint64_t* q_off, uint64_t n_q, const uint8_t* t_text, const uint64_t* t_off,
+                                uint64_t n_t, int strand_specific, uint32_t min_matches, shn_cmprows** out) {
+  return compare_rows(ctx, q_text, q_off, n_q, t_text, t_off, n_t, strand_specific, min_matches, false, out);
+}
+
+extern "C" int shn_compare_chains(shn_ctx* ctx, const uint8_t* q_text, const uint64_t* q_off, uint64_t n_q, const uint8_t* t_text, const uint64_t* t_off,
+                                  uint64_t n_t, int strand_specific, uint32_t min_matches, shn_cmprows** out) {
+  return compare_rows(ctx, q_text, q_off, n_q, t_text, t_off, n_t, strand_specific, min_matches, true, out);
+}
+
+extern "C" int shn_cmprows_chain_sizes(const shn_cmprows* r, uint64_t* sizes3) {
+  if (!r || !sizes3) return shn_fail(SHN_ERR_ARG, "shn_cmprows_chain_sizes: NULL argument");
+  if (!r->chained) return shn_fail(SHN_ERR_ARG, "shn_cmprows_chain_sizes: the rows are shn_compare_rows', not shn_compare_chains'");
+  uint64_t multi = 0;
+  for (uint64_t k = 0; k < r->n_rows; k++) multi += r->gaps[4 * r->n_rows + k] > 1 ? 1 : 0;
+  sizes3[0] = r->n_blocks; sizes3[1] = r->n_groups; sizes3[2] = multi;
+  return SHN_OK;
+}
+
+extern "C" int shn_cmprows_chain_export(const shn_cmprows* r, uint32_t* gaps_out, uint64_t* block_off_out, uint32_t* blocks_out) {
+  if (!r || !block_off_out || (r->n_rows && (!gaps_out || !blocks_out))) return shn_fail(SHN_ERR_ARG, "shn_cmprows_chain_export: NULL argument");
+  if (!r->chained) return shn_fail(SHN_ERR_ARG, "shn_cmprows_chain_export: the rows are shn_compare_rows', not shn_compare_chains'");
+  std::copy(r->gaps.begin(), r->gaps.end(), gaps_out);
+  std::copy(r->blocks.begin(), r->blocks.end(), blocks_out);
+  block_off_out[0] = 0;
+  for (uint64_t k = 0; k < r->n_rows; k++) block_off_out[k + 1] = block_off_out[k] + r->gaps[4 * r->n_rows + k];
   return SHN_OK;
 }
 

@@ -302,13 +302,14 @@ def filter_FP(rec_fasta, read_1, read_2, out_dir, flags="-f --ff", ctx=None):
         f.write(kept)
 
 
-def run_MB_SF_compare(dir_base, strand_specific=False, ctx=None):
+def run_MB_SF_compare(dir_base, strand_specific=False, ctx=None, chain=False):
     """`run_MB_SF_fn.py <dir_base> --compare` (run_MB_SF_fn.py:283-302, as shannon.py:622 starts it on <sample>_all): the known
     transcripts <dir_base>algo_output/reference.fasta against <dir_base>algo_output/reconstructed.fasta.  The BLAT run
     (parallel_blat_python.py, :299) is the rule of DESIGN.md 3.12 on the device; tester.analyzer_blat_noExp (:300) and
     tester.false_positive (:302) are applied to its lines.  Writes reconstr_per.txt, reconstr_log.txt and reconstr_rev_log.txt into
     <dir_base>algo_output/ and prints `rec,tot` (tester.py:313).  dir_base is a prefix, as there: it ends where `algo_output` begins.
-    strand_specific: the reconstructed transcripts are taken forward only (BLAT always looks at both strands)."""
+    strand_specific: the reconstructed transcripts are taken forward only (BLAT always looks at both strands).  chain: the chained
+    form of the rule (multi-block lines, as BLAT writes them for a transcript with a skipped exon or an indel)."""
     from . import compare
     ctx = ctx or default_context()
     out = dir_base + "algo_output"
@@ -316,7 +317,7 @@ def run_MB_SF_compare(dir_base, strand_specific=False, ctx=None):
         ref_text = f.read()
     with open(os.path.join(out, "reconstructed.fasta")) as f:
         rec_text = f.read()
-    texts, st = compare.compare_texts(ctx, ref_text, rec_text, strand_specific)
+    texts, st = compare.compare_texts(ctx, ref_text, rec_text, strand_specific, chain)
     for name, text in sorted(texts.items()):
         with open(os.path.join(out, name), "w") as f:
             f.write(text)

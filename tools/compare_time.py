@@ -6,7 +6,10 @@ and the sum of its stage seconds (from its log), the call's wall time (median, m
 events, with the launch sites' byte models) of the median call, index records / seed hits / candidate diagonals / rows, and the two
 summary lines of reconstr_log.txt with false_positive's `rec,tot`.
 
-    python tools/compare_time.py --pairs 1000000 --genes 1000 [--repeats 5]
+    python tools/compare_time.py --pairs 1000000 --genes 1000 [--repeats 5] [--chain]
+
+--chain: the chained form of the rule (compare_texts(chain=True)): the compare.chain group stands where compare.rows stood, and the
+output also holds the blocks, the (query, target, orientation) groups chained and the rows with more than one block.
 
 --dump DIR: the planted transcripts of a bench config against the final transcripts `bench.py --dump-outputs DIR` left there
 (--genes / --exon-len / --seed as that run's preset; bench.py's default is --config 2: 20000 genes, exons 80 .. 600).  The dump holds
@@ -22,20 +25,21 @@ def spread(v):
     return {"median": round(statistics.median(v), 5), "min": round(min(v), 5), "max": round(max(v), 5), "n": len(v)}
 
 
-def timed_compare(ctx, ref_text, rec_text, strand_specific, repeats):
+def timed_compare(ctx, ref_text, rec_text, strand_specific, repeats, chain=False):
     from shannon_amd import compare
-    texts, st = compare.compare_texts(ctx, ref_text, rec_text, strand_specific)          # warm-up: code objects, workspaces
+    texts, st = compare.compare_texts(ctx, ref_text, rec_text, strand_specific, chain)   # warm-up: code objects, workspaces
     runs = []
     for _ in range(repeats):
         ctx.timer_reset()
         t0 = time.time()
-        texts, st = compare.compare_texts(ctx, ref_text, rec_text, strand_specific)
+        texts, st = compare.compare_texts(ctx, ref_text, rec_text, strand_specific, chain)
         wall = time.time() - t0
         tm, tb = ctx.timers(), ctx.timer_bytes()
         runs.append((wall, {k: {"ms": round(v[0], 4), "regions": v[1], "bytes": tb.get(k, 0)} for k, v in sorted(tm.items()) if k.startswith("compare.")}))
     runs.sort(key=lambda r: r[0])
     summary = [l for l in texts["reconstr_log.txt"].splitlines() if l.startswith("#")]
-    return {"compare_s": spread([r[0] for r in runs]), "kernels_of_median_call": runs[len(runs) // 2][1],
+    extra = {k: st[k] for k in ("blocks", "groups", "multi_block_rows") if k in st}
+    return {"chain": bool(chain), **extra, "compare_s": spread([r[0] for r in runs]), "kernels_of_median_call": runs[len(runs) // 2][1],
             "kernel_ms_sum_of_median_call": round(sum(k["ms"] for k in runs[len(runs) // 2][1].values()), 4),
             "records": st["records"], "hits": st["hits"], "candidates": st["candidates"], "rows": st["rows"], "summary": summary,
             "rec,tot": "%d,%d" % (st["rec"], st["tot"]), "ref_transcripts": ref_text.count(">"), "ref_bases": len(ref_text) - ref_text.count("\n"),
@@ -54,6 +58,7 @@ def main():
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--exon-len", type=int, nargs=2, default=(80, 600))
     ap.add_argument("--dump", default=None)
+    ap.add_argument("--chain", action="store_true")
     a = ap.parse_args()
     import numpy as np
     from shannon_amd import synth, device
@@ -67,7 +72,7 @@ def main():
         off = np.concatenate([[0], np.cumsum(lens[pick])])
         rec_text = fasta_of(("X%d" % j, bases[off[k]:off[k + 1]]) for k, j in enumerate(pick.tolist()))
         ctx = device.Context(0)
-        out = timed_compare(ctx, ref_text, rec_text, False, a.repeats)
+        out = timed_compare(ctx, ref_text, rec_text, False, a.repeats, a.chain)
         ctx.close()
         out.update(dump=a.dump, genes=a.genes, final_transcripts=int(len(lens)), dumped=int(len(pick)),
                    note="all final transcripts" if len(pick) == len(lens) else "a seeded SAMPLE of the final transcripts: the summary bounds the recovery from below")
@@ -91,7 +96,7 @@ def main():
             asm.append({"wall_s": round(wall, 4), "stages_s": round(sum(v for k, v in stages.items() if isinstance(v, float) and ": " not in k), 4)})
         rec_text = open(os.path.join(out, "shannon.fasta")).read()
     ctx = device.Context(0)
-    res = timed_compare(ctx, ref_text, rec_text, False, a.repeats)
+    res = timed_compare(ctx, ref_text, rec_text, False, a.repeats, a.chain)
     ctx.close()
     res.update(pairs=a.pairs, genes=a.genes, assembly_first_run=asm[0], assembly=asm[1])
     print(json.dumps(res))

@@ -187,6 +187,9 @@ int shn_debug_read(shn_ctx* ctx, const void* p, uint64_t n_words, uint32_t* host
  *                         [bit_lo, bit_hi), 0 <= bit_lo, bit_hi <= 64 (csrc/sort.hip; the contract is stated in csrc/common.h)
  *   shn_debug_scan_u32    exclusive sums of n 32-bit numbers as n + 1 64-bit ones, out[n] = the total; total != NULL: the form that
  *                         also hands the total to the host (and synchronises), NULL: the device-only form
+ *   shn_debug_sorted_runs the runs of equal (key >> shift) of n keys sorted by it (csrc/runs.h, shn_sorted_runs): keys_out[r] the first
+ *                         key of run r, start_out[r] its first element with start_out[n_runs] = n, len_out[r] its length, pos_out the
+ *                         n + 1 exclusive sums of the head flags; keys_out / len_out hold n, start_out and pos_out n + 1 elements
  *   shn_debug_table_find  idx_out[i] = index of keys[i] in the table's key array (the order of shn_table_download) or -1, one thread
  *                         per query; variant 0: shn_table_find (bisection), 1: shn_table_find_k (interpolated first guess, gallop;
  *                         key width 2 * k of the table), 2: shn_tab_find (by the table's layout).  Variants 0 and 1 know the hashed
@@ -196,6 +199,8 @@ int shn_debug_sort_pairs(shn_ctx* ctx, const uint64_t* keys, const uint32_t* val
                          uint32_t* vals_out);
 int shn_debug_sort_keys(shn_ctx* ctx, const uint64_t* keys, uint64_t n, int bit_lo, int bit_hi, uint64_t* keys_out);
 int shn_debug_scan_u32(shn_ctx* ctx, const uint32_t* in, uint64_t n, uint64_t* out /* n + 1 */, uint64_t* total /* may be NULL */);
+int shn_debug_sorted_runs(shn_ctx* ctx, const uint64_t* keys, uint64_t n, int shift, uint64_t* keys_out, uint32_t* start_out, uint32_t* len_out,
+                          uint64_t* pos_out, uint64_t* n_runs_out);
 int shn_debug_table_find(shn_ctx* ctx, const shn_table* table, const uint64_t* keys, uint64_t n, int variant, int64_t* idx_out);
 int shn_debug_table_view(shn_ctx* ctx, const shn_table* table, int* bits, int* layout, uint64_t* bucket_off /* may be NULL */);
 /* per walk (host arrays of shn_ext_n_walks entries): right/left extension lengths (n_right ==

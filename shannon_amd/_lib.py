@@ -153,6 +153,7 @@ SIGNATURES = {
     "shn_debug_sort_pairs": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_int, C.c_int, vp, vp]),
     "shn_debug_sort_keys": (C.c_int, [vp, vp, C.c_uint64, C.c_int, C.c_int, vp]),
     "shn_debug_scan_u32": (C.c_int, [vp, vp, C.c_uint64, vp, vp]),
+    "shn_debug_sorted_runs": (C.c_int, [vp, vp, C.c_uint64, C.c_int, vp, vp, vp, vp, vp]),
     "shn_debug_table_find": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_int, vp]),
     "shn_debug_table_view": (C.c_int, [vp, vp, vp, vp, vp]),
     "shn_extend_sharded": (C.c_int, [vp, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, vpp]),

@@ -191,13 +191,8 @@ extern "C" int shn_abundance_classes(shn_ctx* ctx, const uint8_t* text, const ui
   if (n_tr >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many transcripts");
   const uint64_t n_pairs = r1->n_reads;
   if (n_pairs >= 0xFFFFFFFEULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many read pairs in one call");
-  if (t_off[0] != 0) return shn_fail(SHN_ERR_ARG, fn + ": t_off[0] is not 0");
-  std::vector<uint64_t> rec_off(n_tr + 1, 0);
-  for (uint64_t j = 0; j < n_tr; j++) {
-    if (t_off[j + 1] < t_off[j]) return shn_fail(SHN_ERR_ARG, fn + ": t_off not monotone");
-    const uint64_t len = t_off[j + 1] - t_off[j];
-    rec_off[j + 1] = rec_off[j] + (len >= FFP_SEED ? len - FFP_SEED + 1 : 0);
-  }
+  std::vector<uint64_t> rec_off;
+  if (int rc = ffp_record_offsets(fn, t_off, n_tr, &rec_off)) return rc;
   const uint64_t total = t_off[n_tr], n_rec = rec_off[n_tr];
   if (total >= 0xFFFFFF00ULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": more than 2^32 transcript bases in one call");
   shn_abundance* R = new shn_abundance();
@@ -363,11 +358,9 @@ __global__ void abd_entries_kernel(uint64_t n_entries, uint64_t n_classes, const
                                    uint64_t* __restrict__ key, uint32_t* __restrict__ val, uint32_t* __restrict__ cls) {
   const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n_entries) return;
-  uint64_t lo = 0, hi = n_classes;
-  while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (class_off[mid] <= e) lo = mid; else hi = mid; }
   key[e] = members[e];
   val[e] = (uint32_t)e;
-  cls[e] = (uint32_t)lo;
+  cls[e] = (uint32_t)shn_segment_of(class_off, n_classes, e);
 }
 
 // the transposed CSR from the sorted entries: tr_off[j] = first sorted entry of transcript j (j = m: all), tr_cls[k] = class of the k-th
@@ -375,11 +368,7 @@ __global__ void abd_transpose_kernel(uint64_t n_entries, uint64_t m, const uint6
                                      const uint32_t* __restrict__ cls, uint64_t* __restrict__ tr_off, uint32_t* __restrict__ tr_cls) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t < n_entries) tr_cls[t] = cls[val[t]];
-  if (t <= m) {
-    uint64_t lo = 0, hi = n_entries;
-    while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (key[mid] < t) lo = mid + 1; else hi = mid; }
-    tr_off[t] = lo;
-  }
+  if (t <= m) tr_off[t] = shn_lower_bound(key, n_entries, t);
 }
 
 __global__ void abd_em_init_kernel(uint64_t m, const double* __restrict__ eff, double* __restrict__ alpha, double* __restrict__ w) {

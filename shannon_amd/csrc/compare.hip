@@ -22,6 +22,7 @@
 #include "common.h"
 #include "filter_fp_dev.h"
 #include "compare_dev.h"
+#include "runs.h"
 #include <algorithm>
 
 namespace {
@@ -31,8 +32,6 @@ constexpr int CMP_SEED = SHN_COMPARE_SEED;
 constexpr int CMP_DBITS = 21;                       // a diagonal + 2^20 (sequences are shorter than 2^20 bases)
 constexpr uint64_t CMP_DBIAS = 1ULL << 20;
 constexpr uint64_t CMP_BAD_KEY = 1ULL << 32;
-static inline uint32_t cmp_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(cdiv(n, CMP_BLK), 1), 1u << 20); }
-#define CMP_FOR(i, n) for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (uint64_t)gridDim.x * blockDim.x)
 
 // sequences one after the other: w 32 bases a word (first base in the top bits), nm 64 mask bits a word (1 = outside ACGT, the
 // base itself packed as A), both with two zero words behind the end; off[n_seq + 1] on the device
@@ -46,12 +45,6 @@ __device__ __forceinline__ uint32_t cmp_mask32(const uint64_t* __restrict__ nm, 
   if (sh) v |= nm[wi + 1] >> (64 - sh);
   return (uint32_t)(v >> 32);
 }
-// sequence that holds base g (largest s with off[s] <= g: an empty sequence holds none)
-__device__ __forceinline__ uint64_t cmp_seq_of(const uint64_t* __restrict__ off, uint64_t n_seq, uint64_t g) {
-  uint64_t lo = 0, hi = n_seq;
-  while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (off[mid] <= g) lo = mid; else hi = mid; }
-  return lo;
-}
 // base g as a code 0..3, 4 outside ACGT
 __device__ __forceinline__ uint32_t cmp_base(const CmpText& X, uint64_t g) {
   if ((X.nm[g >> 6] >> (63 - (g & 63))) & 1) return 4;
@@ -62,7 +55,7 @@ __device__ __forceinline__ uint32_t cmp_base(const CmpText& X, uint64_t g) {
 // n_out is total or 2 total -- the reverse complement of every sequence, RC(sequence j) lying where j lies, `total` further on.
 __global__ __launch_bounds__(CMP_BLK) void cmp_pack_kernel(const uint8_t* __restrict__ text, const uint64_t* __restrict__ off, uint64_t n_seq,
                                                            uint64_t total, uint64_t n_out, uint64_t* __restrict__ w, uint64_t* __restrict__ nm) {
-  CMP_FOR(grp, (n_out + 63) / 64) {
+  SHN_GRID_FOR(grp, (n_out + 63) / 64) {
     uint64_t w0 = 0, w1 = 0, m = 0, j = 0;
     bool have = false;
     for (uint32_t e = 0; e < 64; e++) {
@@ -72,7 +65,7 @@ __global__ __launch_bounds__(CMP_BLK) void cmp_pack_kernel(const uint8_t* __rest
       if (g < total) ch = text[g];
       else {
         const uint64_t h = g - total;
-        if (!have || h >= off[j + 1]) { j = cmp_seq_of(off, n_seq, h); have = true; }
+        if (!have || h >= off[j + 1]) { j = shn_segment_of(off, n_seq, h); have = true; }
         ch = text[off[j + 1] - 1 - (h - off[j])];
       }
       uint64_t c = 0;
@@ -99,8 +92,8 @@ __global__ __launch_bounds__(CMP_BLK) void cmp_pack_kernel(const uint8_t* __rest
 // record r = the r-th 16-mer position inside an oriented target (rec_off[t] = records of the oriented targets before t)
 __global__ __launch_bounds__(CMP_BLK) void cmp_records_kernel(CmpText T, const uint64_t* __restrict__ rec_off, uint64_t n_rec, uint64_t* __restrict__ keys,
                                                               uint32_t* __restrict__ vals) {
-  CMP_FOR(r, n_rec) {
-    const uint64_t t = cmp_seq_of(rec_off, T.n_seq, r);
+  SHN_GRID_FOR(r, n_rec) {
+    const uint64_t t = shn_segment_of(rec_off, T.n_seq, r);
     const uint64_t g = T.off[t] + (r - rec_off[t]);
     keys[r] = (cmp_mask32(T.nm, g) >> (32 - CMP_SEED)) ? CMP_BAD_KEY : ffp_text32(T.w, g) >> (64 - 2 * CMP_SEED);
     vals[r] = (uint32_t)g;
@@ -113,18 +106,16 @@ template <bool FILL>
 __global__ __launch_bounds__(CMP_BLK) void cmp_seed_kernel(CmpText Q, CmpText T, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                            uint64_t n_rec, uint64_t m, int i_shift, uint32_t* __restrict__ cnt,
                                                            const uint64_t* __restrict__ pos, uint64_t* __restrict__ out) {
-  CMP_FOR(g, Q.total) {
+  SHN_GRID_FOR(g, Q.total) {
     uint32_t c = 0;
-    const uint64_t i = cmp_seq_of(Q.off, Q.n_seq, g);
+    const uint64_t i = shn_segment_of(Q.off, Q.n_seq, g);
     const uint64_t a = g - Q.off[i];
     if (g + CMP_SEED <= Q.off[i + 1] && (cmp_mask32(Q.nm, g) >> (32 - CMP_SEED)) == 0) {
       const uint64_t seed = ffp_text32(Q.w, g) >> (64 - 2 * CMP_SEED);
       const uint32_t before = a ? cmp_base(Q, g - 1) : 4u;
-      uint64_t lo = 0, hi = n_rec;
-      while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (keys[mid] < seed) lo = mid + 1; else hi = mid; }
-      for (uint64_t r = lo; r < n_rec && keys[r] == seed; r++) {
+      for (uint64_t r = shn_lower_bound(keys, n_rec, seed); r < n_rec && keys[r] == seed; r++) {
         const uint64_t h = vals[r];
-        const uint64_t t = cmp_seq_of(T.off, T.n_seq, h);
+        const uint64_t t = shn_segment_of(T.off, T.n_seq, h);
         const uint64_t b = h - T.off[t];
         if (before < 4 && b && cmp_base(T, h - 1) == before) continue;      // (the hit one base earlier names this diagonal)
         if (FILL) {
@@ -136,14 +127,6 @@ __global__ __launch_bounds__(CMP_BLK) void cmp_seed_kernel(CmpText Q, CmpText T,
     }
     if (!FILL) cnt[g] = c;
   }
-}
-
-__global__ void cmp_heads_kernel(const uint64_t* __restrict__ keys, uint64_t n, uint32_t* __restrict__ head) {
-  CMP_FOR(i, n) head[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
-}
-__global__ void cmp_unique_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ head, const uint64_t* __restrict__ pos, uint64_t n,
-                                  uint64_t* __restrict__ ukeys) {
-  CMP_FOR(i, n) if (head[i]) ukeys[pos[i]] = keys[i];
 }
 
 struct CmpCand { uint64_t i, j, t; uint32_t o; int64_t d; };
@@ -203,7 +186,7 @@ __global__ __launch_bounds__(CMP_BLK) void cmp_score_kernel(CmpText Q, CmpText T
 // -- for the greatest score, then the most matches (of equal scores the longer segment holds more); the first of equals stays.
 __global__ void cmp_pairs_kernel(const uint64_t* __restrict__ cand, uint64_t n_cand, const int32_t* __restrict__ s, const uint32_t* __restrict__ len,
                                  uint32_t min_matches, uint32_t* __restrict__ keep, uint32_t* __restrict__ best) {
-  CMP_FOR(c, n_cand) {
+  SHN_GRID_FOR(c, n_cand) {
     const uint64_t pair = cand[c] >> (CMP_DBITS + 1);
     uint32_t k = 0;
     if (c == 0 || (cand[c - 1] >> (CMP_DBITS + 1)) != pair) {
@@ -221,7 +204,7 @@ __global__ void cmp_pairs_kernel(const uint64_t* __restrict__ cand, uint64_t n_c
 __global__ void cmp_rows_kernel(CmpText T, const uint64_t* __restrict__ cand, uint64_t n_cand, uint64_t m, int i_shift, const int32_t* __restrict__ s,
                                 const uint32_t* __restrict__ len, const uint32_t* __restrict__ q0, const uint32_t* __restrict__ keep,
                                 const uint32_t* __restrict__ best, const uint64_t* __restrict__ pos, uint64_t n_rows, uint32_t* __restrict__ rows) {
-  CMP_FOR(c, n_cand) {
+  SHN_GRID_FOR(c, n_cand) {
     if (!keep[c]) continue;
     const uint32_t e = best[c];
     const CmpCand k = cmp_decode(cand[e], i_shift, m);
@@ -247,7 +230,7 @@ constexpr int CMP_QBITS = 20;                       // a qEnd (sequences are sho
 // an oriented pair, which a stable sort by this key keeps as the tie
 __global__ void cmp_chain_keys_kernel(const uint64_t* __restrict__ cand, const uint32_t* __restrict__ len, const uint32_t* __restrict__ q0, uint64_t n_cand,
                                       uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-  CMP_FOR(c, n_cand) {
+  SHN_GRID_FOR(c, n_cand) {
     keys[c] = ((cand[c] >> CMP_DBITS) << CMP_QBITS) | (uint64_t)(q0[c] + len[c]);
     vals[c] = (uint32_t)c;
   }
@@ -256,7 +239,7 @@ __global__ void cmp_chain_keys_kernel(const uint64_t* __restrict__ cand, const u
 __global__ void cmp_blocks_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ perm, uint64_t n_cand, const uint64_t* __restrict__ cand,
                                   const int32_t* __restrict__ s, const uint32_t* __restrict__ len, const uint32_t* __restrict__ q0, CmpBlock* __restrict__ blk,
                                   uint32_t* __restrict__ head) {
-  CMP_FOR(p, n_cand) {
+  SHN_GRID_FOR(p, n_cand) {
     const uint32_t c = perm[p];
     CmpBlock b;
     b.d = (int32_t)((int64_t)(cand[c] & ((1ULL << CMP_DBITS) - 1)) - (int64_t)CMP_DBIAS);
@@ -265,14 +248,6 @@ __global__ void cmp_blocks_kernel(const uint64_t* __restrict__ keys, const uint3
     head[p] = (p == 0 || (keys[p] >> CMP_QBITS) != (keys[p - 1] >> CMP_QBITS)) ? 1u : 0u;
   }
 }
-__global__ void cmp_group_starts_kernel(const uint32_t* __restrict__ head, const uint64_t* __restrict__ gpos, uint64_t n_cand, uint64_t n_groups,
-                                        uint32_t* __restrict__ gstart) {
-  CMP_FOR(p, n_cand) {
-    if (head[p]) gstart[gpos[p]] = (uint32_t)p;
-    if (p == 0) gstart[n_groups] = (uint32_t)n_cand;
-  }
-}
-
 struct CmpGroup { uint64_t i, j, t; uint32_t o; };
 __device__ __forceinline__ CmpGroup cmp_group_of(uint64_t key, int jo_bits, uint64_t m) {
   CmpGroup g;
@@ -337,7 +312,7 @@ __global__ __launch_bounds__(CMP_BLK) void cmp_chain_kernel(CmpText Q, CmpText T
 // holds min_matches matches or more; nblk: its blocks (0 where no row is written).
 __global__ void cmp_chain_pick_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ gstart, uint64_t n_groups, const CmpLink* __restrict__ top,
                                       uint32_t min_matches, uint32_t* __restrict__ keep, uint32_t* __restrict__ nblk, uint32_t* __restrict__ win) {
-  CMP_FOR(g, n_groups) {
+  SHN_GRID_FOR(g, n_groups) {
     const uint64_t pair = keys[gstart[g]] >> (CMP_QBITS + 1);
     uint32_t k = 0, nb = 0;
     if (g == 0 || (keys[gstart[g - 1]] >> (CMP_QBITS + 1)) != pair) {
@@ -360,7 +335,7 @@ __global__ void cmp_chain_rows_kernel(CmpText T, const uint64_t* __restrict__ ke
                                       const uint32_t* __restrict__ keep, const uint32_t* __restrict__ win, const uint64_t* __restrict__ rpos,
                                       const uint64_t* __restrict__ bpos, uint64_t n_rows, uint64_t n_blocks, uint32_t* __restrict__ rows,
                                       uint32_t* __restrict__ gaps, uint32_t* __restrict__ blocks) {
-  CMP_FOR(g, n_groups) {
+  SHN_GRID_FOR(g, n_groups) {
     if (!keep[g]) continue;
     const uint32_t w = win[g];
     const CmpLink C = top[w];
@@ -400,8 +375,6 @@ __global__ void cmp_chain_rows_kernel(CmpText T, const uint64_t* __restrict__ ke
 }
 
 
-int bits_for(uint64_t n) { int b = 1; while (b < 63 && (n - 1) >> b) b++; return b; }          // bits that hold 0 .. n - 1 (n >= 1)
-
 int check_offsets(const char* what, const uint64_t* off, uint64_t n) {
   if (off[0] != 0) return shn_fail(SHN_ERR_ARG, std::string("shn_compare_rows: ") + what + "_off[0] is not 0");
   for (uint64_t j = 0; j < n; j++) {
@@ -431,7 +404,7 @@ int pack_text(shn_ctx* ctx, ShnDevBufs& B, const uint8_t* text, const uint64_t* 
   HIP_TRY(hipStreamSynchronize(s));                          // (o is this frame's)
   HIP_TRY(hipMemsetAsync(d_w + 2 * n_grp, 0, 16, s));
   HIP_TRY(hipMemsetAsync(d_nm + n_grp, 0, 16, s));
-  if (n_out) hipLaunchKernelGGL(cmp_pack_kernel, dim3(cmp_grid(n_grp)), dim3(CMP_BLK), 0, s, (const uint8_t*)d_text, (const uint64_t*)d_off, n_seq, total, n_out, d_w, d_nm);
+  if (n_out) hipLaunchKernelGGL(cmp_pack_kernel, dim3(shn_grid(n_grp, CMP_BLK)), dim3(CMP_BLK), 0, s, (const uint8_t*)d_text, (const uint64_t*)d_off, n_seq, total, n_out, d_w, d_nm);
   HIP_TRY(hipGetLastError());
   out->w = d_w; out->nm = d_nm; out->off = d_off; out->n_seq = n_o; out->total = n_out;
   return SHN_OK;
@@ -458,29 +431,31 @@ int chain_rows(shn_ctx* ctx, ShnDevBufs& B, const CmpText& Q, const CmpText& T, 
   hipStream_t s = ctx->stream;
   int rc;
   const int jo_bits = i_shift - CMP_DBITS, key_bits = CMP_QBITS + jo_bits + i_bits;
-  uint64_t *d_keys = nullptr, *d_keys_tmp = nullptr, *d_gpos = nullptr, *d_rpos = nullptr, *d_bpos = nullptr;
-  uint32_t *d_perm = nullptr, *d_perm_tmp = nullptr, *d_head = nullptr, *d_gstart = nullptr, *d_keep = nullptr, *d_nblk = nullptr, *d_win = nullptr;
+  uint64_t *d_keys = nullptr, *d_keys_tmp = nullptr, *d_rpos = nullptr, *d_bpos = nullptr;
+  uint32_t *d_perm = nullptr, *d_perm_tmp = nullptr, *d_head = nullptr, *d_keep = nullptr, *d_nblk = nullptr, *d_win = nullptr;
   uint32_t *d_rows = nullptr, *d_gaps = nullptr, *d_blocks = nullptr;
   CmpBlock* d_blk = nullptr;
   CmpLink *d_st = nullptr, *d_top = nullptr;
-  uint64_t n_groups = 0, n_rows = 0, n_blocks = 0;
+  uint64_t n_rows = 0, n_blocks = 0;
   HIP_TRY(B.get(&d_keys, (n_cand + 1) * 8)); HIP_TRY(B.get(&d_keys_tmp, (n_cand + 1) * 8));
   HIP_TRY(B.get(&d_perm, (n_cand + 1) * 4)); HIP_TRY(B.get(&d_perm_tmp, (n_cand + 1) * 4));
-  HIP_TRY(B.get(&d_head, (n_cand + 1) * 4)); HIP_TRY(B.get(&d_gpos, (n_cand + 2) * 8));
+  HIP_TRY(B.get(&d_head, (n_cand + 1) * 4));
   HIP_TRY(B.get(&d_blk, n_cand * sizeof(CmpBlock))); HIP_TRY(B.get(&d_st, n_cand * sizeof(CmpLink)));
   TimerRegion treg(ctx, T_CMP_CHAIN);
-  hipLaunchKernelGGL(cmp_chain_keys_kernel, dim3(cmp_grid(n_cand)), dim3(CMP_BLK), 0, s, d_ucand, d_len, d_q0, n_cand, d_keys, d_perm);
+  hipLaunchKernelGGL(cmp_chain_keys_kernel, dim3(shn_grid(n_cand, CMP_BLK)), dim3(CMP_BLK), 0, s, d_ucand, d_len, d_q0, n_cand, d_keys, d_perm);
   if ((rc = shn_sort_pairs(ctx, d_keys, d_perm, d_keys_tmp, d_perm_tmp, n_cand, 0, key_bits))) return rc;
-  hipLaunchKernelGGL(cmp_blocks_kernel, dim3(cmp_grid(n_cand)), dim3(CMP_BLK), 0, s, (const uint64_t*)d_keys, (const uint32_t*)d_perm, n_cand, d_ucand, d_s, d_len, d_q0,
+  hipLaunchKernelGGL(cmp_blocks_kernel, dim3(shn_grid(n_cand, CMP_BLK)), dim3(CMP_BLK), 0, s, (const uint64_t*)d_keys, (const uint32_t*)d_perm, n_cand, d_ucand, d_s, d_len, d_q0,
                      d_blk, d_head);
-  if ((rc = shn_device_scan_u32(ctx, d_head, n_cand, d_gpos, &n_groups))) return rc;
-  HIP_TRY(B.get(&d_gstart, (n_groups + 1) * 4)); HIP_TRY(B.get(&d_top, n_groups * sizeof(CmpLink)));
+  ShnRuns groups;                               // a group = the blocks of one (query, target, orientation)
+  if ((rc = shn_runs_from_heads(ctx, B, d_head, n_cand, nullptr, SHN_RUNS_START, &groups))) return rc;
+  const uint64_t n_groups = groups.n_runs;
+  const uint32_t* d_gstart = groups.start;
+  HIP_TRY(B.get(&d_top, n_groups * sizeof(CmpLink)));
   HIP_TRY(B.get(&d_keep, (n_groups + 1) * 4)); HIP_TRY(B.get(&d_nblk, (n_groups + 1) * 4)); HIP_TRY(B.get(&d_win, n_groups * 4));
   HIP_TRY(B.get(&d_rpos, (n_groups + 2) * 8)); HIP_TRY(B.get(&d_bpos, (n_groups + 2) * 8));
-  hipLaunchKernelGGL(cmp_group_starts_kernel, dim3(cmp_grid(n_cand)), dim3(CMP_BLK), 0, s, (const uint32_t*)d_head, (const uint64_t*)d_gpos, n_cand, n_groups, d_gstart);
   hipLaunchKernelGGL(cmp_chain_kernel, dim3((uint32_t)std::min<uint64_t>(cdiv(n_groups, CMP_BLK / 64), 1u << 20)), dim3(CMP_BLK), 0, s, Q, T, (const uint64_t*)d_keys,
-                     (const uint32_t*)d_gstart, n_groups, n_t, jo_bits, (const CmpBlock*)d_blk, d_st, d_top);
-  hipLaunchKernelGGL(cmp_chain_pick_kernel, dim3(cmp_grid(n_groups)), dim3(CMP_BLK), 0, s, (const uint64_t*)d_keys, (const uint32_t*)d_gstart, n_groups,
+                     d_gstart, n_groups, n_t, jo_bits, (const CmpBlock*)d_blk, d_st, d_top);
+  hipLaunchKernelGGL(cmp_chain_pick_kernel, dim3(shn_grid(n_groups, CMP_BLK)), dim3(CMP_BLK), 0, s, (const uint64_t*)d_keys, d_gstart, n_groups,
                      (const CmpLink*)d_top, min_matches, d_keep, d_nblk, d_win);
   HIP_TRY(hipGetLastError());
   if ((rc = shn_device_scan_u32(ctx, d_keep, n_groups, d_rpos, &n_rows))) return rc;
@@ -495,7 +470,7 @@ int chain_rows(shn_ctx* ctx, ShnDevBufs& B, const CmpText& Q, const CmpText& T, 
   R->rows.resize(n_rows * 8); R->gaps.resize(n_rows * 5); R->blocks.resize(n_blocks * 3);
   if (n_rows) {
     HIP_TRY(B.get(&d_rows, n_rows * 8 * 4)); HIP_TRY(B.get(&d_gaps, n_rows * 5 * 4)); HIP_TRY(B.get(&d_blocks, n_blocks * 3 * 4));
-    hipLaunchKernelGGL(cmp_chain_rows_kernel, dim3(cmp_grid(n_groups)), dim3(CMP_BLK), 0, s, T, (const uint64_t*)d_keys, (const uint32_t*)d_gstart, n_groups, n_t, jo_bits,
+    hipLaunchKernelGGL(cmp_chain_rows_kernel, dim3(shn_grid(n_groups, CMP_BLK)), dim3(CMP_BLK), 0, s, T, (const uint64_t*)d_keys, d_gstart, n_groups, n_t, jo_bits,
                        (const CmpBlock*)d_blk, (const CmpLink*)d_st, (const CmpLink*)d_top, (const uint32_t*)d_keep, (const uint32_t*)d_win, (const uint64_t*)d_rpos,
                        (const uint64_t*)d_bpos, n_rows, n_blocks, d_rows, d_gaps, d_blocks);
     HIP_TRY(hipGetLastError());
@@ -517,7 +492,7 @@ int compare_rows(shn_ctx* ctx, const uint8_t* q_text, const uint64_t* q_off, uin
   if ((q_off[n_q] && !q_text) || (t_off[n_t] && !t_text)) return shn_fail(SHN_ERR_ARG, "shn_compare_rows: NULL text");
   const uint64_t n_o = strand_specific ? n_t : 2 * n_t;
   if (t_off[n_t] >= 0x7FFFFF00ULL) return shn_fail(SHN_ERR_OVERFLOW, "shn_compare_rows: 2^31 target bases or more in one call");
-  const int t_bits = bits_for(std::max<uint64_t>(2 * n_t, 1)), i_bits = bits_for(std::max<uint64_t>(n_q, 1)), i_shift = CMP_DBITS + t_bits;
+  const int t_bits = shn_bits_for(2 * n_t), i_bits = shn_bits_for(n_q), i_shift = CMP_DBITS + t_bits;
   if (i_shift + i_bits > 64) return shn_fail(SHN_ERR_OVERFLOW, "shn_compare_rows: queries times targets do not fit the 64-bit candidate key");
   std::vector<uint64_t> rec_off(n_o + 1, 0);
   for (uint64_t t = 0; t < n_o; t++) {
@@ -550,18 +525,19 @@ int compare_rows(shn_ctx* ctx, const uint8_t* q_text, const uint64_t* q_off, uin
     // bytes: both texts read (1 B a base; the targets twice with their reverse complements) and written packed (2 + 1 bits a base),
     // a record written (12 B), every one of the sort's five 8-bit passes reads and writes the records
     treg.bytes(Q.total + T.total + (Q.total + T.total) * 3 / 8 + n_rec * 12 + 5 * n_rec * 24);
-    hipLaunchKernelGGL(cmp_records_kernel, dim3(cmp_grid(n_rec)), dim3(CMP_BLK), 0, s, T, (const uint64_t*)d_roff, n_rec, d_keys, d_vals);
+    hipLaunchKernelGGL(cmp_records_kernel, dim3(shn_grid(n_rec, CMP_BLK)), dim3(CMP_BLK), 0, s, T, (const uint64_t*)d_roff, n_rec, d_keys, d_vals);
     if ((rc = shn_sort_pairs(ctx, d_keys, d_vals, d_keys_tmp, d_vals_tmp, n_rec, 0, 2 * CMP_SEED + 1))) return rc;
   }
 
   // ---- seeds: candidates counted, scanned, filled, sorted, made unique
   uint32_t* d_cnt = nullptr;
-  uint64_t *d_pos = nullptr, *d_cand = nullptr, *d_cand_tmp = nullptr, *d_ucand = nullptr;
+  uint64_t *d_pos = nullptr, *d_cand = nullptr, *d_cand_tmp = nullptr;
+  const uint64_t* d_ucand = nullptr;
   uint64_t n_hits = 0, n_cand = 0;
   HIP_TRY(B.get(&d_cnt, (Q.total + 1) * 4)); HIP_TRY(B.get(&d_pos, (Q.total + 2) * 8));
   {
     TimerRegion treg(ctx, T_CMP_SEEDS);
-    hipLaunchKernelGGL(cmp_seed_kernel<false>, dim3(cmp_grid(Q.total)), dim3(CMP_BLK), 0, s, Q, T, (const uint64_t*)d_keys, (const uint32_t*)d_vals, n_rec, n_t, i_shift,
+    hipLaunchKernelGGL(cmp_seed_kernel<false>, dim3(shn_grid(Q.total, CMP_BLK)), dim3(CMP_BLK), 0, s, Q, T, (const uint64_t*)d_keys, (const uint32_t*)d_vals, n_rec, n_t, i_shift,
                        d_cnt, (const uint64_t*)nullptr, (uint64_t*)nullptr);
     if ((rc = shn_device_scan_u32(ctx, d_cnt, Q.total, d_pos, &n_hits))) return rc;
     if (n_hits >= 0xFFFFFFFEULL) return shn_fail(SHN_ERR_OVERFLOW, "shn_compare_rows: 2^32 seed hits or more in one call (" + std::to_string(n_hits) + ")");
@@ -572,17 +548,13 @@ int compare_rows(shn_ctx* ctx, const uint8_t* q_text, const uint64_t* q_off, uin
     const uint64_t passes = (uint64_t)(i_shift + i_bits + 7) / 8;
     treg.bytes(Q.total * 3 / 4 + Q.total * 20 + n_rec * 12 + T.total * 3 / 8 + n_hits * 8 + passes * n_hits * 16 + n_hits * 28);
     if (n_hits) {
-      hipLaunchKernelGGL(cmp_seed_kernel<true>, dim3(cmp_grid(Q.total)), dim3(CMP_BLK), 0, s, Q, T, (const uint64_t*)d_keys, (const uint32_t*)d_vals, n_rec, n_t, i_shift,
+      hipLaunchKernelGGL(cmp_seed_kernel<true>, dim3(shn_grid(Q.total, CMP_BLK)), dim3(CMP_BLK), 0, s, Q, T, (const uint64_t*)d_keys, (const uint32_t*)d_vals, n_rec, n_t, i_shift,
                          (uint32_t*)nullptr, (const uint64_t*)d_pos, d_cand);
       uint64_t* sorted = nullptr;
       if ((rc = shn_sort_keys(ctx, d_cand, d_cand_tmp, n_hits, 0, i_shift + i_bits, &sorted))) return rc;
-      uint32_t* d_head = nullptr; uint64_t* d_hpos = nullptr;
-      HIP_TRY(B.get(&d_head, (n_hits + 1) * 4)); HIP_TRY(B.get(&d_hpos, (n_hits + 2) * 8));
-      hipLaunchKernelGGL(cmp_heads_kernel, dim3(cmp_grid(n_hits)), dim3(CMP_BLK), 0, s, (const uint64_t*)sorted, n_hits, d_head);
-      if ((rc = shn_device_scan_u32(ctx, d_head, n_hits, d_hpos, &n_cand))) return rc;
-      HIP_TRY(B.get(&d_ucand, (n_cand + 1) * 8));
-      hipLaunchKernelGGL(cmp_unique_kernel, dim3(cmp_grid(n_hits)), dim3(CMP_BLK), 0, s, (const uint64_t*)sorted, (const uint32_t*)d_head, (const uint64_t*)d_hpos, n_hits, d_ucand);
-      HIP_TRY(hipGetLastError());
+      ShnRuns runs;
+      if ((rc = shn_sorted_runs(ctx, B, sorted, n_hits, 0, SHN_RUNS_KEYS, &runs))) return rc;
+      n_cand = runs.n_runs; d_ucand = runs.keys;
     }
   }
   R->n_hits = n_hits; R->n_cand = n_cand;
@@ -599,7 +571,7 @@ int compare_rows(shn_ctx* ctx, const uint8_t* q_text, const uint64_t* q_off, uin
     // bytes: a candidate read (8 B), four offsets (32 B), three results written (12 B); the diagonals' bases come from the packed
     // texts, which are re-read from the caches and priced once
     treg.bytes(n_cand * 52 + (Q.total + T.total) * 3 / 8);
-    hipLaunchKernelGGL(cmp_score_kernel, dim3((uint32_t)std::min<uint64_t>(cdiv(n_cand, CMP_BLK / 64), 1u << 20)), dim3(CMP_BLK), 0, s, Q, T, (const uint64_t*)d_ucand, n_cand,
+    hipLaunchKernelGGL(cmp_score_kernel, dim3((uint32_t)std::min<uint64_t>(cdiv(n_cand, CMP_BLK / 64), 1u << 20)), dim3(CMP_BLK), 0, s, Q, T, d_ucand, n_cand,
                        n_t, i_shift, d_s, d_len, d_q0);
     HIP_TRY(hipGetLastError());
   }
@@ -617,7 +589,7 @@ int compare_rows(shn_ctx* ctx, const uint8_t* q_text, const uint64_t* q_off, uin
   uint64_t n_rows = 0;
   {
     TimerRegion treg(ctx, T_CMP_ROWS);
-    hipLaunchKernelGGL(cmp_pairs_kernel, dim3(cmp_grid(n_cand)), dim3(CMP_BLK), 0, s, (const uint64_t*)d_ucand, n_cand, (const int32_t*)d_s, (const uint32_t*)d_len, min_matches,
+    hipLaunchKernelGGL(cmp_pairs_kernel, dim3(shn_grid(n_cand, CMP_BLK)), dim3(CMP_BLK), 0, s, d_ucand, n_cand, (const int32_t*)d_s, (const uint32_t*)d_len, min_matches,
                        d_keep, d_best);
     if ((rc = shn_device_scan_u32(ctx, d_keep, n_cand, d_rpos, &n_rows))) return rc;
     // bytes: per candidate its key, score and length read (16 B), the flag written, scanned and read (4 + 4 + 8 + 4 + 8 B), the
@@ -625,7 +597,7 @@ int compare_rows(shn_ctx* ctx, const uint8_t* q_text, const uint64_t* q_off, uin
     treg.bytes(n_cand * 48 + n_rows * 68);
     if (n_rows) {
       HIP_TRY(B.get(&d_rows, n_rows * 8 * 4));
-      hipLaunchKernelGGL(cmp_rows_kernel, dim3(cmp_grid(n_cand)), dim3(CMP_BLK), 0, s, T, (const uint64_t*)d_ucand, n_cand, n_t, i_shift, (const int32_t*)d_s,
+      hipLaunchKernelGGL(cmp_rows_kernel, dim3(shn_grid(n_cand, CMP_BLK)), dim3(CMP_BLK), 0, s, T, d_ucand, n_cand, n_t, i_shift, (const int32_t*)d_s,
                          (const uint32_t*)d_len, (const uint32_t*)d_q0, (const uint32_t*)d_keep, (const uint32_t*)d_best, (const uint64_t*)d_rpos, n_rows, d_rows);
       HIP_TRY(hipGetLastError());
     }

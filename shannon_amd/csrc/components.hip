@@ -2,6 +2,7 @@
 // table (component_shard, behind shn_extend_sharded) and on owner shards (shn_cc_*).
 #include "ext_state.h"
 #include "k1dict.h"
+#include "runs.h"
 #include <cstring>
 #include <vector>
 #include <algorithm>
@@ -44,7 +45,7 @@ __global__ void cc_edges_kernel(const TabIdx T, const uint8_t* __restrict__ flag
   const uint64_t mask = (k == 32) ? ~0ULL : ((1ULL << (2 * k)) - 1);
   const uint64_t total = n * 8, rounded = (total + 63) & ~63ULL;
   const int lane = threadIdx.x & 63, g0 = lane & ~7, p = lane & 7;
-  for (uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; gid < rounded; gid += (uint64_t)gridDim.x * blockDim.x) {
+  SHN_GRID_FOR(gid, rounded) {
     const bool in = gid < total;
     const uint64_t i = in ? gid >> 3 : 0;
     const bool dead = !in || (flags[i] & 2);
@@ -284,7 +285,7 @@ __global__ void cc_query_kernel(const uint64_t* __restrict__ tkeys, const uint8_
   const uint64_t total_items = n * 8;
   const int m = k < SHN_OWNER_M ? k : SHN_OWNER_M, w = k - m + 1;
   const uint32_t mmask = m == 16 ? 0xFFFFFFFFu : ((1u << (2 * m)) - 1u);
-  for (uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; gid < total_items; gid += (uint64_t)gridDim.x * blockDim.x) {
+  SHN_GRID_FOR(gid, total_items) {
     const uint64_t i = gid >> 3;
     const int p = (int)(gid & 7);
     if (flags[i] & 2) continue;                                         // (the eight lanes of a k1-mer leave together)
@@ -349,7 +350,7 @@ __global__ void cc_answer_kernel(const TabIdx T, const uint8_t* __restrict__ fla
                                  uint64_t* __restrict__ edges, unsigned long long* __restrict__ n_edges) {
   const int lane = threadIdx.x & 63;
   const uint64_t rounded = (nq + 63) & ~63ULL;
-  for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < rounded; q += (uint64_t)gridDim.x * blockDim.x) {
+  SHN_GRID_FOR(q, rounded) {
     int64_t j = -1;
     if (q < nq) { j = shn_tab_find(T, qk[q]); if (j >= 0 && (flags[j] & 2)) j = -1; }
     const unsigned long long m = __ballot(j >= 0);
@@ -483,27 +484,24 @@ extern "C" int shn_cc_answer(shn_cc* c, const void* dev_keys, const void* dev_la
 
 // ---- the component graph (nodes = local components that have an edge to another rank), the same computation on every rank
 __global__ void ccs_iota_kernel(uint32_t* __restrict__ v, uint64_t n) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) v[i] = (uint32_t)i;
+  SHN_GRID_FOR(i, n) v[i] = (uint32_t)i;
 }
-__global__ void ccs_first_kernel(const uint64_t* __restrict__ keys, uint64_t n, uint32_t* __restrict__ first) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) first[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
-}
-// pos = exclusive scan of first: the node number of sorted position i is pos[i + 1] - 1
+// first, pos: the runs of the sorted ids (runs.h); a run is a node, its number the run index
 __global__ void ccs_number_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ first,
                                   const uint64_t* __restrict__ pos, uint64_t n, uint32_t* __restrict__ node_of_end, uint64_t* __restrict__ nodes,
                                   uint32_t* __restrict__ lab) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint32_t id = (uint32_t)(pos[i + 1] - 1);
+  SHN_GRID_FOR(i, n) {
+    const uint32_t id = (uint32_t)shn_run_index(first, pos, i);
     node_of_end[vals[i]] = id;
     if (first[i]) { nodes[id] = keys[i]; lab[id] = id; }
   }
 }
 __global__ void ccs_unite_kernel(const uint32_t* __restrict__ node_of_end, uint64_t n_edges, uint32_t* lab) {
-  for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_edges; e += (uint64_t)gridDim.x * blockDim.x)
+  SHN_GRID_FOR(e, n_edges)
     cc_unite(lab, node_of_end[2 * e], node_of_end[2 * e + 1]);
 }
 __global__ void ccs_label_kernel(uint32_t* lab, const uint64_t* __restrict__ nodes, uint64_t n_nodes, uint64_t* __restrict__ label_out) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_nodes; i += (uint64_t)gridDim.x * blockDim.x)
+  SHN_GRID_FOR(i, n_nodes)
     label_out[i] = nodes[cc_find(lab, (uint32_t)i)];
 }
 
@@ -521,10 +519,10 @@ extern "C" int shn_cc_solve(shn_ctx* ctx, const void* dev_edges, uint64_t n_edge
   SHN_ENTER(ctx);
   hipStream_t s = ctx->stream; shn_use_stream(s);
   ShnDevBufs bufs(s);
-  uint64_t *k0, *k1, *pos; uint32_t *v0, *v1, *first, *node_of_end, *lab;
+  uint64_t *k0, *k1; uint32_t *v0, *v1, *node_of_end, *lab;
   auto no = [](hipError_t e) { return e != hipSuccess; };
-  if (no(bufs.get(&k0, m * 8)) || no(bufs.get(&k1, m * 8)) || no(bufs.get(&v0, m * 4)) || no(bufs.get(&v1, m * 4)) || no(bufs.get(&first, m * 4)) ||
-      no(bufs.get(&pos, (m + 1) * 8)) || no(bufs.get(&node_of_end, m * 4)) || no(bufs.get(&lab, m * 4)))
+  if (no(bufs.get(&k0, m * 8)) || no(bufs.get(&k1, m * 8)) || no(bufs.get(&v0, m * 4)) || no(bufs.get(&v1, m * 4)) ||
+      no(bufs.get(&node_of_end, m * 4)) || no(bufs.get(&lab, m * 4)))
     return shn_fail(SHN_ERR_HIP, "shn_cc_solve: out of device memory");
   const uint32_t grid = (uint32_t)std::min<uint64_t>(cdiv(m, 256), 1u << 20);
   HIP_TRY(hipMemcpyAsync(k0, dev_edges, m * 8, hipMemcpyDeviceToDevice, s));
@@ -533,10 +531,10 @@ extern "C" int shn_cc_solve(shn_ctx* ctx, const void* dev_edges, uint64_t n_edge
   if (id_limit) { bit_hi = 8; while (bit_hi < 64 && (id_limit >> bit_hi)) bit_hi += 8; }
   int rc = shn_sort_pairs(ctx, k0, v0, k1, v1, m, 0, bit_hi);
   if (rc) return rc;
-  hipLaunchKernelGGL(ccs_first_kernel, dim3(grid), dim3(256), 0, s, k0, m, first);
-  uint64_t nn = 0;
-  if ((rc = shn_device_scan_u32(ctx, first, m, pos, &nn))) return rc;
-  hipLaunchKernelGGL(ccs_number_kernel, dim3(grid), dim3(256), 0, s, k0, v0, first, pos, m, node_of_end, (uint64_t*)dev_nodes_out, lab);
+  ShnRuns runs;
+  if ((rc = shn_sorted_runs(ctx, bufs, k0, m, 0, 0, &runs))) return rc;
+  const uint64_t nn = runs.n_runs;
+  hipLaunchKernelGGL(ccs_number_kernel, dim3(grid), dim3(256), 0, s, k0, v0, runs.head, runs.pos, m, node_of_end, (uint64_t*)dev_nodes_out, lab);
   hipLaunchKernelGGL(ccs_unite_kernel, dim3((uint32_t)std::min<uint64_t>(cdiv(n_edges, 256), 1u << 20)), dim3(256), 0, s, node_of_end, n_edges, lab);
   hipLaunchKernelGGL(ccs_label_kernel, dim3((uint32_t)std::min<uint64_t>(cdiv(nn, 256), 1u << 20)), dim3(256), 0, s, lab, (const uint64_t*)dev_nodes_out, nn,
                      (uint64_t*)dev_labels_out);
@@ -553,7 +551,7 @@ __device__ __forceinline__ int64_t ccs_search(const uint64_t* __restrict__ a, ui
 }
 __global__ void ccs_glabel_kernel(const uint32_t* __restrict__ lab, uint64_t n, uint64_t base_me, const uint64_t* __restrict__ nodes,
                                   const uint64_t* __restrict__ labels, uint64_t n_nodes, uint64_t* __restrict__ out) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+  SHN_GRID_FOR(i, n) {
     const uint64_t g = base_me + lab[i];
     const int64_t j = ccs_search(nodes, n_nodes, g);
     out[i] = j >= 0 ? labels[j] : g;
@@ -578,7 +576,7 @@ extern "C" int shn_cc_labels(shn_cc* c, uint64_t base_me, const void* dev_nodes,
 
 __global__ void ccs_owner_kernel(const uint64_t* __restrict__ glabel, uint64_t n, const uint64_t* __restrict__ big, const uint8_t* __restrict__ big_owner,
                                  uint64_t n_big, uint32_t world, uint8_t* __restrict__ owner) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+  SHN_GRID_FOR(i, n) {
     const uint64_t g = glabel[i];
     const int64_t j = ccs_search(big, n_big, g);
     owner[i] = j >= 0 ? big_owner[j] : (uint8_t)(shn_mix64(g ^ 0x5851F42D4C957F2DULL) % world);
@@ -612,7 +610,7 @@ __global__ void ccs_shard_kernel(const uint64_t* __restrict__ keys, const uint32
     if (WRITE) lbase[threadIdx.x] = (int)threadIdx.x < world ? pos[(uint64_t)threadIdx.x * gridDim.x + blockIdx.x] : 0;
   }
   __syncthreads();
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+  SHN_GRID_FOR(i, n) {
     const int o = (int)owner[i];
     const uint32_t at = atomicAdd(&lh[o], 1u);
     if (WRITE) { const uint64_t d = lbase[o] + at; ok[d] = keys[i]; oc[d] = counts[i]; }

@@ -1,7 +1,8 @@
-// Test hooks of the shared device primitives (tests/test_primitives_gpu.py): the radix sort (sort.hip), the scan (count.hip) and the
-// three bucket searches of common.h, each called unchanged on host arrays staged into buffers of the caching allocator on the
+// Test hooks of the shared device primitives (tests/test_primitives_gpu.py): the radix sort (sort.hip), the scan (count.hip), the runs
+// of a sorted array (runs.hip) and the three bucket searches of common.h, each called unchanged on host arrays staged into buffers of the caching allocator on the
 // context's stream.  Not part of the path.
 #include "common.h"
+#include "runs.h"
 
 static bool bad_range(int bit_lo, int bit_hi) { return bit_lo < 0 || bit_hi < 0 || bit_lo > 64 || bit_hi > 64; }
 
@@ -62,6 +63,33 @@ extern "C" int shn_debug_scan_u32(shn_ctx* ctx, const uint32_t* in, uint64_t n, 
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, dout, (n + 1) * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  return SHN_OK;
+}
+
+// everything shn_sorted_runs gives, of keys the caller has sorted by (key >> shift): keys_out / len_out take n_runs (n at the most),
+// start_out n_runs + 1, pos_out n + 1 elements
+extern "C" int shn_debug_sorted_runs(shn_ctx* ctx, const uint64_t* keys, uint64_t n, int shift, uint64_t* keys_out, uint32_t* start_out, uint32_t* len_out,
+                                     uint64_t* pos_out, uint64_t* n_runs_out) {
+  if (!ctx || !start_out || !pos_out || !n_runs_out || (n && (!keys || !keys_out || !len_out))) return shn_fail(SHN_ERR_ARG, "shn_debug_sorted_runs: NULL argument");
+  if (shift < 0 || shift > 63) return shn_fail(SHN_ERR_ARG, "shn_debug_sorted_runs: shift outside 0 .. 63");
+  SHN_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  ShnDevBufs bufs(s);
+  uint64_t* dk = nullptr;
+  HIP_TRY(bufs.get(&dk, (n + 1) * 8));
+  if (n) HIP_TRY(hipMemcpyAsync(dk, keys, n * 8, hipMemcpyHostToDevice, s));
+  ShnRuns r;
+  int rc = shn_sorted_runs(ctx, bufs, dk, n, shift, SHN_RUNS_KEYS | SHN_RUNS_START | SHN_RUNS_LEN, &r);
+  if (rc) return rc;
+  if (r.n_runs > n) return shn_fail(SHN_ERR_INTERNAL, "shn_debug_sorted_runs: more runs than keys");
+  if (r.n_runs) {
+    HIP_TRY(hipMemcpyAsync(keys_out, r.keys, r.n_runs * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(len_out, r.len, r.n_runs * 4, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipMemcpyAsync(start_out, r.start, (r.n_runs + 1) * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(pos_out, r.pos, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *n_runs_out = r.n_runs;
   return SHN_OK;
 }
 

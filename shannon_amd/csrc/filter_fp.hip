@@ -110,8 +110,7 @@ __global__ void ffp_records_kernel(const uint64_t* __restrict__ tw, const uint64
                                    uint32_t* __restrict__ vals) {
   const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n_rec) return;
-  uint64_t lo = 0, hi = n_tr;                 // largest j with rec_off[j] <= r: the transcript that holds record r
-  while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (rec_off[mid] <= r) lo = mid; else hi = mid; }
+  const uint64_t lo = shn_segment_of(rec_off, n_tr, r);       // the transcript that holds record r
   const uint64_t g = t_off[lo] + (r - rec_off[lo]);
   keys[r] = ((uint64_t)t_part[lo] << (2 * FFP_SEED)) | ffp_text_seed(tw, g);
   vals[r] = (uint32_t)g;
@@ -129,9 +128,7 @@ __global__ void ffp_revcomp_kernel(const uint64_t* __restrict__ words, const uin
     const uint32_t gpr = wpr / 2;
     r = gid / gpr; g = gid % gpr; wbase = r * wpr; len = fixed_len;
   } else {
-    uint64_t lo = 0, hi = n_reads;            // largest r with woff[r] <= 2 gid
-    while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (woff[mid] <= gid * 2) lo = mid; else hi = mid; }
-    r = lo; wbase = woff[r]; g = (gid * 2 - wbase) / 2; len = lens[r];
+    r = shn_segment_of(woff, n_reads, gid * 2); wbase = woff[r]; g = (gid * 2 - wbase) / 2; len = lens[r];
   }
   const uint64_t* w = words + wbase;
   const uint64_t* m = mask ? mask + wbase / 2 : nullptr;
@@ -221,6 +218,17 @@ int ffp_set(shn_ctx* ctx, ShnDevBufs& bufs, const shn_reads* r, bool want_rc, Ff
   return SHN_OK;
 }
 
+int ffp_record_offsets(const std::string& fn, const uint64_t* t_off, uint64_t n_tr, std::vector<uint64_t>* rec_off) {
+  if (t_off[0] != 0) return shn_fail(SHN_ERR_ARG, fn + ": t_off[0] is not 0");
+  rec_off->assign(n_tr + 1, 0);
+  for (uint64_t j = 0; j < n_tr; j++) {
+    if (t_off[j + 1] < t_off[j]) return shn_fail(SHN_ERR_ARG, fn + ": t_off not monotone");
+    const uint64_t len = t_off[j + 1] - t_off[j];
+    (*rec_off)[j + 1] = (*rec_off)[j] + (len >= FFP_SEED ? len - FFP_SEED + 1 : 0);
+  }
+  return SHN_OK;
+}
+
 // The transcripts' text packed and the sorted index of its 15-mers (the header says what the arguments are).
 int ffp_index_build(const std::string& fn, shn_ctx* ctx, ShnDevBufs& bufs, int slot, const uint8_t* text, const uint64_t* t_off, const uint32_t* t_part,
                     uint64_t n_tr, uint32_t n_parts, const std::vector<uint64_t>& rec_off, FfpIndex* out, uint64_t* n_tw_out) {
@@ -247,8 +255,9 @@ int ffp_index_build(const std::string& fn, shn_ctx* ctx, ShnDevBufs& bufs, int s
   HIP_TRY(hipMemsetAsync(d_flag, 0, 4, s));
   HIP_TRY(hipMemsetAsync(d_tw + n_tw, 0, 16, s));
   {
-    int key_bits = 2 * FFP_SEED;
-    while (key_bits < 62 && ((uint64_t)n_parts >> (key_bits - 2 * FFP_SEED))) key_bits++;
+    // (n_parts >= 1 here.  The partition field holds 0 .. n_parts, one value more than there are partitions: kept as it was, it
+    // decides the number of sort passes at n_parts = 2^k)
+    const int key_bits = 2 * FFP_SEED + shn_bits_for((uint64_t)n_parts + 1);
     const uint64_t passes = (uint64_t)(key_bits + 7) / 8;
     TimerRegion treg(ctx, slot);
     // bytes: the text read and written packed (1.25 B a base), a record written (12 B), every sort pass reads and writes the records
@@ -282,15 +291,11 @@ static int ffp_run(const char* fn_, shn_ctx* ctx, const uint8_t* text, const uin
   if (n_parts >= (1u << 31)) return shn_fail(SHN_ERR_ARG, fn + ": too many partitions");
   const uint64_t n_pairs = r1->n_reads;
   const uint64_t total = t_off[n_tr];
-  if (t_off[0] != 0) return shn_fail(SHN_ERR_ARG, fn + ": t_off[0] is not 0");
+  std::vector<uint64_t> rec_off;
+  if (int rc = ffp_record_offsets(fn, t_off, n_tr, &rec_off)) return rc;
   if (total >= 0xFFFFFF00ULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": more than 2^32 transcript bases in one call");
-  std::vector<uint64_t> rec_off(n_tr + 1, 0);
-  for (uint64_t j = 0; j < n_tr; j++) {
-    if (t_off[j + 1] < t_off[j]) return shn_fail(SHN_ERR_ARG, fn + ": t_off not monotone");
+  for (uint64_t j = 0; j < n_tr; j++)
     if (t_part[j] >= n_parts) return shn_fail(SHN_ERR_ARG, fn + ": partition of a transcript out of range");
-    const uint64_t len = t_off[j + 1] - t_off[j];
-    rec_off[j + 1] = rec_off[j] + (len >= FFP_SEED ? len - FFP_SEED + 1 : 0);
-  }
   const uint64_t n_rec = rec_off[n_tr];
   if (!routes)
     for (uint64_t i = 0; i < n_host; i++)

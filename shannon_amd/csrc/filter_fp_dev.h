@@ -3,6 +3,7 @@
 // every concordant placement of an oriented pair (DESIGN.md "filter_FP", rules 2-5).  What a caller does with a placement is its own.
 #pragma once
 #include "common.h"
+#include "runs.h"
 
 #define FFP_SEED SHN_FILTER_FP_SEED
 #define FFP_NONE 0xFFFFFFFFu
@@ -95,18 +96,6 @@ __device__ __forceinline__ bool ffp_named_before(const FfpRead& x, const uint64_
   return false;
 }
 
-__device__ __forceinline__ uint64_t ffp_lower(const FfpIndex& I, uint64_t key) {
-  uint64_t lo = 0, hi = I.n_rec;
-  while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (I.keys[mid] < key) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-// transcript that holds base g of the text (empty transcripts hold none)
-__device__ __forceinline__ uint64_t ffp_transcript_of(const FfpIndex& I, uint64_t g) {
-  uint64_t lo = 0, hi = I.n_tr;               // largest j with t_off[j] <= g
-  while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (I.t_off[mid] <= g) lo = mid; else hi = mid; }
-  return lo;
-}
-
 // Every concordant placement of the oriented pair (x, y) in the partition whose key prefix is pkey: x at u, y at v on the same
 // transcript j, u <= v, u + |x| <= v + |y|, v + |y| - u <= max_span, each mate within its mismatch bound; f(cost, j, u, v) is
 // called for each of them whose first mate alone does not already cost more than *best (EXACT == false: not already as much --
@@ -122,9 +111,9 @@ __device__ __forceinline__ void ffp_each_placement(const FfpIndex& I, uint64_t p
     uint64_t seed;
     if (!ffp_seed_of(x, s, &seed)) continue;
     const uint64_t key = pkey | seed;
-    for (uint64_t r = ffp_lower(I, key); r < I.n_rec && I.keys[r] == key; r++) {
+    for (uint64_t r = shn_lower_bound(I.keys, I.n_rec, key); r < I.n_rec && I.keys[r] == key; r++) {
       const uint64_t g = I.vals[r];
-      const uint64_t j = ffp_transcript_of(I, g);
+      const uint64_t j = shn_segment_of(I.t_off, I.n_tr, g);               // (an empty transcript holds no base)
       const uint64_t a = I.t_off[j], b = I.t_off[j + 1];
       if (g < a + (uint64_t)s * FFP_SEED) continue;
       const uint64_t u = g - (uint64_t)s * FFP_SEED;
@@ -134,7 +123,7 @@ __device__ __forceinline__ void ffp_each_placement(const FfpIndex& I, uint64_t p
       if (!have_y) {                                     // (the first verified first mate: where the second mate's seeds start in the index)
         for (uint32_t t = 0; t <= thry && t < FFP_YSEEDS; t++) {
           uint64_t seed_y;
-          ylo[t] = ffp_seed_of(y, t, &seed_y) ? (uint32_t)ffp_lower(I, pkey | seed_y) : FFP_NONE;
+          ylo[t] = ffp_seed_of(y, t, &seed_y) ? (uint32_t)shn_lower_bound(I.keys, I.n_rec, pkey | seed_y) : FFP_NONE;
         }
         have_y = true;
       }
@@ -142,7 +131,7 @@ __device__ __forceinline__ void ffp_each_placement(const FfpIndex& I, uint64_t p
         uint64_t seed_y;
         if (!ffp_seed_of(y, t, &seed_y)) continue;
         const uint64_t key_y = pkey | seed_y;
-        for (uint64_t q = t < FFP_YSEEDS ? ylo[t] : ffp_lower(I, key_y); q < I.n_rec && I.keys[q] == key_y; q++) {
+        for (uint64_t q = t < FFP_YSEEDS ? ylo[t] : shn_lower_bound(I.keys, I.n_rec, key_y); q < I.n_rec && I.keys[q] == key_y; q++) {
           const uint64_t gy = I.vals[q];
           if (gy < a + (uint64_t)t * FFP_SEED || gy >= b) continue;                 // (another transcript, or y would start before this one)
           const uint64_t v = gy - (uint64_t)t * FFP_SEED;
@@ -165,7 +154,10 @@ __device__ __forceinline__ void ffp_min_cost(const FfpIndex& I, uint64_t pkey, c
 // ---- host side (filter_fp.hip): what both callers prepare the same way
 // the device view of a resident read set; want_rc: its reverse complement written beside it (rc_bytes += what that read and wrote)
 int ffp_set(shn_ctx* ctx, ShnDevBufs& bufs, const shn_reads* r, bool want_rc, FfpSet* out, uint64_t* rc_bytes);
-// the transcripts' text packed 2 bits a base and the sorted index of its 15-mers, timed under `slot`; rec_off[j] = records of the
-// transcripts before j (host, n_tr + 1).  Synchronises; a base outside ACGT fails the call.  *n_tw = words of the packed text.
+// t_off (host, n_tr + 1) checked -- [0] == 0, monotone: SHN_ERR_ARG in fn's name -- and rec_off[j] = 15-mer records of the
+// transcripts before j (n_tr + 1).  Host work alone: both callers run it with their other argument checks, before the device is touched.
+int ffp_record_offsets(const std::string& fn, const uint64_t* t_off, uint64_t n_tr, std::vector<uint64_t>* rec_off);
+// the transcripts' text packed 2 bits a base and the sorted index of its 15-mers, timed under `slot`; rec_off: ffp_record_offsets'.
+// Synchronises; a base outside ACGT fails the call.  *n_tw = words of the packed text.
 int ffp_index_build(const std::string& fn, shn_ctx* ctx, ShnDevBufs& bufs, int slot, const uint8_t* text, const uint64_t* t_off, const uint32_t* t_part,
                     uint64_t n_tr, uint32_t n_parts, const std::vector<uint64_t>& rec_off, FfpIndex* out, uint64_t* n_tw);

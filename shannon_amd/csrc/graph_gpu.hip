@@ -27,6 +27,7 @@
 #include <thread>
 #include <atomic>
 #include "unitigs.h"
+#include "runs.h"
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -37,9 +38,6 @@
 #define UG_NONE 0xFFFFFFFFu
 
 namespace {
-
-static inline uint32_t ug_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(cdiv(n, UG_BLK), 1), 1u << 20); }
-#define UG_FOR(i, n) for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (uint64_t)gridDim.x * blockDim.x)
 
 struct DevBufs {
   std::vector<void*> p;
@@ -60,7 +58,7 @@ __global__ void ug_insert_kernel(const uint8_t* __restrict__ bases, const uint64
                                  const uint32_t* __restrict__ part_of, const uint64_t* __restrict__ tab_off, uint64_t total, int K,
                                  unsigned long long* __restrict__ tkey, uint32_t* __restrict__ tfirst, uint32_t* __restrict__ wslot,
                                  unsigned long long* __restrict__ n_bad) {
-  UG_FOR(g, total) {
+  SHN_GRID_FOR(g, total) {
     const uint32_t c = cid[g];
     const uint64_t end = off[c + 1];
     if (end - off[c] < (uint64_t)K + 1 || g + (uint64_t)K > end) { wslot[g] = UG_NONE; continue; }
@@ -83,18 +81,18 @@ __global__ void ug_insert_kernel(const uint8_t* __restrict__ bases, const uint64
   }
 }
 __global__ void ug_first_flag_kernel(const uint32_t* __restrict__ wslot, const uint32_t* __restrict__ tfirst, uint64_t total, uint32_t* __restrict__ flag) {
-  UG_FOR(g, total) flag[g] = (wslot[g] != UG_NONE && tfirst[wslot[g]] == (uint32_t)g) ? 1u : 0u;
+  SHN_GRID_FOR(g, total) flag[g] = (wslot[g] != UG_NONE && tfirst[wslot[g]] == (uint32_t)g) ? 1u : 0u;
 }
 // node id of a table slot = rank of its first occurrence; nfirst[node] = that window
 __global__ void ug_node_ids_kernel(const uint32_t* __restrict__ flag, const uint64_t* __restrict__ rank, const uint32_t* __restrict__ wslot, uint64_t total,
                                    uint32_t* __restrict__ slot_node, uint32_t* __restrict__ nfirst) {
-  UG_FOR(g, total) if (flag[g]) { slot_node[wslot[g]] = (uint32_t)rank[g]; nfirst[rank[g]] = (uint32_t)g; }
+  SHN_GRID_FOR(g, total) if (flag[g]) { slot_node[wslot[g]] = (uint32_t)rank[g]; nfirst[rank[g]] = (uint32_t)g; }
 }
 // one edge per k1-window (row): degrees, and the edge itself remembered at both ends (meaningful where the degree is 1)
 __global__ void ug_degree_kernel(const uint32_t* __restrict__ wslot, const uint32_t* __restrict__ slot_node, const uint32_t* __restrict__ cid,
                                  const uint64_t* __restrict__ off, uint64_t total, int K, uint32_t* __restrict__ outdeg, uint32_t* __restrict__ indeg,
                                  uint32_t* __restrict__ out_to, uint32_t* __restrict__ in_from) {
-  UG_FOR(g, total) {
+  SHN_GRID_FOR(g, total) {
     if (wslot[g] == UG_NONE || g + (uint64_t)K + 1 > off[cid[g] + 1]) continue;
     const uint32_t u = slot_node[wslot[g]], v = slot_node[wslot[g + 1]];
     atomicAdd(&outdeg[u], 1u);
@@ -106,7 +104,7 @@ __global__ void ug_degree_kernel(const uint32_t* __restrict__ wslot, const uint3
 // condensable links: succ / pred along the chains
 __global__ void ug_links_kernel(const uint32_t* __restrict__ outdeg, const uint32_t* __restrict__ indeg, const uint32_t* __restrict__ out_to, uint64_t nn,
                                 uint32_t* __restrict__ succ, uint32_t* __restrict__ pred) {
-  UG_FOR(u, nn) {
+  SHN_GRID_FOR(u, nn) {
     if (outdeg[u] != 1) continue;
     const uint32_t v = out_to[u];
     if (indeg[v] == 1 && v != (uint32_t)u) { succ[u] = v; pred[v] = (uint32_t)u; }
@@ -114,15 +112,15 @@ __global__ void ug_links_kernel(const uint32_t* __restrict__ outdeg, const uint3
 }
 // list ranking by pointer jumping: (jump[u], dist[u]) = an ancestor along pred and the distance to it
 __global__ void ug_jump_init_kernel(const uint32_t* __restrict__ pred, uint64_t nn, uint32_t* __restrict__ jump, uint32_t* __restrict__ dist) {
-  UG_FOR(u, nn) { const uint32_t p = pred[u]; jump[u] = p == UG_NONE ? (uint32_t)u : p; dist[u] = p == UG_NONE ? 0u : 1u; }
+  SHN_GRID_FOR(u, nn) { const uint32_t p = pred[u]; jump[u] = p == UG_NONE ? (uint32_t)u : p; dist[u] = p == UG_NONE ? 0u : 1u; }
 }
 __global__ void ug_jump_kernel(const uint32_t* __restrict__ jin, const uint32_t* __restrict__ din, uint64_t nn, uint32_t* __restrict__ jout, uint32_t* __restrict__ dout) {
-  UG_FOR(u, nn) { const uint32_t j = jin[u]; jout[u] = jin[j]; dout[u] = din[u] + din[j]; }
+  SHN_GRID_FOR(u, nn) { const uint32_t j = jin[u]; jout[u] = jin[j]; dout[u] = din[u] + din[j]; }
 }
 // after the jumps: jump[u] is the chain's head unless u lies on a cycle; chain length by atomicMax at the head
 __global__ void ug_chain_len_kernel(const uint32_t* __restrict__ jump, const uint32_t* __restrict__ dist, const uint32_t* __restrict__ pred,
                                     const uint32_t* __restrict__ part_of_node, uint64_t nn, uint32_t* __restrict__ clen, uint32_t* __restrict__ cyclic) {
-  UG_FOR(u, nn) {
+  SHN_GRID_FOR(u, nn) {
     const uint32_t h = jump[u];
     if (pred[h] != UG_NONE) { cyclic[part_of_node[u]] = 1; continue; }
     atomicMax(&clen[h], dist[u] + 1);
@@ -130,18 +128,18 @@ __global__ void ug_chain_len_kernel(const uint32_t* __restrict__ jump, const uin
 }
 __global__ void ug_node_part_kernel(const uint32_t* __restrict__ nfirst, const uint32_t* __restrict__ cid, const uint32_t* __restrict__ part_of, uint64_t nn,
                                     uint32_t* __restrict__ part_of_node) {
-  UG_FOR(u, nn) part_of_node[u] = part_of[cid[nfirst[u]]];
+  SHN_GRID_FOR(u, nn) part_of_node[u] = part_of[cid[nfirst[u]]];
 }
 // heads of chains with >= 2 K-mers: flag for the scans (chain index, first group slot)
 __global__ void ug_multi_flag_kernel(const uint32_t* __restrict__ clen, uint64_t nn, uint32_t* __restrict__ is_multi, uint32_t* __restrict__ multi_len) {
-  UG_FOR(u, nn) { const bool m = clen[u] >= 2; is_multi[u] = m ? 1u : 0u; multi_len[u] = m ? clen[u] : 0u; }
+  SHN_GRID_FOR(u, nn) { const bool m = clen[u] >= 2; is_multi[u] = m ? 1u : 0u; multi_len[u] = m ? clen[u] : 0u; }
 }
 // chain-major layout of the K-mers of the multi-K-mer chains: slot = chain_off[head] + dist
 __global__ void ug_layout_kernel(const uint32_t* __restrict__ jump, const uint32_t* __restrict__ dist, const uint32_t* __restrict__ clen,
                                  const uint64_t* __restrict__ chain_off, const uint64_t* __restrict__ chain_idx, uint64_t nn,
                                  uint32_t* __restrict__ lay_node, uint32_t* __restrict__ gchain, uint64_t* __restrict__ gpos,
                                  uint64_t* __restrict__ coff, uint32_t* __restrict__ chain_head) {
-  UG_FOR(u, nn) {
+  SHN_GRID_FOR(u, nn) {
     const uint32_t h = jump[u];
     if (clen[h] < 2) continue;
     const uint64_t at = chain_off[h] + dist[u];
@@ -156,17 +154,17 @@ __global__ void ug_layout_kernel(const uint32_t* __restrict__ jump, const uint32
 // reset[i] = 1 where an ascending run of visiting positions starts (chain start, or predecessor visited later)
 __global__ void ug_reset_kernel(const uint32_t* __restrict__ gchain, const uint64_t* __restrict__ gpos, const uint64_t* __restrict__ coff, uint64_t ng,
                                 uint32_t* __restrict__ reset) {
-  UG_FOR(i, ng) reset[i] = (i == coff[gchain[i]] || !(gpos[i - 1] < gpos[i])) ? 1u : 0u;
+  SHN_GRID_FOR(i, ng) reset[i] = (i == coff[gchain[i]] || !(gpos[i - 1] < gpos[i])) ? 1u : 0u;
 }
 __global__ void ug_run_start_kernel(const uint32_t* __restrict__ reset, const uint64_t* __restrict__ rsum, uint64_t ng, uint64_t* __restrict__ starts) {
-  UG_FOR(i, ng) if (reset[i]) starts[rsum[i]] = i;            // rsum = exclusive scan: the index of this run
+  SHN_GRID_FOR(i, ng) if (reset[i]) starts[rsum[i]] = i;            // rsum = exclusive scan: the index of this run
 }
 // merged[i] = group i is alive when visited and not the chain's last: it merges with what follows.
 // boundary[i] = a new group starts at i.  Records the head merge time of the chain for the edge lists (the tail's: ug_chain_done_kernel).
 __global__ void ug_alive_kernel(const uint32_t* __restrict__ reset, const uint64_t* __restrict__ rsum, const uint64_t* __restrict__ starts,
                                 const uint32_t* __restrict__ gchain, const uint64_t* __restrict__ gpos, const uint64_t* __restrict__ coff, uint64_t ng,
                                 uint64_t round_tag, uint32_t* __restrict__ merged, uint64_t* __restrict__ t_head) {
-  UG_FOR(i, ng) {
+  SHN_GRID_FOR(i, ng) {
     const uint32_t c = gchain[i];
     const uint64_t run = reset[i] ? rsum[i] : rsum[i] - 1;      // exclusive scan counts the resets before i
     const bool alive = ((i - starts[run]) & 1ULL) == 0;
@@ -178,19 +176,19 @@ __global__ void ug_alive_kernel(const uint32_t* __restrict__ reset, const uint64
 }
 __global__ void ug_boundary_kernel(const uint32_t* __restrict__ merged, const uint32_t* __restrict__ gchain, const uint64_t* __restrict__ coff, uint64_t ng,
                                    uint32_t* __restrict__ boundary) {
-  UG_FOR(i, ng) boundary[i] = (i == coff[gchain[i]] || !merged[i - 1]) ? 1u : 0u;
+  SHN_GRID_FOR(i, ng) boundary[i] = (i == coff[gchain[i]] || !merged[i - 1]) ? 1u : 0u;
 }
 // creation time of the new groups: the largest visiting position among their merging groups
 __global__ void ug_newpos_kernel(const uint32_t* __restrict__ merged, const uint32_t* __restrict__ boundary, const uint64_t* __restrict__ bsum,
                                  const uint64_t* __restrict__ gpos, uint64_t ng, unsigned long long* __restrict__ newpos) {
-  UG_FOR(i, ng) {
+  SHN_GRID_FOR(i, ng) {
     const uint64_t g = boundary[i] ? bsum[i] : bsum[i] - 1;
     if (merged[i]) atomicMax(&newpos[g], (unsigned long long)gpos[i]);
   }
 }
 // groups per chain after the round
 __global__ void ug_chain_count_kernel(const uint32_t* __restrict__ boundary, const uint32_t* __restrict__ gchain, uint64_t ng, uint32_t* __restrict__ ccount) {
-  UG_FOR(i, ng) if (boundary[i]) atomicAdd(&ccount[gchain[i]], 1u);
+  SHN_GRID_FOR(i, ng) if (boundary[i]) atomicAdd(&ccount[gchain[i]], 1u);
 }
 // chains left with one group are finished (creation stamp recorded); the others keep their groups for the next round.
 // Tail time: every merge whose second node holds the chain's last K-mer re-creates that K-mer's out-edges, so when the last group is
@@ -202,7 +200,7 @@ __global__ void ug_chain_done_kernel(const uint32_t* __restrict__ ccount, const 
                                      const uint64_t* __restrict__ bsum, const unsigned long long* __restrict__ newpos, uint64_t nc, uint64_t round_tag,
                                      uint64_t* __restrict__ fin_stamp, uint64_t* __restrict__ fin_thead, uint64_t* __restrict__ fin_ttail,
                                      uint32_t* __restrict__ keep, uint32_t* __restrict__ keep_groups) {
-  UG_FOR(c, nc) {
+  SHN_GRID_FOR(c, nc) {
     const bool done = ccount[c] == 1;
     const uint64_t last = coff[c + 1] - 1;                           // (a chain in the array has >= 2 groups: last > coff[c])
     if (!boundary[last]) t_tail_in[c] = round_tag | (uint64_t)newpos[bsum[last] - 1];
@@ -222,7 +220,7 @@ __global__ void ug_carry_chains_kernel(const uint32_t* __restrict__ keep, const 
                                        const uint32_t* __restrict__ chain_head_in, const uint64_t* __restrict__ t_head_in, const uint64_t* __restrict__ t_tail_in,
                                        uint64_t nc, uint32_t* __restrict__ chain_head_out, uint64_t* __restrict__ t_head_out, uint64_t* __restrict__ t_tail_out,
                                        uint64_t* __restrict__ coff_out) {
-  UG_FOR(c, nc) if (keep[c]) {
+  SHN_GRID_FOR(c, nc) if (keep[c]) {
     const uint64_t n = ksum[c];
     chain_head_out[n] = chain_head_in[c]; t_head_out[n] = t_head_in[c]; t_tail_out[n] = t_tail_in[c];
     coff_out[n] = gsum[c];
@@ -232,7 +230,7 @@ __global__ void ug_carry_groups_kernel(const uint32_t* __restrict__ boundary, co
                                        const uint32_t* __restrict__ keep, const uint64_t* __restrict__ ksum, const uint64_t* __restrict__ gsum,
                                        const uint64_t* __restrict__ coff, const unsigned long long* __restrict__ newpos, const uint64_t* __restrict__ gpos,
                                        const uint32_t* __restrict__ merged, uint64_t ng, uint32_t* __restrict__ gchain_out, uint64_t* __restrict__ gpos_out) {
-  UG_FOR(i, ng) {
+  SHN_GRID_FOR(i, ng) {
     if (!boundary[i]) continue;
     const uint32_t c = gchain[i];
     if (!keep[c]) continue;
@@ -248,17 +246,17 @@ __global__ void ug_carry_groups_kernel(const uint32_t* __restrict__ boundary, co
 // ---- products
 // per K-mer node: chain head (itself for a single K-mer); per head: final-node record
 __global__ void ug_fin_single_kernel(const uint32_t* __restrict__ jump, const uint32_t* __restrict__ clen, uint64_t nn, uint64_t* __restrict__ fin_stamp) {
-  UG_FOR(u, nn) if (jump[u] == (uint32_t)u && clen[u] == 1) fin_stamp[u] = (uint64_t)u;    // round tag 0: before every merged node
+  SHN_GRID_FOR(u, nn) if (jump[u] == (uint32_t)u && clen[u] == 1) fin_stamp[u] = (uint64_t)u;    // round tag 0: before every merged node
 }
 __global__ void ug_head_flag_kernel(const uint32_t* __restrict__ jump, const uint32_t* __restrict__ pred, uint64_t nn, uint32_t* __restrict__ flag,
                                     uint32_t* __restrict__ blen, const uint32_t* __restrict__ clen, int K) {
-  UG_FOR(u, nn) { const bool h = jump[u] == (uint32_t)u && pred[u] == UG_NONE; flag[u] = h ? 1u : 0u; blen[u] = h ? (uint32_t)K + clen[u] - 1 : 0u; }
+  SHN_GRID_FOR(u, nn) { const bool h = jump[u] == (uint32_t)u && pred[u] == UG_NONE; flag[u] = h ? 1u : 0u; blen[u] = h ? (uint32_t)K + clen[u] - 1 : 0u; }
 }
 // bases of the final nodes: the head's K-mer, then the last base of every further K-mer of the chain
 __global__ void ug_bases_kernel(const uint8_t* __restrict__ bases, const uint32_t* __restrict__ nfirst, const uint32_t* __restrict__ jump,
                                 const uint32_t* __restrict__ dist, const uint32_t* __restrict__ pred, const uint64_t* __restrict__ boff, uint64_t nn, int K,
                                 uint8_t* __restrict__ out) {
-  UG_FOR(u, nn) {
+  SHN_GRID_FOR(u, nn) {
     const uint32_t h = jump[u];
     if (pred[h] != UG_NONE) continue;                               // on a cycle
     const uint64_t o = boff[h];
@@ -270,7 +268,7 @@ __global__ void ug_bases_kernel(const uint8_t* __restrict__ bases, const uint32_
 // edges between final nodes: the rows that are not condensable links
 __global__ void ug_edge_flag_kernel(const uint32_t* __restrict__ wslot, const uint32_t* __restrict__ slot_node, const uint32_t* __restrict__ cid,
                                     const uint64_t* __restrict__ off, const uint32_t* __restrict__ succ, uint64_t total, int K, uint32_t* __restrict__ flag) {
-  UG_FOR(g, total) {
+  SHN_GRID_FOR(g, total) {
     uint32_t f = 0;
     if (wslot[g] != UG_NONE && g + (uint64_t)K + 1 <= off[cid[g] + 1]) {
       const uint32_t u = slot_node[wslot[g]], v = slot_node[wslot[g + 1]];
@@ -282,7 +280,7 @@ __global__ void ug_edge_flag_kernel(const uint32_t* __restrict__ wslot, const ui
 __global__ void ug_edges_kernel(const uint32_t* __restrict__ flag, const uint64_t* __restrict__ epos, const uint32_t* __restrict__ wslot,
                                 const uint32_t* __restrict__ slot_node, const uint32_t* __restrict__ jump, uint64_t total, uint32_t* __restrict__ e_src,
                                 uint32_t* __restrict__ e_dst) {
-  UG_FOR(g, total) if (flag[g]) {
+  SHN_GRID_FOR(g, total) if (flag[g]) {
     const uint32_t u = slot_node[wslot[g]], v = slot_node[wslot[g + 1]];
     e_src[epos[g]] = jump[u];                   // chain heads (u is its chain's last K-mer, v its chain's first)
     e_dst[epos[g]] = jump[v];
@@ -292,7 +290,7 @@ __global__ void ug_edges_kernel(const uint32_t* __restrict__ flag, const uint64_
 // out-degree of a chain's last K-mer, recorded at its head
 __global__ void ug_tail_out_kernel(const uint32_t* __restrict__ jump, const uint32_t* __restrict__ dist, const uint32_t* __restrict__ clen,
                                    const uint32_t* __restrict__ pred, const uint32_t* __restrict__ outdeg, uint64_t nn, uint32_t* __restrict__ tail_out) {
-  UG_FOR(u, nn) { const uint32_t h = jump[u]; if (pred[h] == UG_NONE && dist[u] + 1 == clen[h]) tail_out[h] = outdeg[u]; }
+  SHN_GRID_FOR(u, nn) { const uint32_t h = jump[u]; if (pred[h] == UG_NONE && dist[u] + 1 == clen[h]) tail_out[h] = outdeg[u]; }
 }
 // the final nodes (chain heads) compacted in K-mer id order = partition by partition
 __global__ void ug_head_compact_kernel(const uint32_t* __restrict__ hflag, const uint64_t* __restrict__ hpos, const uint64_t* __restrict__ stamp,
@@ -300,7 +298,7 @@ __global__ void ug_head_compact_kernel(const uint32_t* __restrict__ hflag, const
                                        const uint32_t* __restrict__ tail_out, const uint32_t* __restrict__ part_of_node, const uint64_t* __restrict__ boff,
                                        uint64_t nn, uint64_t* __restrict__ o_stamp, uint64_t* __restrict__ o_thead, uint64_t* __restrict__ o_ttail,
                                        uint32_t* __restrict__ o_clen, uint32_t* __restrict__ o_tail_out, uint32_t* __restrict__ o_part, uint64_t* __restrict__ o_boff) {
-  UG_FOR(u, nn) if (hflag[u]) {
+  SHN_GRID_FOR(u, nn) if (hflag[u]) {
     const uint64_t i = hpos[u];
     o_stamp[i] = stamp[u]; o_thead[i] = thead[u]; o_ttail[i] = ttail[u]; o_clen[i] = clen[u]; o_tail_out[i] = tail_out[u];
     o_part[i] = part_of_node[u]; o_boff[i] = boff[u];
@@ -308,7 +306,7 @@ __global__ void ug_head_compact_kernel(const uint32_t* __restrict__ hflag, const
 }
 // edges as (compact head index of the source chain, of the destination chain)
 __global__ void ug_edge_heads_kernel(uint32_t* __restrict__ e_src, uint32_t* __restrict__ e_dst, const uint64_t* __restrict__ hpos, uint64_t ne) {
-  UG_FOR(x, ne) { e_src[x] = (uint32_t)hpos[e_src[x]]; e_dst[x] = (uint32_t)hpos[e_dst[x]]; }
+  SHN_GRID_FOR(x, ne) { e_src[x] = (uint32_t)hpos[e_src[x]]; e_dst[x] = (uint32_t)hpos[e_dst[x]]; }
 }
 
 }  // namespace
@@ -397,8 +395,8 @@ extern "C" int shn_unitigs_build(shn_ctx* ctx, const uint8_t* bases, const uint6
   HIP_TRY(hipMemsetAsync(d_bad, 0, 8, s));
   HIP_TRY(hipMemsetAsync(d_wslot + total, 0xFF, 8, s));
   hipLaunchKernelGGL(ug_cid_kernel, dim3((uint32_t)cdiv(n_contigs * 64, UG_BLK)), dim3(UG_BLK), 0, s, d_off, n_contigs, d_cid);
-  hipLaunchKernelGGL(ug_insert_kernel, dim3(ug_grid(total)), dim3(UG_BLK), 0, s, d_bases, d_off, d_cid, d_part_of, d_tab_off, total, K, d_tkey, d_tfirst, d_wslot, d_bad);
-  hipLaunchKernelGGL(ug_first_flag_kernel, dim3(ug_grid(total)), dim3(UG_BLK), 0, s, d_wslot, d_tfirst, total, d_flag);
+  hipLaunchKernelGGL(ug_insert_kernel, dim3(shn_grid(total, UG_BLK)), dim3(UG_BLK), 0, s, d_bases, d_off, d_cid, d_part_of, d_tab_off, total, K, d_tkey, d_tfirst, d_wslot, d_bad);
+  hipLaunchKernelGGL(ug_first_flag_kernel, dim3(shn_grid(total, UG_BLK)), dim3(UG_BLK), 0, s, d_wslot, d_tfirst, total, d_flag);
   uint64_t nn = 0;
   int rc = shn_device_scan_u32(ctx, d_flag, total, d_scan, &nn);
   if (rc) return rc;
@@ -423,21 +421,21 @@ extern "C" int shn_unitigs_build(shn_ctx* ctx, const uint8_t* bases, const uint6
   HIP_TRY(hipMemsetAsync(d_outdeg, 0, nn * 4, s)); HIP_TRY(hipMemsetAsync(d_indeg, 0, nn * 4, s));
   HIP_TRY(hipMemsetAsync(d_succ, 0xFF, nn * 4, s)); HIP_TRY(hipMemsetAsync(d_pred, 0xFF, nn * 4, s));
   HIP_TRY(hipMemsetAsync(d_clen, 0, nn * 4, s)); HIP_TRY(hipMemsetAsync(d_cyc, 0, (n_parts + 1) * 4, s));
-  hipLaunchKernelGGL(ug_node_ids_kernel, dim3(ug_grid(total)), dim3(UG_BLK), 0, s, d_flag, d_scan, d_wslot, total, d_slot_node, d_nfirst);
-  hipLaunchKernelGGL(ug_node_part_kernel, dim3(ug_grid(nn)), dim3(UG_BLK), 0, s, d_nfirst, d_cid, d_part_of, nn, d_node_part);
-  hipLaunchKernelGGL(ug_degree_kernel, dim3(ug_grid(total)), dim3(UG_BLK), 0, s, d_wslot, d_slot_node, d_cid, d_off, total, K, d_outdeg, d_indeg, d_out_to, d_in_from);
-  hipLaunchKernelGGL(ug_links_kernel, dim3(ug_grid(nn)), dim3(UG_BLK), 0, s, d_outdeg, d_indeg, d_out_to, nn, d_succ, d_pred);
-  hipLaunchKernelGGL(ug_jump_init_kernel, dim3(ug_grid(nn)), dim3(UG_BLK), 0, s, d_pred, nn, d_jump[0], d_dist[0]);
+  hipLaunchKernelGGL(ug_node_ids_kernel, dim3(shn_grid(total, UG_BLK)), dim3(UG_BLK), 0, s, d_flag, d_scan, d_wslot, total, d_slot_node, d_nfirst);
+  hipLaunchKernelGGL(ug_node_part_kernel, dim3(shn_grid(nn, UG_BLK)), dim3(UG_BLK), 0, s, d_nfirst, d_cid, d_part_of, nn, d_node_part);
+  hipLaunchKernelGGL(ug_degree_kernel, dim3(shn_grid(total, UG_BLK)), dim3(UG_BLK), 0, s, d_wslot, d_slot_node, d_cid, d_off, total, K, d_outdeg, d_indeg, d_out_to, d_in_from);
+  hipLaunchKernelGGL(ug_links_kernel, dim3(shn_grid(nn, UG_BLK)), dim3(UG_BLK), 0, s, d_outdeg, d_indeg, d_out_to, nn, d_succ, d_pred);
+  hipLaunchKernelGGL(ug_jump_init_kernel, dim3(shn_grid(nn, UG_BLK)), dim3(UG_BLK), 0, s, d_pred, nn, d_jump[0], d_dist[0]);
   int cur = 0;
   for (uint64_t span = 1; span < nn; span <<= 1) {
-    hipLaunchKernelGGL(ug_jump_kernel, dim3(ug_grid(nn)), dim3(UG_BLK), 0, s, d_jump[cur], d_dist[cur], nn, d_jump[cur ^ 1], d_dist[cur ^ 1]);
+    hipLaunchKernelGGL(ug_jump_kernel, dim3(shn_grid(nn, UG_BLK)), dim3(UG_BLK), 0, s, d_jump[cur], d_dist[cur], nn, d_jump[cur ^ 1], d_dist[cur ^ 1]);
     cur ^= 1;
     uint64_t max_contig = 0;
     (void)max_contig;
     if (span >= (1ULL << 24)) break;               // (a chain is no longer than its partition's contigs; 2^24 jumps of slack)
   }
   uint32_t *jump = d_jump[cur], *dist = d_dist[cur];
-  hipLaunchKernelGGL(ug_chain_len_kernel, dim3(ug_grid(nn)), dim3(UG_BLK), 0, s, jump, dist, d_pred, d_node_part, nn, d_clen, d_cyc);
+  hipLaunchKernelGGL(ug_chain_len_kernel, dim3(shn_grid(nn, UG_BLK)), dim3(UG_BLK), 0, s, jump, dist, d_pred, d_node_part, nn, d_clen, d_cyc);
   {
     std::vector<uint32_t> cyc(n_parts);
     HIP_TRY(hipMemcpyAsync(cyc.data(), d_cyc, n_parts * 4, hipMemcpyDeviceToHost, s));
@@ -449,14 +447,14 @@ extern "C" int shn_unitigs_build(shn_ctx* ctx, const uint8_t* bases, const uint6
   uint64_t *d_fin_stamp, *d_fin_thead, *d_fin_ttail;
   HIP_TRY(B.get(&d_fin_stamp, nn * 8)); HIP_TRY(B.get(&d_fin_thead, nn * 8)); HIP_TRY(B.get(&d_fin_ttail, nn * 8));
   HIP_TRY(hipMemsetAsync(d_fin_stamp, 0, nn * 8, s)); HIP_TRY(hipMemsetAsync(d_fin_thead, 0, nn * 8, s)); HIP_TRY(hipMemsetAsync(d_fin_ttail, 0, nn * 8, s));
-  hipLaunchKernelGGL(ug_fin_single_kernel, dim3(ug_grid(nn)), dim3(UG_BLK), 0, s, jump, d_clen, nn, d_fin_stamp);
+  hipLaunchKernelGGL(ug_fin_single_kernel, dim3(shn_grid(nn, UG_BLK)), dim3(UG_BLK), 0, s, jump, d_clen, nn, d_fin_stamp);
   uint64_t n_rounds = 0;
   {
     DevBufs R;
     uint32_t *d_is_multi, *d_multi_len;
     uint64_t *d_cidx, *d_coff0;
     HIP_TRY(R.get(&d_is_multi, (nn + 1) * 4)); HIP_TRY(R.get(&d_multi_len, (nn + 1) * 4)); HIP_TRY(R.get(&d_cidx, (nn + 2) * 8)); HIP_TRY(R.get(&d_coff0, (nn + 2) * 8));
-    hipLaunchKernelGGL(ug_multi_flag_kernel, dim3(ug_grid(nn)), dim3(UG_BLK), 0, s, d_clen, nn, d_is_multi, d_multi_len);
+    hipLaunchKernelGGL(ug_multi_flag_kernel, dim3(shn_grid(nn, UG_BLK)), dim3(UG_BLK), 0, s, d_clen, nn, d_is_multi, d_multi_len);
     uint64_t nc = 0, ng = 0;
     if ((rc = shn_device_scan_u32(ctx, d_is_multi, nn, d_cidx, &nc)) || (rc = shn_device_scan_u32(ctx, d_multi_len, nn, d_coff0, &ng))) return rc;
     if (nc) {
@@ -473,7 +471,7 @@ extern "C" int shn_unitigs_build(shn_ctx* ctx, const uint8_t* bases, const uint6
       HIP_TRY(R.get(&d_rsum, (ng + 2) * 8)); HIP_TRY(R.get(&d_starts, (ng + 2) * 8)); HIP_TRY(R.get(&d_bsum, (ng + 2) * 8));
       HIP_TRY(R.get(&d_ksum, (nc + 2) * 8)); HIP_TRY(R.get(&d_gsum, (nc + 2) * 8)); HIP_TRY(R.get(&d_newpos, (ng + 1) * 8));
       HIP_TRY(hipMemsetAsync(thead[0], 0, (nc + 1) * 8, s)); HIP_TRY(hipMemsetAsync(ttail[0], 0, (nc + 1) * 8, s));
-      hipLaunchKernelGGL(ug_layout_kernel, dim3(ug_grid(nn)), dim3(UG_BLK), 0, s, jump, dist, d_clen, d_coff0, d_cidx, nn, d_lay, gchain[0], gpos[0], coff[0], chead[0]);
+      hipLaunchKernelGGL(ug_layout_kernel, dim3(shn_grid(nn, UG_BLK)), dim3(UG_BLK), 0, s, jump, dist, d_clen, d_coff0, d_cidx, nn, d_lay, gchain[0], gpos[0], coff[0], chead[0]);
       HIP_TRY(hipMemcpyAsync(coff[0] + nc, &ng, 8, hipMemcpyHostToDevice, s));
       int a = 0;
       while (nc) {
@@ -481,25 +479,25 @@ extern "C" int shn_unitigs_build(shn_ctx* ctx, const uint8_t* bases, const uint6
         if (n_rounds > 4096) return shn_fail(SHN_ERR_INTERNAL, "shn_unitigs_build: the merge rounds do not end");
         const uint64_t tag = n_rounds << 40;                       // stamps: round in the high bits (round 0 = single K-mers)
         uint64_t nruns = 0, ngn = 0, ncn = 0, ngk = 0;
-        hipLaunchKernelGGL(ug_reset_kernel, dim3(ug_grid(ng)), dim3(UG_BLK), 0, s, gchain[a], gpos[a], coff[a], ng, d_reset);
+        hipLaunchKernelGGL(ug_reset_kernel, dim3(shn_grid(ng, UG_BLK)), dim3(UG_BLK), 0, s, gchain[a], gpos[a], coff[a], ng, d_reset);
         if ((rc = shn_device_scan_u32(ctx, d_reset, ng, d_rsum, &nruns))) return rc;
-        hipLaunchKernelGGL(ug_run_start_kernel, dim3(ug_grid(ng)), dim3(UG_BLK), 0, s, d_reset, d_rsum, ng, d_starts);
-        hipLaunchKernelGGL(ug_alive_kernel, dim3(ug_grid(ng)), dim3(UG_BLK), 0, s, d_reset, d_rsum, d_starts, gchain[a], gpos[a], coff[a], ng, tag, d_merged,
+        hipLaunchKernelGGL(ug_run_start_kernel, dim3(shn_grid(ng, UG_BLK)), dim3(UG_BLK), 0, s, d_reset, d_rsum, ng, d_starts);
+        hipLaunchKernelGGL(ug_alive_kernel, dim3(shn_grid(ng, UG_BLK)), dim3(UG_BLK), 0, s, d_reset, d_rsum, d_starts, gchain[a], gpos[a], coff[a], ng, tag, d_merged,
                            thead[a]);
-        hipLaunchKernelGGL(ug_boundary_kernel, dim3(ug_grid(ng)), dim3(UG_BLK), 0, s, d_merged, gchain[a], coff[a], ng, d_boundary);
+        hipLaunchKernelGGL(ug_boundary_kernel, dim3(shn_grid(ng, UG_BLK)), dim3(UG_BLK), 0, s, d_merged, gchain[a], coff[a], ng, d_boundary);
         if ((rc = shn_device_scan_u32(ctx, d_boundary, ng, d_bsum, &ngn))) return rc;
         HIP_TRY(hipMemsetAsync(d_newpos, 0, (ngn + 1) * 8, s));
         HIP_TRY(hipMemsetAsync(d_ccount, 0, (nc + 1) * 4, s));
-        hipLaunchKernelGGL(ug_newpos_kernel, dim3(ug_grid(ng)), dim3(UG_BLK), 0, s, d_merged, d_boundary, d_bsum, gpos[a], ng, d_newpos);
-        hipLaunchKernelGGL(ug_chain_count_kernel, dim3(ug_grid(ng)), dim3(UG_BLK), 0, s, d_boundary, gchain[a], ng, d_ccount);
-        hipLaunchKernelGGL(ug_chain_done_kernel, dim3(ug_grid(nc)), dim3(UG_BLK), 0, s, d_ccount, chead[a], thead[a], ttail[a], coff[a], d_boundary, d_bsum, d_newpos,
+        hipLaunchKernelGGL(ug_newpos_kernel, dim3(shn_grid(ng, UG_BLK)), dim3(UG_BLK), 0, s, d_merged, d_boundary, d_bsum, gpos[a], ng, d_newpos);
+        hipLaunchKernelGGL(ug_chain_count_kernel, dim3(shn_grid(ng, UG_BLK)), dim3(UG_BLK), 0, s, d_boundary, gchain[a], ng, d_ccount);
+        hipLaunchKernelGGL(ug_chain_done_kernel, dim3(shn_grid(nc, UG_BLK)), dim3(UG_BLK), 0, s, d_ccount, chead[a], thead[a], ttail[a], coff[a], d_boundary, d_bsum, d_newpos,
                            nc, tag, d_fin_stamp, d_fin_thead, d_fin_ttail, d_keep, d_keepg);
         if ((rc = shn_device_scan_u32(ctx, d_keep, nc, d_ksum, &ncn)) || (rc = shn_device_scan_u32(ctx, d_keepg, nc, d_gsum, &ngk))) return rc;
         if (ncn) {
-          hipLaunchKernelGGL(ug_carry_chains_kernel, dim3(ug_grid(nc)), dim3(UG_BLK), 0, s, d_keep, d_ksum, d_gsum, chead[a], thead[a], ttail[a], nc, chead[a ^ 1],
+          hipLaunchKernelGGL(ug_carry_chains_kernel, dim3(shn_grid(nc, UG_BLK)), dim3(UG_BLK), 0, s, d_keep, d_ksum, d_gsum, chead[a], thead[a], ttail[a], nc, chead[a ^ 1],
                              thead[a ^ 1], ttail[a ^ 1], coff[a ^ 1]);
           HIP_TRY(hipMemcpyAsync(coff[a ^ 1] + ncn, &ngk, 8, hipMemcpyHostToDevice, s));
-          hipLaunchKernelGGL(ug_carry_groups_kernel, dim3(ug_grid(ng)), dim3(UG_BLK), 0, s, d_boundary, d_bsum, gchain[a], d_keep, d_ksum, d_gsum, coff[a], d_newpos,
+          hipLaunchKernelGGL(ug_carry_groups_kernel, dim3(shn_grid(ng, UG_BLK)), dim3(UG_BLK), 0, s, d_boundary, d_bsum, gchain[a], d_keep, d_ksum, d_gsum, coff[a], d_newpos,
                              gpos[a], d_merged, ng, gchain[a ^ 1], gpos[a ^ 1]);
           HIP_TRY(hipStreamSynchronize(s));          // (ngk lives on the host stack)
         }
@@ -512,29 +510,29 @@ extern "C" int shn_unitigs_build(shn_ctx* ctx, const uint8_t* bases, const uint6
   // ---- products: final nodes (chain heads), their bases, the edges between them
   uint32_t *d_hflag, *d_blen, *d_eflag; uint64_t *d_hpos, *d_boff, *d_epos; uint8_t* d_obases;
   HIP_TRY(B.get(&d_hflag, (nn + 1) * 4)); HIP_TRY(B.get(&d_blen, (nn + 1) * 4)); HIP_TRY(B.get(&d_hpos, (nn + 2) * 8)); HIP_TRY(B.get(&d_boff, (nn + 2) * 8));
-  hipLaunchKernelGGL(ug_head_flag_kernel, dim3(ug_grid(nn)), dim3(UG_BLK), 0, s, jump, d_pred, nn, d_hflag, d_blen, d_clen, K);
+  hipLaunchKernelGGL(ug_head_flag_kernel, dim3(shn_grid(nn, UG_BLK)), dim3(UG_BLK), 0, s, jump, d_pred, nn, d_hflag, d_blen, d_clen, K);
   uint64_t nf = 0, nb = 0, ne = 0;
   if ((rc = shn_device_scan_u32(ctx, d_hflag, nn, d_hpos, &nf)) || (rc = shn_device_scan_u32(ctx, d_blen, nn, d_boff, &nb))) return rc;
   HIP_TRY(B.get(&d_obases, nb + 64));
-  hipLaunchKernelGGL(ug_bases_kernel, dim3(ug_grid(nn)), dim3(UG_BLK), 0, s, d_bases, d_nfirst, jump, dist, d_pred, d_boff, nn, K, d_obases);
+  hipLaunchKernelGGL(ug_bases_kernel, dim3(shn_grid(nn, UG_BLK)), dim3(UG_BLK), 0, s, d_bases, d_nfirst, jump, dist, d_pred, d_boff, nn, K, d_obases);
   HIP_TRY(B.get(&d_eflag, (total + 1) * 4)); HIP_TRY(B.get(&d_epos, (total + 2) * 8));
-  hipLaunchKernelGGL(ug_edge_flag_kernel, dim3(ug_grid(total)), dim3(UG_BLK), 0, s, d_wslot, d_slot_node, d_cid, d_off, d_succ, total, K, d_eflag);
+  hipLaunchKernelGGL(ug_edge_flag_kernel, dim3(shn_grid(total, UG_BLK)), dim3(UG_BLK), 0, s, d_wslot, d_slot_node, d_cid, d_off, d_succ, total, K, d_eflag);
   if ((rc = shn_device_scan_u32(ctx, d_eflag, total, d_epos, &ne))) return rc;
   uint32_t *d_esrc = nullptr, *d_edst = nullptr;
   if (ne) {
     HIP_TRY(B.get(&d_esrc, ne * 4)); HIP_TRY(B.get(&d_edst, ne * 4));
-    hipLaunchKernelGGL(ug_edges_kernel, dim3(ug_grid(total)), dim3(UG_BLK), 0, s, d_eflag, d_epos, d_wslot, d_slot_node, jump, total, d_esrc, d_edst);
+    hipLaunchKernelGGL(ug_edges_kernel, dim3(shn_grid(total, UG_BLK)), dim3(UG_BLK), 0, s, d_eflag, d_epos, d_wslot, d_slot_node, jump, total, d_esrc, d_edst);
   }
   // the final nodes' records, compacted on the device (chain heads in K-mer id order, i.e. partition by partition)
   uint32_t *d_tail_out, *d_oclen, *d_otail, *d_opart; uint64_t *d_ostamp, *d_othead, *d_ottail, *d_oboff;
   HIP_TRY(B.get(&d_tail_out, nn * 4));
   HIP_TRY(hipMemsetAsync(d_tail_out, 0, nn * 4, s));
-  hipLaunchKernelGGL(ug_tail_out_kernel, dim3(ug_grid(nn)), dim3(UG_BLK), 0, s, jump, dist, d_clen, d_pred, d_outdeg, nn, d_tail_out);
+  hipLaunchKernelGGL(ug_tail_out_kernel, dim3(shn_grid(nn, UG_BLK)), dim3(UG_BLK), 0, s, jump, dist, d_clen, d_pred, d_outdeg, nn, d_tail_out);
   HIP_TRY(B.get(&d_oclen, (nf + 1) * 4)); HIP_TRY(B.get(&d_otail, (nf + 1) * 4)); HIP_TRY(B.get(&d_opart, (nf + 1) * 4));
   HIP_TRY(B.get(&d_ostamp, (nf + 1) * 8)); HIP_TRY(B.get(&d_othead, (nf + 1) * 8)); HIP_TRY(B.get(&d_ottail, (nf + 1) * 8)); HIP_TRY(B.get(&d_oboff, (nf + 1) * 8));
-  hipLaunchKernelGGL(ug_head_compact_kernel, dim3(ug_grid(nn)), dim3(UG_BLK), 0, s, d_hflag, d_hpos, d_fin_stamp, d_fin_thead, d_fin_ttail, d_clen, d_tail_out,
+  hipLaunchKernelGGL(ug_head_compact_kernel, dim3(shn_grid(nn, UG_BLK)), dim3(UG_BLK), 0, s, d_hflag, d_hpos, d_fin_stamp, d_fin_thead, d_fin_ttail, d_clen, d_tail_out,
                      d_node_part, d_boff, nn, d_ostamp, d_othead, d_ottail, d_oclen, d_otail, d_opart, d_oboff);
-  if (ne) hipLaunchKernelGGL(ug_edge_heads_kernel, dim3(ug_grid(ne)), dim3(UG_BLK), 0, s, d_esrc, d_edst, d_hpos, ne);
+  if (ne) hipLaunchKernelGGL(ug_edge_heads_kernel, dim3(shn_grid(ne, UG_BLK)), dim3(UG_BLK), 0, s, d_esrc, d_edst, d_hpos, ne);
   std::vector<uint32_t> h_clen(nf), tail_out(nf), h_part(nf), h_esrc(ne), h_edst(ne);
   std::vector<uint64_t> h_stamp(nf), h_thead(nf), h_ttail(nf), h_boff(nf);
   std::string obases(nb, '\0');

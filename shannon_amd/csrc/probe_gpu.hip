@@ -5,12 +5,12 @@
 // (gpmetis run + r2 run of a big component): singleton sets are set p = {p}; the k1-mers of several partitions are few, they
 // go to the host where their sets are interned.
 #include "common.h"
+#include "runs.h"
 #include <algorithm>
 #include <cstring>
 #include <map>
 
 #define PG_BLK 256
-#define PG_FOR(i, n) for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (uint64_t)gridDim.x * blockDim.x)
 
 struct shn_probe {
   shn_table* table = nullptr;
@@ -18,12 +18,11 @@ struct shn_probe {
 };
 
 namespace {
-static inline uint32_t pg_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(cdiv(n, PG_BLK), 1), 1u << 20); }
 
 // run heads of the sorted windows: one entry per distinct k1-mer; single[i] = 1 if all its windows lie in one partition
 __global__ void pg_head_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ cid,
                                const uint32_t* __restrict__ part_of, uint64_t n, uint32_t* __restrict__ head, uint32_t* __restrict__ multi) {
-  PG_FOR(i, n) {
+  SHN_GRID_FOR(i, n) {
     if (i && keys[i] == keys[i - 1]) { head[i] = 0; multi[i] = 0; continue; }
     head[i] = 1;
     uint64_t e = i + 1;
@@ -35,7 +34,7 @@ __global__ void pg_head_kernel(const uint64_t* __restrict__ keys, const uint32_t
 __global__ void pg_unique_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ cid,
                                  const uint32_t* __restrict__ part_of, const uint32_t* __restrict__ head, const uint64_t* __restrict__ hpos, uint64_t n,
                                  uint64_t* __restrict__ ukeys, uint32_t* __restrict__ uvals) {
-  PG_FOR(i, n) if (head[i]) { ukeys[hpos[i]] = keys[i]; uvals[hpos[i]] = part_of[cid[vals[i]]] + 1; }    // set p = {p}; multi ones are patched
+  SHN_GRID_FOR(i, n) if (head[i]) { ukeys[hpos[i]] = keys[i]; uvals[hpos[i]] = part_of[cid[vals[i]]] + 1; }    // set p = {p}; multi ones are patched
 }
 // number of different partitions among the windows of the run that starts at i (they come in ascending partition order: the sort
 // is stable and the contigs were laid out partition by partition); the first two in p1 / p2
@@ -57,7 +56,7 @@ __device__ __forceinline__ uint32_t pg_run_parts(const uint64_t* __restrict__ ke
 __global__ void pg_pair_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ cid,
                                const uint32_t* __restrict__ part_of, const uint32_t* __restrict__ multi, const uint64_t* __restrict__ hpos,
                                uint64_t n, unsigned long long* __restrict__ n_out, uint64_t* __restrict__ o_pair, uint32_t* __restrict__ o_uidx) {
-  PG_FOR(i, n) {
+  SHN_GRID_FOR(i, n) {
     if (!multi[i]) continue;
     uint32_t p1 = 0, p2 = 0;
     if (pg_run_parts(keys, vals, cid, part_of, n, i, p1, p2) != 2) continue;
@@ -66,15 +65,12 @@ __global__ void pg_pair_kernel(const uint64_t* __restrict__ keys, const uint32_t
     o_uidx[at] = (uint32_t)hpos[i];
   }
 }
-__global__ void pg_pair_head_kernel(const uint64_t* __restrict__ pairs, uint64_t n, uint32_t* __restrict__ head) {
-  PG_FOR(i, n) head[i] = (i == 0 || pairs[i] != pairs[i - 1]) ? 1u : 0u;
-}
 // value of every such k1-mer = id of its pair's set + 1; the distinct pairs, in order, for the host
 __global__ void pg_pair_patch_kernel(const uint64_t* __restrict__ pairs, const uint32_t* __restrict__ uidx, const uint32_t* __restrict__ head,
                                      const uint64_t* __restrict__ pos, uint64_t n, uint32_t first_sid, uint32_t* __restrict__ uvals,
                                      uint64_t* __restrict__ distinct) {
-  PG_FOR(i, n) {
-    const uint64_t run = pos[i] - (head[i] ? 0 : 1);
+  SHN_GRID_FOR(i, n) {
+    const uint64_t run = shn_run_index(head, pos, i);
     uvals[uidx[i]] = first_sid + (uint32_t)run + 1;
     if (head[i]) distinct[run] = pairs[i];
   }
@@ -84,7 +80,7 @@ __global__ void pg_pair_patch_kernel(const uint64_t* __restrict__ pairs, const u
 __global__ void pg_multi_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ cid,
                                 const uint32_t* __restrict__ part_of, const uint32_t* __restrict__ multi, const uint64_t* __restrict__ hpos,
                                 uint64_t n, unsigned long long* __restrict__ n_out, uint64_t cap, uint32_t* __restrict__ o_uidx, uint32_t* __restrict__ o_part) {
-  PG_FOR(i, n) {
+  SHN_GRID_FOR(i, n) {
     if (!multi[i]) continue;
     uint32_t p1 = 0, p2 = 0;
     if (pg_run_parts(keys, vals, cid, part_of, n, i, p1, p2) < 3) continue;
@@ -95,7 +91,7 @@ __global__ void pg_multi_kernel(const uint64_t* __restrict__ keys, const uint32_
   }
 }
 __global__ void pg_patch_kernel(const uint32_t* __restrict__ uidx, const uint32_t* __restrict__ setid, uint64_t n, uint32_t* __restrict__ uvals) {
-  PG_FOR(i, n) uvals[uidx[i]] = setid[i] + 1;
+  SHN_GRID_FOR(i, n) uvals[uidx[i]] = setid[i] + 1;
 }
 }  // namespace
 
@@ -121,7 +117,7 @@ extern "C" int shn_probe_build(shn_ctx* ctx, const uint8_t* bases, const uint64_
     if (part_of[c] >= n_parts || (c && part_of[c] < part_of[c - 1])) return shn_fail(SHN_ERR_ARG, "shn_probe_build: part_of must be ascending and < n_parts");
   SHN_ENTER(ctx);
   shn_stage_begin(ctx);
-  hipStream_t s = ctx->stream; shn_use_stream(s);
+  hipStream_t s = ctx->stream;
   shn_probe* P = new shn_probe();
   struct Guard { shn_probe* p; ~Guard() { shn_probe_destroy(p); } } guard{P};
   // set p = {p} for every partition; sets of several partitions follow
@@ -145,32 +141,29 @@ extern "C" int shn_probe_build(shn_ctx* ctx, const uint8_t* bases, const uint64_
     if (nv) {
       uint32_t *d_head, *d_multi; uint64_t *d_hpos;
       HIP_TRY(B.get(&d_head, (nv + 1) * 4)); HIP_TRY(B.get(&d_multi, (nv + 1) * 4)); HIP_TRY(B.get(&d_hpos, (nv + 2) * 8));
-      hipLaunchKernelGGL(pg_head_kernel, dim3(pg_grid(nv)), dim3(PG_BLK), 0, s, keys, vals, d_cid, d_part, nv, d_head, d_multi);
+      hipLaunchKernelGGL(pg_head_kernel, dim3(shn_grid(nv, PG_BLK)), dim3(PG_BLK), 0, s, keys, vals, d_cid, d_part, nv, d_head, d_multi);
       if ((rc = shn_device_scan_u32(ctx, d_head, nv, d_hpos, &nu))) return rc;
       HIP_TRY(B.get(&ukeys, (nu + 1) * 8)); HIP_TRY(B.get(&uvals, (nu + 1) * 4));
-      hipLaunchKernelGGL(pg_unique_kernel, dim3(pg_grid(nv)), dim3(PG_BLK), 0, s, keys, vals, d_cid, d_part, d_head, d_hpos, nv, ukeys, uvals);
+      hipLaunchKernelGGL(pg_unique_kernel, dim3(shn_grid(nv, PG_BLK)), dim3(PG_BLK), 0, s, keys, vals, d_cid, d_part, d_head, d_hpos, nv, ukeys, uvals);
       unsigned long long* d_nm; uint32_t *d_mu = nullptr, *d_mp = nullptr;
       HIP_TRY(B.get(&d_nm, 8));
       // k1-mers of exactly two partitions: their sets are interned on the device (pg_pair_kernel)
       {
-        uint64_t *d_pair, *d_pair2, *d_ppos, *d_dist; uint32_t *d_pu, *d_pu2, *d_phead;
+        uint64_t *d_pair, *d_pair2, *d_dist; uint32_t *d_pu, *d_pu2;
         HIP_TRY(B.get(&d_pair, (nu + 1) * 8)); HIP_TRY(B.get(&d_pair2, (nu + 1) * 8)); HIP_TRY(B.get(&d_pu, (nu + 1) * 4)); HIP_TRY(B.get(&d_pu2, (nu + 1) * 4));
         HIP_TRY(hipMemsetAsync(d_nm, 0, 8, s));
-        hipLaunchKernelGGL(pg_pair_kernel, dim3(pg_grid(nv)), dim3(PG_BLK), 0, s, keys, vals, d_cid, d_part, d_multi, d_hpos, nv, d_nm, d_pair, d_pu);
+        hipLaunchKernelGGL(pg_pair_kernel, dim3(shn_grid(nv, PG_BLK)), dim3(PG_BLK), 0, s, keys, vals, d_cid, d_part, d_multi, d_hpos, nv, d_nm, d_pair, d_pu);
         unsigned long long n_pair = 0;
         HIP_TRY(hipMemcpyAsync(&n_pair, d_nm, 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (n_pair) {
-          int pbits = 1;
-          while ((1ULL << pbits) < (uint64_t)n_parts) pbits++;
-          if ((rc = shn_sort_pairs(ctx, d_pair, d_pu, d_pair2, d_pu2, n_pair, 0, 32 + pbits))) return rc;
-          HIP_TRY(B.get(&d_phead, (n_pair + 1) * 4)); HIP_TRY(B.get(&d_ppos, (n_pair + 2) * 8));
-          hipLaunchKernelGGL(pg_pair_head_kernel, dim3(pg_grid(n_pair)), dim3(PG_BLK), 0, s, d_pair, (uint64_t)n_pair, d_phead);
-          uint64_t n_dist = 0;
-          if ((rc = shn_device_scan_u32(ctx, d_phead, n_pair, d_ppos, &n_dist))) return rc;
+          if ((rc = shn_sort_pairs(ctx, d_pair, d_pu, d_pair2, d_pu2, n_pair, 0, 32 + shn_bits_for(n_parts)))) return rc;
+          ShnRuns runs;                           // a run = the k1-mers of one pair of partitions: one set
+          if ((rc = shn_sorted_runs(ctx, B, d_pair, n_pair, 0, 0, &runs))) return rc;
+          const uint64_t n_dist = runs.n_runs;
           HIP_TRY(B.get(&d_dist, (n_dist + 1) * 8));
           const uint32_t first_sid = (uint32_t)(P->set_off.size() - 1);
-          hipLaunchKernelGGL(pg_pair_patch_kernel, dim3(pg_grid(n_pair)), dim3(PG_BLK), 0, s, d_pair, d_pu, d_phead, d_ppos, (uint64_t)n_pair, first_sid, uvals, d_dist);
+          hipLaunchKernelGGL(pg_pair_patch_kernel, dim3(shn_grid(n_pair, PG_BLK)), dim3(PG_BLK), 0, s, d_pair, d_pu, runs.head, runs.pos, (uint64_t)n_pair, first_sid, uvals, d_dist);
           std::vector<uint64_t> dist(n_dist);
           HIP_TRY(hipMemcpyAsync(dist.data(), d_dist, n_dist * 8, hipMemcpyDeviceToHost, s));
           HIP_TRY(hipStreamSynchronize(s));
@@ -186,7 +179,7 @@ extern "C" int shn_probe_build(shn_ctx* ctx, const uint8_t* bases, const uint64_
       while (true) {
         HIP_TRY(B.get(&d_mu, cap * 4)); HIP_TRY(B.get(&d_mp, cap * 4));
         HIP_TRY(hipMemsetAsync(d_nm, 0, 8, s));
-        hipLaunchKernelGGL(pg_multi_kernel, dim3(pg_grid(nv)), dim3(PG_BLK), 0, s, keys, vals, d_cid, d_part, d_multi, d_hpos, nv, d_nm, cap, d_mu, d_mp);
+        hipLaunchKernelGGL(pg_multi_kernel, dim3(shn_grid(nv, PG_BLK)), dim3(PG_BLK), 0, s, keys, vals, d_cid, d_part, d_multi, d_hpos, nv, d_nm, cap, d_mu, d_mp);
         HIP_TRY(hipMemcpyAsync(&nm, d_nm, 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (nm <= cap) break;
@@ -220,13 +213,11 @@ extern "C" int shn_probe_build(shn_ctx* ctx, const uint8_t* bases, const uint64_
         HIP_TRY(B.get(&d_pu, pu.size() * 4)); HIP_TRY(B.get(&d_ps, ps.size() * 4));
         HIP_TRY(hipMemcpyAsync(d_pu, pu.data(), pu.size() * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(d_ps, ps.data(), ps.size() * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(pg_patch_kernel, dim3(pg_grid(pu.size())), dim3(PG_BLK), 0, s, d_pu, d_ps, (uint64_t)pu.size(), uvals);
+        hipLaunchKernelGGL(pg_patch_kernel, dim3(shn_grid(pu.size(), PG_BLK)), dim3(PG_BLK), 0, s, d_pu, d_ps, (uint64_t)pu.size(), uvals);
         HIP_TRY(hipStreamSynchronize(s));
       }
     }
   }
-  uint64_t dummy_k = 0; uint32_t dummy_v = 0;
-  (void)dummy_k; (void)dummy_v;
   if (!ukeys) { HIP_TRY(B.get(&ukeys, 8)); HIP_TRY(B.get(&uvals, 4)); }
   int rc = shn_table_from_pairs(ctx, ukeys, uvals, nu, k1, 0, &P->table);
   if (rc) return rc;

@@ -9,6 +9,7 @@
 // The high-quality mask is the ingest's (shn_reads_quality_mask, ingest.hip).
 #include "record_expand_dev.h"
 #include "quorum_dev.h"
+#include "runs.h"
 
 int shn_reads_clone(shn_ctx* ctx, const shn_reads* src, shn_reads** out);      // core.hip
 int shn_reads_refresh_bad(shn_ctx* ctx, shn_reads* r);
@@ -16,14 +17,12 @@ int shn_reads_refresh_bad(shn_ctx* ctx, shn_reads* r);
 namespace {
 
 constexpr int Q_BLK = 256;
-static inline uint32_t q_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(cdiv(n, Q_BLK), 1), 1u << 20); }
-#define Q_FOR(i, n) for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (uint64_t)gridDim.x * blockDim.x)
 
 __device__ __forceinline__ uint32_t q_len(const ReadSetView& S, uint64_t r) { return S.len ? S.len[r] : S.fixed_len; }
 
 // HQ windows of every read: a window ends at base j when j and the k - 1 bases before it are all marked.  One mask word per 64 bases.
 __global__ __launch_bounds__(Q_BLK) void quorum_count_kernel(ReadSetView S, const uint64_t* __restrict__ hq, int k, uint32_t* __restrict__ cnt) {
-  Q_FOR(r, S.n) {
+  SHN_GRID_FOR(r, S.n) {
     const uint32_t len = q_len(S, r);
     const uint64_t mb = S.word_base(r) >> 1;
     uint32_t run = 0, c = 0;
@@ -43,7 +42,7 @@ __global__ __launch_bounds__(Q_BLK) void quorum_count_kernel(ReadSetView S, cons
 __global__ __launch_bounds__(Q_BLK) void quorum_fill_kernel(ReadSetView S, const uint64_t* __restrict__ hq, int k, const uint64_t* __restrict__ off,
                                                             uint64_t* __restrict__ keys) {
   const uint64_t kmask = k == 32 ? ~0ULL : ((1ULL << (2 * k)) - 1);
-  Q_FOR(r, S.n) {
+  SHN_GRID_FOR(r, S.n) {
     const uint32_t len = q_len(S, r);
     const uint64_t wb = S.word_base(r);
     uint64_t at = off[r];
@@ -64,24 +63,13 @@ __global__ __launch_bounds__(Q_BLK) void quorum_fill_kernel(ReadSetView S, const
   }
 }
 
-__global__ void quorum_heads_kernel(const uint64_t* __restrict__ keys, uint64_t n, uint32_t* __restrict__ head) {
-  Q_FOR(i, n) head[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
-}
-__global__ void quorum_starts_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ head, const uint64_t* __restrict__ pos, uint64_t n,
-                                     uint64_t* __restrict__ ukeys, uint32_t* __restrict__ ustart) {
-  Q_FOR(i, n) if (head[i]) { ukeys[pos[i]] = keys[i]; ustart[pos[i]] = (uint32_t)i; }
-}
-__global__ void quorum_runs_kernel(const uint32_t* __restrict__ ustart, uint64_t nu, uint64_t n, uint32_t* __restrict__ ucnt) {
-  Q_FOR(j, nu) ucnt[j] = (uint32_t)((j + 1 < nu ? (uint64_t)ustart[j + 1] : n) - ustart[j]);
-}
-
 // One read per thread.  S: the reads as they are (read only); ow / om: the output set's words and mask, already a copy of S's.
 // ctr[5]: reads with an anchor, reads changed, substitutions, stopped directions, window reverts.
 __global__ __launch_bounds__(Q_BLK) void quorum_correct_kernel(ReadSetView S, TabIdx T, const uint32_t* __restrict__ counts, int k, uint32_t A, uint32_t W,
                                                                uint32_t E, uint64_t* __restrict__ ow, uint64_t* __restrict__ om,
                                                                unsigned long long* __restrict__ ctr) {
   const uint64_t kmask = k == 32 ? ~0ULL : ((1ULL << (2 * k)) - 1);
-  Q_FOR(r, S.n) {
+  SHN_GRID_FOR(r, S.n) {
     const uint32_t len = q_len(S, r);
     if (len < (uint32_t)k) continue;
     const uint64_t wb = S.word_base(r);
@@ -144,7 +132,7 @@ extern "C" int shn_quorum_table(shn_ctx* ctx, const shn_reads* const* sets, cons
     uint64_t r0 = 0, bytes = 0;
     for (int i = 0; i < n_sets; i++) {
       if (sets[i]->n_reads)
-        hipLaunchKernelGGL(quorum_count_kernel, dim3(q_grid(sets[i]->n_reads)), dim3(Q_BLK), 0, s, view_of(sets[i]), (const uint64_t*)masks[i]->d_hq, k, d_cnt + r0);
+        hipLaunchKernelGGL(quorum_count_kernel, dim3(shn_grid(sets[i]->n_reads, Q_BLK)), dim3(Q_BLK), 0, s, view_of(sets[i]), (const uint64_t*)masks[i]->d_hq, k, d_cnt + r0);
       r0 += sets[i]->n_reads;
       bytes += sets[i]->n_words / 2 * 8 + sets[i]->n_reads * 4;
     }
@@ -153,9 +141,7 @@ extern "C" int shn_quorum_table(shn_ctx* ctx, const shn_reads* const* sets, cons
     t.bytes(bytes + n_reads * 12);
   }
   if (total >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, "shn_quorum_table: 2^32 high-quality windows or more in one call (" + std::to_string(total) + ")");
-  uint64_t *d_keys = nullptr, *d_tmp = nullptr, *d_ukeys = nullptr;
-  uint32_t* d_ucnt = nullptr;
-  uint64_t nu = 0;
+  uint64_t *d_keys = nullptr, *d_tmp = nullptr;
   HIP_TRY(B.get(&d_keys, (total + 1) * 8)); HIP_TRY(B.get(&d_tmp, (total + 1) * 8));
   if (total) {
     // bytes: words and masks once, 8 B of offset per read, 8 B per window written
@@ -163,7 +149,7 @@ extern "C" int shn_quorum_table(shn_ctx* ctx, const shn_reads* const* sets, cons
     uint64_t r0 = 0, bytes = 0;
     for (int i = 0; i < n_sets; i++) {
       if (sets[i]->n_reads)
-        hipLaunchKernelGGL(quorum_fill_kernel, dim3(q_grid(sets[i]->n_reads)), dim3(Q_BLK), 0, s, view_of(sets[i]), (const uint64_t*)masks[i]->d_hq, k,
+        hipLaunchKernelGGL(quorum_fill_kernel, dim3(shn_grid(sets[i]->n_reads, Q_BLK)), dim3(Q_BLK), 0, s, view_of(sets[i]), (const uint64_t*)masks[i]->d_hq, k,
                            (const uint64_t*)(d_off + r0), d_keys);
       r0 += sets[i]->n_reads;
       bytes += sets[i]->n_words * 12 + sets[i]->n_reads * 8;
@@ -175,21 +161,13 @@ extern "C" int shn_quorum_table(shn_ctx* ctx, const shn_reads* const* sets, cons
     // bytes: the sort reads and writes every key once per 8-bit pass; heads, scan and run lengths touch 8 + 4 + 8 B per window and
     // 8 + 4 + 4 B per distinct k-mer; the table build reads and writes the pairs once more
     TimerRegion t(ctx, T_QUORUM_TABLE);
-    if (total) {
-      uint64_t* sorted = nullptr;
-      if ((rc = shn_sort_keys(ctx, d_keys, d_tmp, total, 0, 2 * k, &sorted))) return rc;
-      uint32_t *d_head = nullptr, *d_ustart = nullptr; uint64_t* d_pos = nullptr;
-      HIP_TRY(B.get(&d_head, (total + 1) * 4)); HIP_TRY(B.get(&d_pos, (total + 2) * 8));
-      hipLaunchKernelGGL(quorum_heads_kernel, dim3(q_grid(total)), dim3(Q_BLK), 0, s, (const uint64_t*)sorted, total, d_head);
-      if ((rc = shn_device_scan_u32(ctx, d_head, total, d_pos, &nu))) return rc;
-      HIP_TRY(B.get(&d_ukeys, (nu + 1) * 8)); HIP_TRY(B.get(&d_ustart, (nu + 1) * 4)); HIP_TRY(B.get(&d_ucnt, (nu + 1) * 4));
-      hipLaunchKernelGGL(quorum_starts_kernel, dim3(q_grid(total)), dim3(Q_BLK), 0, s, (const uint64_t*)sorted, (const uint32_t*)d_head, (const uint64_t*)d_pos, total,
-                         d_ukeys, d_ustart);
-      hipLaunchKernelGGL(quorum_runs_kernel, dim3(q_grid(nu)), dim3(Q_BLK), 0, s, (const uint32_t*)d_ustart, nu, total, d_ucnt);
-      HIP_TRY(hipGetLastError());
-    } else { HIP_TRY(B.get(&d_ukeys, 8)); HIP_TRY(B.get(&d_ucnt, 4)); }
+    uint64_t* sorted = d_keys;
+    if (total && (rc = shn_sort_keys(ctx, d_keys, d_tmp, total, 0, 2 * k, &sorted))) return rc;
+    ShnRuns runs;                                 // (no window: no run, nothing launched)
+    if ((rc = shn_sorted_runs(ctx, B, sorted, total, 0, SHN_RUNS_KEYS | SHN_RUNS_LEN, &runs))) return rc;
+    const uint64_t nu = runs.n_runs;
     t.bytes(total * 16 * (uint64_t)((2 * k + 7) / 8) + total * 20 + nu * 16 + nu * 24);
-    if ((rc = shn_table_from_pairs(ctx, d_ukeys, d_ucnt, nu, k, 1, out))) return rc;
+    if ((rc = shn_table_from_pairs(ctx, runs.keys, runs.len, nu, k, 1, out))) return rc;
   }
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipGetLastError());
@@ -220,7 +198,7 @@ extern "C" int shn_quorum_correct(shn_ctx* ctx, const shn_reads* reads, const sh
     if (rc) return rc;
     hipError_t e = hipMemsetAsync(d_ctr, 0, 5 * 8, s);
     if (e == hipSuccess && reads->n_reads) {
-      hipLaunchKernelGGL(quorum_correct_kernel, dim3(q_grid(reads->n_reads)), dim3(Q_BLK), 0, s, view_of(reads), shn_tab_idx(table), (const uint32_t*)table->d_counts, k,
+      hipLaunchKernelGGL(quorum_correct_kernel, dim3(shn_grid(reads->n_reads, Q_BLK)), dim3(Q_BLK), 0, s, view_of(reads), shn_tab_idx(table), (const uint32_t*)table->d_counts, k,
                          anchor_count, window, max_subs, r->d_words, r->d_mask, d_ctr);
       e = hipGetLastError();
     }

@@ -1,8 +1,9 @@
 """Inputs and checkers for the shared device primitives: the radix sort (csrc/sort.hip), the scan (shn_device_scan_u32, csrc/count.hip),
-the three bucket searches of csrc/common.h and the table builds (shn_table_create, shn_table_from_pairs).
+the runs of a sorted array (shn_sorted_runs, csrc/runs.hip), the three bucket searches of csrc/common.h and the table builds
+(shn_table_create, shn_table_from_pairs).
 
-Plain numpy: nothing here loads the library.  The references are np.argsort(kind="stable"), np.cumsum in uint64, a Python dict and
-np.unique / np.add.at.  The inputs are the smallest at which each primitive takes another way: a wavefront's share of a sort tile
+Plain numpy: nothing here loads the library.  The references are np.argsort(kind="stable"), np.cumsum in uint64, np.flatnonzero of
+the neighbours that differ, a Python dict and np.unique / np.add.at.  The inputs are the smallest at which each primitive takes another way: a wavefront's share of a sort tile
 (1024), a tile (4096), a histogram longer than one scan block (5 tiles), more than 1024 scan block sums (2^20 elements), a final
 bucket past the 950 distinct keys its LDS table takes.  Every case is made on demand from a seed of its own and cached.
 
@@ -20,6 +21,7 @@ CAP_LIMIT = 950                  # distinct keys a final bucket's LDS table take
 PER_BUCKET = 96                  # shn_table_from_pairs / shn_table_create: bits = the first with (n >> bits) <= 96
 
 SortCase = namedtuple("SortCase", "keys vals lo hi")
+RunCase = namedtuple("RunCase", "keys shift")
 TableCase = namedtuple("TableCase", "keys counts k canonical")
 
 
@@ -112,6 +114,30 @@ def check_scan(values, out, total):
     assert out.dtype == np.uint64, "the scan's output is 64 bits wide, not %s" % out.dtype
     _same("sums", out, want)
     assert int(total) == int(want[-1]), "total %d, expected %d" % (int(total), int(want[-1]))
+
+
+def run_starts(keys, shift):
+    """where the runs of equal (key >> shift) begin"""
+    k = np.asarray(keys, dtype=np.uint64) >> U64(shift)
+    if not len(k):
+        return np.zeros(0, dtype=np.int64)
+    return np.flatnonzero(np.r_[True, k[1:] != k[:-1]])
+
+
+def check_runs(keys, shift, n_runs, run_keys, start, length, pos):
+    """everything shn_sorted_runs gives: n_runs runs; run_keys[r] = the whole first key of run r; start[r] = its first element, with
+    the sentinel start[n_runs] = n; length[r] = its elements; pos = the n + 1 exclusive sums of the head flags"""
+    keys = np.asarray(keys, dtype=np.uint64)
+    n, want = len(keys), run_starts(keys, shift)
+    assert int(n_runs) == len(want), "%d runs, expected %d" % (int(n_runs), len(want))
+    start, length, pos = np.asarray(start), np.asarray(length), np.asarray(pos)
+    assert start.dtype == np.uint32 and length.dtype == np.uint32 and pos.dtype == np.uint64, (start.dtype, length.dtype, pos.dtype)
+    _same("starts and the sentinel", start, np.r_[want, n].astype(np.uint32))
+    _same("lengths", length, np.diff(np.r_[want, n]).astype(np.uint32))
+    _same("run keys", np.asarray(run_keys, dtype=np.uint64), keys[want])
+    head = np.zeros(n, dtype=np.uint64)
+    head[want] = 1
+    _same("positions", pos, np.r_[0, np.cumsum(head)].astype(np.uint64))
 
 
 def expected_find(table_keys, queries):
@@ -249,6 +275,65 @@ def scan_case(name):
         v = (rng.integers(0, 97, size=n) == 0).astype(np.uint32)
     v.setflags(write=False)
     return v
+
+
+# ---------------------------------------------------------------- run cases
+# sizes: nothing, one, two; around one workgroup (256); around one scan block (1024); several scan blocks with an odd tail
+RUN_SIZES = (0, 1, 2, 255, 256, 257, 1023, 1024, 1025, 70001)
+RUN_PATTERNS = ("all_equal", "all_distinct", "random_runs", "edge_runs", "shift20", "bit63", "all_ones")
+RUN_CASES = tuple("%s_%d" % (p, n) for n in RUN_SIZES for p in RUN_PATTERNS)
+
+
+def _random_lengths(rng, n):
+    """run lengths 1 .. 9 that sum to n"""
+    lens = []
+    while sum(lens) < n:
+        lens.append(int(rng.integers(1, 10)))
+    if lens:
+        lens[-1] -= sum(lens) - n
+    return lens
+
+
+@lru_cache(maxsize=None)
+def run_case(name):
+    """keys sorted by (key >> shift):
+    all_equal / all_distinct   one run / n runs
+    random_runs                runs of 1 .. 9 elements
+    edge_runs                  the first and the last run hold one element (n >= 3: longer ones between them)
+    shift20                    random_runs by the bits from 20 up, random bits below the shift inside a run
+    bit63                      two runs (n >= 2) whose keys differ in bit 63 alone, shift 0
+    all_ones                   random_runs, the last run's key 0xFFFFFFFFFFFFFFFF"""
+    pattern, n = name.rsplit("_", 1)
+    n = int(n)
+    rng = _rng("runs:" + name)
+    shift = 20 if pattern == "shift20" else 0
+    if pattern == "all_equal":
+        lens = [n] if n else []
+    elif pattern == "all_distinct":
+        lens = [1] * n
+    elif pattern == "edge_runs":
+        lens = [1] * n if n < 3 else [1] + _random_lengths(rng, n - 2) + [1]
+    elif pattern == "bit63":
+        lens = [n // 2, n - n // 2] if n >= 2 else [1] * n
+    else:
+        lens = _random_lengths(rng, n)
+    if pattern == "bit63":
+        low = int(rng.integers(0, 1 << 63))
+        values = np.array([low, low | (1 << 63)][2 - len(lens):], dtype=np.uint64)
+    else:
+        values = np.zeros(0, dtype=np.uint64)
+        while len(values) < len(lens):                                  # distinct, ascending, below 2^(64 - shift) - 1
+            values = np.unique(rng.integers(0, (1 << (64 - shift)) - 1, size=len(lens) + 8, dtype=np.uint64))
+        values = values[np.sort(rng.choice(len(values), size=len(lens), replace=False))]
+        if pattern == "all_ones" and len(values):
+            values[-1] = U64(ALL64)
+    keys = np.repeat(values, lens) << U64(shift)
+    if shift:
+        keys |= rng.integers(0, 1 << shift, size=n, dtype=np.uint64)
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    assert len(keys) == n
+    keys.setflags(write=False)
+    return RunCase(keys, shift)
 
 
 # ---------------------------------------------------------------- table cases

@@ -1,4 +1,4 @@
-"""Thin numpy wrappers of the primitives' test hooks (include/shannon_hip.h: shn_debug_sort_pairs ... shn_debug_table_view) and the two
+"""Thin numpy wrappers of the primitives' test hooks (include/shannon_hip.h: shn_debug_sort_pairs ... shn_debug_table_view, shn_debug_sorted_runs) and the two
 table builds, for tests/test_primitives_gpu.py and its child process tests/primitives_poison_worker.py."""
 import ctypes as C
 import numpy as np
@@ -37,6 +37,20 @@ def scan(ctx, values, with_total):
     total = C.c_uint64(0x5A5A5A5A)
     _lib.check(L.shn_debug_scan_u32(ctx.h, _ptr(values), len(values), out.ctypes.data, C.byref(total) if with_total else None))
     return out, (int(total.value) if with_total else int(out[-1]))
+
+
+def sorted_runs(ctx, keys, shift):
+    """(n_runs, run keys[n_runs], start[n_runs + 1], len[n_runs], pos[n + 1]) of keys sorted by (key >> shift)"""
+    _lib, L = _L()
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    n = len(keys)
+    rk, ln = np.full(n, 0x5A5A5A5A5A5A5A5A, dtype=np.uint64), np.full(n, 0x5A5A5A5A, dtype=np.uint32)
+    st, pos = np.full(n + 1, 0x5A5A5A5A, dtype=np.uint32), np.full(n + 1, 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)
+    n_runs = C.c_uint64(0x5A5A5A5A)
+    _lib.check(L.shn_debug_sorted_runs(ctx.h, _ptr(keys), n, int(shift), _ptr(rk), st.ctypes.data, _ptr(ln), pos.ctypes.data, C.byref(n_runs)))
+    r = int(n_runs.value)
+    assert r <= n
+    return r, rk[:r], st[:r + 1], ln[:r], pos
 
 
 def table_create(ctx, keys, counts, k, canonical):

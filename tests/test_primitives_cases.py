@@ -103,6 +103,71 @@ def test_scan_checker():
         pc.check_scan(r, bad, good[-1])
 
 
+def _good_runs(name):
+    c = pc.run_case(name)
+    st = pc.run_starts(c.keys, c.shift)
+    n = len(c.keys)
+    head = np.zeros(n, dtype=np.uint64)
+    head[st] = 1
+    return c, [len(st), c.keys[st].copy(), np.r_[st, n].astype(np.uint32), np.diff(np.r_[st, n]).astype(np.uint32),
+               np.r_[0, np.cumsum(head)].astype(np.uint64)]
+
+
+def test_runs_checker_accepts_the_reference_and_rejects_four_wrong_answers():
+    for name in pc.RUN_CASES:
+        c, good = _good_runs(name)
+        pc.check_runs(c.keys, c.shift, *good)
+    c, good = _good_runs("random_runs_1025")
+    n_runs, rk, start, length, pos = good
+    with pytest.raises(AssertionError):                                 # the last run missing
+        pc.check_runs(c.keys, c.shift, n_runs - 1, rk[:-1], np.r_[start[:-2], start[-1:]], length[:-1], pos)
+    bad = start.copy()
+    bad[-1] -= 1                                                        # start[n_runs] is not n
+    with pytest.raises(AssertionError):
+        pc.check_runs(c.keys, c.shift, n_runs, rk, bad, length, pos)
+    bad = length.copy()
+    bad[len(bad) // 2] += 1                                             # a length off by one
+    with pytest.raises(AssertionError):
+        pc.check_runs(c.keys, c.shift, n_runs, rk, start, bad, pos)
+    with pytest.raises(AssertionError):
+        pc.check_runs(c.keys, c.shift, n_runs, rk, start, length - np.uint32(1), pos)
+    c, good = _good_runs("shift20_1025")                                # the runs of the whole keys: split where the bits below the shift change
+    st0 = pc.run_starts(c.keys, 0)
+    assert len(st0) > good[0]
+    n = len(c.keys)
+    head = np.zeros(n, dtype=np.uint64)
+    head[st0] = 1
+    with pytest.raises(AssertionError):
+        pc.check_runs(c.keys, c.shift, len(st0), c.keys[st0], np.r_[st0, n].astype(np.uint32), np.diff(np.r_[st0, n]).astype(np.uint32),
+                      np.r_[0, np.cumsum(head)].astype(np.uint64))
+    with pytest.raises(AssertionError):                                 # the first key of a run, not its shifted form
+        pc.check_runs(c.keys, c.shift, good[0], good[1] >> U64(c.shift), *good[2:])
+
+
+def test_run_cases_are_what_they_claim():
+    assert len(set(pc.RUN_CASES)) == len(pc.RUN_CASES) == len(pc.RUN_SIZES) * len(pc.RUN_PATTERNS)
+    for name in pc.RUN_CASES:
+        c = pc.run_case(name)
+        n = int(name.rsplit("_", 1)[1])
+        k = c.keys >> U64(c.shift)
+        assert c.keys.dtype == np.uint64 and len(c.keys) == n and (k[1:] >= k[:-1]).all()
+    for n in pc.RUN_SIZES:
+        runs = {p: pc.run_starts(*pc.run_case("%s_%d" % (p, n))) for p in pc.RUN_PATTERNS}
+        assert len(runs["all_equal"]) == min(n, 1) and len(runs["all_distinct"]) == n
+        if n >= 2:
+            b = pc.run_case("bit63_%d" % n).keys
+            assert len(runs["bit63"]) == 2 and int(b[0]) ^ int(b[-1]) == 1 << 63
+        if n >= 3:
+            e = runs["edge_runs"]
+            assert e[1] == 1 and e[-1] == n - 1                         # a first and a last run of one element
+        if n:
+            assert int(pc.run_case("all_ones_%d" % n).keys[-1]) == pc.ALL64
+        if n >= 255:
+            s = pc.run_case("shift20_%d" % n)
+            assert s.shift == 20 and 2 * len(runs["shift20"]) < len(pc.run_starts(s.keys, 0))     # ignoring the shift splits most runs
+            assert 1 < len(runs["random_runs"]) < n
+
+
 def test_find_checker():
     tk = np.array([40, 10, 30, 20], dtype=np.uint64)                    # (download order: by bucket, not by key)
     q = np.array([10, 11, 20, 40, 0], dtype=np.uint64)

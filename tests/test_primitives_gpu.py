@@ -1,5 +1,5 @@
 """GPU: the shared device primitives, each against a plain numpy reference through its test hook (csrc/debug_hooks.hip) -- the radix
-sort (shn_sort_pairs, shn_sort_keys), the scan (shn_device_scan_u32), the three bucket searches of csrc/common.h (shn_table_find,
+sort (shn_sort_pairs, shn_sort_keys), the scan (shn_device_scan_u32), the runs of a sorted array (shn_sorted_runs), the three bucket searches of csrc/common.h (shn_table_find,
 shn_table_find_k, shn_tab_find) and the two table builds (shn_table_create on the host, shn_table_from_pairs on the device).  The
 inputs and checkers are tests/primitives_cases.py; tests/test_primitives_cases.py shows on the CPU that they tell right from wrong."""
 import os, subprocess, sys
@@ -68,6 +68,15 @@ def test_scan_with_and_without_the_host_total(ctx, name):
     for with_total in (True, False):
         out, total = ph.scan(ctx, v, with_total)
         pc.check_scan(v, out, total)
+
+
+# ---------------------------------------------------------------- runs
+@pytest.mark.parametrize("name", pc.RUN_CASES)
+def test_sorted_runs_heads_keys_starts_lengths_and_positions(ctx, name):
+    """shn_sorted_runs with everything wanted (its scan and scatter are shn_runs_from_heads').  The refusal of 2^32 keys or more is not
+    tested: it would take 32 GB of keys."""
+    c = pc.run_case(name)
+    pc.check_runs(c.keys, c.shift, *ph.sorted_runs(ctx, c.keys, c.shift))
 
 
 # ---------------------------------------------------------------- tables: content
@@ -176,10 +185,10 @@ def test_from_pairs_tries_again_with_more_buckets_after_a_bucket_overflows(ctx, 
 def test_the_primitives_with_every_workspace_request_poisoned():
     """SHN_DEV_POISON=165 SHN_DEV_POISON_WS=1 (read once per process, hence the child): every allocator block and, on every request,
     every workspace slot is filled with 0xA5 first.  A primitive that reads a slot it did not write -- the sort's histogram, the scan's
-    block sums, the build's cursors -- gives wrong elements; the child counts them."""
+    block sums, the runs' positions, the build's cursors -- gives wrong elements; the child counts them."""
     p = subprocess.run([sys.executable, "-X", "faulthandler", os.path.join(ROOT, "tests", "primitives_poison_worker.py")], stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, env=dict(os.environ, SHN_DEV_POISON="165", SHN_DEV_POISON_WS="1"), timeout=300)
     assert p.returncode == 0, (p.returncode, p.stdout[-500:], p.stderr[-3000:])
     words = p.stdout.split()
     counts = {words[i]: int(words[i + 1]) for i in range(0, len(words), 2)}
-    assert counts == {"FIND": 0, "SCAN": 0, "SORT_KEYS": 0, "SORT_PAIRS": 0, "TABLE": 0}, counts
+    assert counts == {"FIND": 0, "RUNS": 0, "SCAN": 0, "SORT_KEYS": 0, "SORT_PAIRS": 0, "TABLE": 0}, counts

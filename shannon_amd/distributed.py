@@ -1078,7 +1078,7 @@ class GpuOps(object):
         found on the device (shn_mbgraph_run_rows), all components go through shn_sparse_flow in one call.  {partition: FASTA}."""
         import time, threading
         from concurrent.futures import ThreadPoolExecutor
-        from . import mbgraph_native, _lib
+        from . import mbgraph_native, _lib, graph_intake
         if self.unitigs is None:
             return None
         t0 = time.time()
@@ -1090,48 +1090,42 @@ class GpuOps(object):
             merged = (np.zeros((0, 1), np.uint8), np.zeros(0, np.uint8)) if local is not None else self._merge_pieces(pieces, self.strand_specific and paired)
             ragged = merged if isinstance(merged, exchange.RaggedPiece) else None
             rows, rc1 = (np.zeros((0, 1), np.uint8), np.zeros(0, np.uint8)) if ragged is not None else merged
-            rb = None
-            for _attempt in (0, 1):
+            def run(rb):
+                if ragged is not None:
+                    # reads that carry their lengths: codes + offsets straight to the graph stage, as the one-process path hands
+                    # ragged reads over (pipeline.py: gather_codes / gather_codes_ss -> run_partition_handle)
+                    b1, o1, b2, o2, r1, r2 = self._ragged_args(ragged, paired)
+                    return mbgraph_native.run_partition_handle(rb, 0 if rb is None else len(rb) // (K + 1), K, b1, o1, b2, o2, ctx=self.ctx, enc=1,
+                                                               rc1=r1, rc2=r2, unitigs=self.unitigs, part=i)
+                if self.strand_specific and len(rows):
+                    # -s: the rows hold reads_1[i] and, for pairs, reads_2[i] side by side (collect); the second mate is read on its
+                    # reverse strand (rc2 = 1): the pairs (reads_1[i], RC(reads_2[i])) of shannon.py:407-411, not strand-doubled
+                    n, L2 = rows.shape
+                    L = L2 // 2 if paired else L2
+                    b1 = np.ascontiguousarray(rows[:, :L]).reshape(-1)
+                    o1 = np.arange(n + 1, dtype=np.uint64) * np.uint64(L)
+                    b2 = np.ascontiguousarray(rows[:, L:]).reshape(-1) if paired else None
+                    return mbgraph_native.run_partition_handle(rb, 0 if rb is None else len(rb) // (K + 1), K, b1, o1, b2, o1 if paired else None,
+                                                               ctx=self.ctx, enc=1, rc1=np.zeros(n, np.uint8), rc2=np.ones(n, np.uint8) if paired else None,
+                                                               unitigs=self.unitigs, part=i)
+                if local is not None and len(local):
+                    # this rank's own reads, named by their rows in its resident input (as pipeline.assemble_resident does)
+                    return mbgraph_native.run_partition_rows(self.ctx, self.unitigs, i, self.d1, self.d2 if paired else None, self.store.r1,
+                                                             self.store.r2 if paired else None, local.sel, rb, 0 if rb is None else len(rb) // (K + 1))
+                if len(rows) == 0:
+                    z, o = np.zeros(1, np.uint8), np.zeros(1, np.uint64)
+                    return mbgraph_native.run_partition_handle(rb, 0 if rb is None else len(rb) // (K + 1), K, z, o, z if paired else None,
+                                                               o if paired else None, ctx=self.ctx, unitigs=self.unitigs, part=i)
+                with up:
+                    d = self._dev.Reads.from_codes(self.ctx, rows)
+                n = len(rows)
+                didx = (np.arange(n, dtype=np.int64) + np.where(rc1 != 0, n, 0)).astype(np.uint32)
                 try:
-                    if ragged is not None:
-                        # reads that carry their lengths: codes + offsets straight to the graph stage, as the one-process path hands
-                        # ragged reads over (pipeline.py: gather_codes / gather_codes_ss -> run_partition_handle)
-                        b1, o1, b2, o2, r1, r2 = self._ragged_args(ragged, paired)
-                        return mbgraph_native.run_partition_handle(rb, 0 if rb is None else len(rb) // (K + 1), K, b1, o1, b2, o2, ctx=self.ctx, enc=1,
-                                                                   rc1=r1, rc2=r2, unitigs=self.unitigs, part=i)
-                    if self.strand_specific and len(rows):
-                        # -s: the rows hold reads_1[i] and, for pairs, reads_2[i] side by side (collect); the second mate is read on its
-                        # reverse strand (rc2 = 1): the pairs (reads_1[i], RC(reads_2[i])) of shannon.py:407-411, not strand-doubled
-                        n, L2 = rows.shape
-                        L = L2 // 2 if paired else L2
-                        b1 = np.ascontiguousarray(rows[:, :L]).reshape(-1)
-                        o1 = np.arange(n + 1, dtype=np.uint64) * np.uint64(L)
-                        b2 = np.ascontiguousarray(rows[:, L:]).reshape(-1) if paired else None
-                        return mbgraph_native.run_partition_handle(rb, 0 if rb is None else len(rb) // (K + 1), K, b1, o1, b2, o1 if paired else None,
-                                                                   ctx=self.ctx, enc=1, rc1=np.zeros(n, np.uint8), rc2=np.ones(n, np.uint8) if paired else None,
-                                                                   unitigs=self.unitigs, part=i)
-                    if local is not None and len(local):
-                        # this rank's own reads, named by their rows in its resident input (as pipeline.assemble_resident does)
-                        return mbgraph_native.run_partition_rows(self.ctx, self.unitigs, i, self.d1, self.d2 if paired else None, self.store.r1,
-                                                                 self.store.r2 if paired else None, local.sel, rb, 0 if rb is None else len(rb) // (K + 1))
-                    if len(rows) == 0:
-                        z, o = np.zeros(1, np.uint8), np.zeros(1, np.uint64)
-                        return mbgraph_native.run_partition_handle(rb, 0 if rb is None else len(rb) // (K + 1), K, z, o, z if paired else None,
-                                                                   o if paired else None, ctx=self.ctx, unitigs=self.unitigs, part=i)
-                    with up:
-                        d = self._dev.Reads.from_codes(self.ctx, rows)
-                    n = len(rows)
-                    didx = (np.arange(n, dtype=np.int64) + np.where(rc1 != 0, n, 0)).astype(np.uint32)
-                    try:
-                        return mbgraph_native.run_partition_rows(self.ctx, self.unitigs, i, d, d if paired else None, rows, rows if paired else None,
-                                                                 didx, rb, 0 if rb is None else len(rb) // (K + 1))
-                    finally:
-                        d.close()
-                except _lib.ShannonError as ex:
-                    if rb is not None or "needs the k1-mer rows" not in str(ex):
-                        raise
-                    rb_ = part["k1mer_bytes"][names[i]]                  # a partition holding a cycle of condensable edges
-                    rb = rb_() if callable(rb_) else rb_
+                    return mbgraph_native.run_partition_rows(self.ctx, self.unitigs, i, d, d if paired else None, rows, rows if paired else None,
+                                                             didx, rb, 0 if rb is None else len(rb) // (K + 1))
+                finally:
+                    d.close()
+            return graph_intake.with_k1mer_rows(run, part, names[i])     # (rows: a partition holding a cycle of condensable edges)
         nthreads = max(1, min(len(owned), _lib.host_cpus()))
         graphs, futs = [], []
         try:

@@ -453,9 +453,16 @@ int shn_filter_fp_count(shn_ctx* ctx, const uint64_t* covers, uint32_t n_covers,
 typedef struct shn_abundance shn_abundance;
 int shn_abundance_classes(shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off, uint64_t n_tr, const shn_reads* r1, const shn_reads* r2,
                           int strand_specific, uint32_t max_span, shn_abundance** out);
-/* sizes[6]: transcripts, pairs, mapped pairs, classes, members of all classes, bins of the histogram (max_span + 1) */
+/* shn_abundance_classes_single -- the same for single reads (`kallisto quant --single`, filter_kallisto.py:25; DESIGN.md 3.13 rule
+ * 1): for every read of the resident set the transcripts that hold a placement of its minimum cost, the read tried as itself and,
+ * unless strand_specific, as its reverse complement; reads with equal sets merged into classes.  The same handle; it holds no
+ * histogram (0 bins): the fragment-length model of single reads is fixed (abundance.eff_lengths_model). */
+int shn_abundance_classes_single(shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off, uint64_t n_tr, const shn_reads* r, int strand_specific,
+                                 shn_abundance** out);
+/* sizes[6]: transcripts, pairs (or reads), mapped pairs, classes, members of all classes, bins of the histogram (max_span + 1; 0
+ * behind shn_abundance_classes_single) */
 int shn_abundance_sizes(const shn_abundance* a, uint64_t* sizes);
-/* class_off[classes + 1], members[class_off[classes]], n_c[classes], hist[max_span + 1] (host) */
+/* class_off[classes + 1], members[class_off[classes]], n_c[classes], hist[max_span + 1] (host; hist may be NULL for a handle of 0 bins) */
 int shn_abundance_export(const shn_abundance* a, uint64_t* class_off, uint32_t* members, uint64_t* n_c, uint64_t* hist);
 void shn_abundance_destroy(shn_abundance* a);
 /* shn_abundance_em -- the EM of `kallisto quant` (filter_kallisto.py:29; its est_counts column is what filter_kallisto.py:13-14 reads)

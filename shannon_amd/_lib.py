@@ -75,6 +75,7 @@ SIGNATURES = {
     "shn_filter_fp_cover": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_uint32, vp, vp]),
     "shn_filter_fp_count": (C.c_int, [vp, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp]),
     "shn_abundance_classes": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, C.c_int, C.c_uint32, vpp]),
+    "shn_abundance_classes_single": (C.c_int, [vp, vp, vp, C.c_uint64, vp, C.c_int, vpp]),
     "shn_abundance_sizes": (C.c_int, [vp, vp]),
     "shn_abundance_export": (C.c_int, [vp, vp, vp, vp, vp]),
     "shn_abundance_destroy": (None, [vp]),

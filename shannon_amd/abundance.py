@@ -13,32 +13,63 @@ its abundance.tsv line reaches the cutoff.  Here kallisto is a stated rule (DESI
     decide         filter_kallisto.py:8-21 on the TEXT of abundance.tsv and of the FASTA -> the text of the filtered FASTA
     apply          final transcripts {name: sequence} -> (filtered {name: sequence}, table, tsv text, FASTA text before)
 
-`eff_lengths`, `abundance_tsv` and `decide` need neither the library nor a GPU.
+Single reads (the command is shannon_amd/quant.py):
+
+    classes_single     a read's compatibility set over its orientations, classes, mapped count (shn_abundance_classes_single)
+    eff_lengths_model  effective lengths from the fixed fragment-length model (mean, sd), in double
+    quantify_single    names + sequences + one resident read set -> table
+
+`eff_lengths`, `eff_lengths_model`, `abundance_tsv` and `decide` need neither the library nor a GPU.
 """
 import ctypes as C
 import io
+import math
 import numpy as np
 
 MAX_SPAN = 500        # as --filter_FP: the longest fragment a concordant pair may span
 SEED = 15             # a transcript shorter than this takes part in no class
+MODEL_MEAN, MODEL_SD, MODEL_BINS = 200.0, 20.0, 1000        # single reads: kallisto quant --single -l 200 -s 20 (filter_kallisto.py:25), fragments of 0..999 bases
 HEADER = "target_id\tlength\teff_length\test_counts\ttpm\n"
+
+
+def _transcript_text(seqs):
+    """(text uint8, t_off uint64[n + 1]) of the transcripts one after the other; one shorter than SEED bases or with a base outside
+    ACGT is handed over empty: it takes part in no class"""
+    seqs = [s if len(s) >= SEED and not s.encode().translate(None, b"ACGTacgt") else "" for s in seqs]
+    t_off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    if seqs:
+        t_off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+    joined = "".join(seqs).encode()
+    return (np.frombuffer(joined, dtype=np.uint8) if joined else np.zeros(1, np.uint8)), t_off
 
 
 def classes(ctx, seqs, d1, d2, strand_specific, max_span=MAX_SPAN):
     """rules 1-3 (shn_abundance_classes): {"class_off", "members", "n_c", "hist", "mapped", "fragments"}.  A transcript shorter
     than SEED bases or with a base outside ACGT is handed over empty: it takes part in no class."""
     from . import _lib
-    seqs = [s if len(s) >= SEED and not s.encode().translate(None, b"ACGTacgt") else "" for s in seqs]
-    n_tr = len(seqs)
-    t_off = np.zeros(n_tr + 1, dtype=np.uint64)
-    if n_tr:
-        t_off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
-    joined = "".join(seqs).encode()
-    text = np.frombuffer(joined, dtype=np.uint8) if joined else np.zeros(1, np.uint8)
+    text, t_off = _transcript_text(seqs)
     h = C.c_void_p()
     lib = _lib.lib()
-    _lib.check(lib.shn_abundance_classes(ctx.h, text.ctypes.data, t_off.ctypes.data, n_tr, d1.h, d2.h, 1 if strand_specific else 0, int(max_span),
+    _lib.check(lib.shn_abundance_classes(ctx.h, text.ctypes.data, t_off.ctypes.data, len(seqs), d1.h, d2.h, 1 if strand_specific else 0, int(max_span),
                                          C.byref(h)))
+    return _export(lib, h)
+
+
+def classes_single(ctx, seqs, d, strand_specific):
+    """rules 1 of DESIGN.md 3.13 and 3 of 3.10 for the single reads of the resident set d (shn_abundance_classes_single): {"class_off",
+    "members", "n_c", "mapped", "fragments"} (fragments: the reads) and "hist", empty -- single reads have no span.  Transcripts as in
+    `classes`."""
+    from . import _lib
+    text, t_off = _transcript_text(seqs)
+    h = C.c_void_p()
+    lib = _lib.lib()
+    _lib.check(lib.shn_abundance_classes_single(ctx.h, text.ctypes.data, t_off.ctypes.data, len(seqs), d.h, 1 if strand_specific else 0, C.byref(h)))
+    return _export(lib, h)
+
+
+def _export(lib, h):
+    """what a handle of shn_abundance_classes / _single holds, as arrays; destroys the handle"""
+    from . import _lib
     try:
         sizes = np.zeros(6, dtype=np.uint64)
         _lib.check(lib.shn_abundance_sizes(h, sizes.ctypes.data))
@@ -47,7 +78,7 @@ def classes(ctx, seqs, d1, d2, strand_specific, max_span=MAX_SPAN):
         members = np.zeros(max(n_entries, 1), dtype=np.uint32)
         n_c = np.zeros(max(n_classes, 1), dtype=np.uint64)
         hist = np.zeros(n_bins, dtype=np.uint64)
-        _lib.check(lib.shn_abundance_export(h, class_off.ctypes.data, members.ctypes.data, n_c.ctypes.data, hist.ctypes.data))
+        _lib.check(lib.shn_abundance_export(h, class_off.ctypes.data, members.ctypes.data, n_c.ctypes.data, hist.ctypes.data if n_bins else None))
     finally:
         lib.shn_abundance_destroy(h)
     return {"class_off": class_off, "members": members[:n_entries], "n_c": n_c[:n_classes], "hist": hist, "mapped": mapped, "fragments": n_frag}
@@ -115,6 +146,48 @@ def quantify(ctx, names, seqs, d1, d2, strand_specific, max_span=MAX_SPAN):
                 "rounds": 0, "hist": np.zeros(max_span + 1, np.uint64)}
     cl = classes(ctx, seqs, d1, d2, strand_specific, max_span)
     eff = eff_lengths(lens, cl["hist"])
+    alpha, rounds = em(ctx, cl["class_off"], cl["members"], cl["n_c"], eff)
+    return {"names": list(names), "length": lens, "eff_length": eff.tolist(), "est_counts": alpha.tolist(), "tpm": tpm_of(alpha, eff),
+            "mapped": cl["mapped"], "fragments": cl["fragments"], "classes": len(cl["n_c"]), "rounds": rounds, "hist": cl["hist"]}
+
+
+def eff_lengths_model(lens, mean=MODEL_MEAN, sd=MODEL_SD):
+    """rule 2 of DESIGN.md 3.13 (single reads: no span is seen, the fragment-length model is fixed): g[s] = exp(-0.5 * (z * z)), z =
+    (s - mean) / sd, for s = 0..999; mu_l = (sum of s * g[s]) / (sum of g[s]) over s <= min(l, 999), both sums from 0.0 in ascending
+    s in double; eff_j = len_j - mu_{len_j} + 1, or len_j when that is < 1 (or the sum of g is 0)."""
+    mean, sd = float(mean), float(sd)
+    if not sd > 0.0:
+        raise ValueError("eff_lengths_model: sd %r is not above 0" % sd)
+    cnt, tot = [0.0] * (MODEL_BINS + 1), [0.0] * (MODEL_BINS + 1)        # prefix sums: s < k
+    for s in range(MODEL_BINS):
+        z = (float(s) - mean) / sd
+        g = math.exp(-0.5 * (z * z))
+        cnt[s + 1] = cnt[s] + g
+        tot[s + 1] = tot[s] + float(s) * g
+    out = []
+    for n in lens:
+        n = int(n)
+        k = min(n, MODEL_BINS - 1) + 1
+        eff = float(n)
+        if k > 0 and cnt[k] > 0.0:
+            e = float(n) - tot[k] / cnt[k] + 1.0
+            if e >= 1.0:
+                eff = e
+        out.append(eff)
+    return np.array(out, dtype=np.float64)
+
+
+def quantify_single(ctx, names, seqs, d, strand_specific, mean=MODEL_MEAN, sd=MODEL_SD):
+    """`quantify` for the single reads of the resident set d: classes_single, eff_lengths_model, em, tpm -- the same
+    table, "fragments" the reads, "hist" empty"""
+    if len(names) != len(seqs):
+        raise ValueError("quantify_single: %d names for %d sequences" % (len(names), len(seqs)))
+    lens = [len(s) for s in seqs]
+    if not seqs:
+        return {"names": [], "length": [], "eff_length": [], "est_counts": [], "tpm": [], "mapped": 0, "fragments": len(d), "classes": 0,
+                "rounds": 0, "hist": np.zeros(0, np.uint64)}
+    eff = eff_lengths_model(lens, mean, sd)
+    cl = classes_single(ctx, seqs, d, strand_specific)
     alpha, rounds = em(ctx, cl["class_off"], cl["members"], cl["n_c"], eff)
     return {"names": list(names), "length": lens, "eff_length": eff.tolist(), "est_counts": alpha.tolist(), "tpm": tpm_of(alpha, eff),
             "mapped": cl["mapped"], "fragments": cl["fragments"], "classes": len(cl["n_c"]), "rounds": rounds, "hist": cl["hist"]}

@@ -1,7 +1,8 @@
 // --kallisto_cutoff on the device: how many read pairs every final transcript explains (shannon.py:309-318, 609-614,
 // filter_kallisto.py:23-31 -- `kallisto index` + `kallisto quant`).  kallisto is replaced by the rule of DESIGN.md 3.10 ("abundance");
 // the kernels below state the part of it they implement.  The placement of a pair is --filter_FP's (filter_fp_dev.h: the same
-// index, the same enumeration), all transcripts forming one partition.
+// index, the same enumeration), all transcripts forming one partition.  Single reads (python -m shannon_amd.quant --single, DESIGN.md
+// 3.13) go the same way with a map stage of their own: no mate, no span, no histogram.
 //
 //   map      one thread per fragment, three passes over the same enumeration: the minimum cost; the number of placements that attain
 //            it (and the span of the only one: the fragment-length histogram, integer atomics in LDS, then one global add per
@@ -96,6 +97,33 @@ __device__ __forceinline__ void abd_sift_down(uint32_t* L, uint64_t p, uint64_t 
   L[p] = v;
 }
 
+// The n >= 1 ids of a fragment's placements as they were enumerated -> sorted, repeats dropped: *nuniq of them stay at the front,
+// *key = 63 bits of their hash: the tail of abd_fill_kernel, for abd_fill_single_kernel.  (abd_fill_kernel keeps its own lines:
+// calling this from it compiles to 90 VGPRs instead of its 88.)
+__device__ __forceinline__ void abd_finish_list(uint32_t* L, uint64_t n, uint32_t* nuniq, uint64_t* key) {
+  if (n <= ABD_INSERTION) {
+    for (uint64_t p = 1; p < n; p++) {
+      const uint32_t v = L[p];
+      uint64_t q = p;
+      while (q > 0 && L[q - 1] > v) { L[q] = L[q - 1]; q--; }
+      L[q] = v;
+    }
+  } else {
+    for (uint64_t p = n / 2; p-- > 0;) abd_sift_down(L, p, n);
+    for (uint64_t e = n - 1; e > 0; e--) {
+      const uint32_t v = L[0]; L[0] = L[e]; L[e] = v;
+      abd_sift_down(L, 0, e);
+    }
+  }
+  uint64_t u = 1;
+  for (uint64_t p = 1; p < n; p++)
+    if (L[p] != L[u - 1]) L[u++] = L[p];
+  uint64_t h = abd_mix(0, u);
+  for (uint64_t p = 0; p < u; p++) h = abd_mix(h, L[p]);
+  *nuniq = (uint32_t)u;
+  *key = h >> 1;
+}
+
 // pass 3: the transcript ids of fragment i's placements into ids[off[i] .. off[i + 1]), sorted, repeats dropped: nuniq[i] of them
 // stay at the front.  key[i] = 63 bits of the list's hash; an unmapped fragment: all ones.
 __global__ __launch_bounds__(FFP_BLOCK) void abd_fill_kernel(FfpIndex I, FfpSet A, FfpSet B, uint64_t n_pairs, int ss, uint32_t max_span,
@@ -134,6 +162,51 @@ __global__ __launch_bounds__(FFP_BLOCK) void abd_fill_kernel(FfpIndex I, FfpSet 
   for (uint64_t p = 0; p < u; p++) h = abd_mix(h, L[p]);
   nuniq[i] = (uint32_t)u;
   key[i] = h >> 1;
+}
+
+// ---- single reads (DESIGN.md 3.13 rule 1): read i as itself and, unless strand-specific, as its reverse complement
+// f(j) for every placement of read i whose cost is `best`
+template <class F>
+__device__ __forceinline__ void abd_each_best_single(const FfpIndex& I, const FfpSet& A, uint64_t i, int ss, uint32_t best, F&& f) {
+  ffp_each_single<true>(I, 0, ffp_read(A, i, false), &best, [&](uint32_t c, uint64_t j, uint64_t) { if (c == best) f(j); });
+  if (!ss) ffp_each_single<true>(I, 0, ffp_read(A, i, true), &best, [&](uint32_t c, uint64_t j, uint64_t) { if (c == best) f(j); });
+}
+
+// pass 1 + 2: best[i] = the read's minimum cost over its orientations (FFP_NONE: unmapped), cnt[i] = placements of that cost
+__global__ __launch_bounds__(FFP_BLOCK) void abd_count_single_kernel(FfpIndex I, FfpSet A, uint64_t n_reads, int ss, uint32_t* __restrict__ best_out,
+                                                                     uint32_t* __restrict__ cnt, unsigned long long* __restrict__ n_mapped,
+                                                                     uint32_t* __restrict__ too_many) {
+  const uint64_t i = (uint64_t)blockIdx.x * FFP_BLOCK + threadIdx.x;
+  bool placed = false;
+  if (i < n_reads) {
+    uint32_t best = FFP_NONE;
+    auto lower = [&](uint32_t c, uint64_t, uint64_t) { if (c < best) best = c; };
+    ffp_each_single<false>(I, 0, ffp_read(A, i, false), &best, lower);
+    if (!ss) ffp_each_single<false>(I, 0, ffp_read(A, i, true), &best, lower);
+    uint64_t n = 0;
+    if (best != FFP_NONE) abd_each_best_single(I, A, i, ss, best, [&](uint64_t) { n++; });
+    if (n > 0xFFFFFFFEULL) { atomicOr(too_many, 1u); n = 0; }
+    placed = n != 0;
+    best_out[i] = placed ? best : FFP_NONE;
+    cnt[i] = (uint32_t)n;
+  }
+  const unsigned long long vote = __ballot(placed);
+  if ((threadIdx.x & 63) == 0 && vote) atomicAdd(n_mapped, (unsigned long long)__popcll(vote));
+}
+
+// pass 3, as abd_fill_kernel: the ids of read i's placements into ids[off[i] .. off[i + 1]), sorted, repeats dropped, hashed
+__global__ __launch_bounds__(FFP_BLOCK) void abd_fill_single_kernel(FfpIndex I, FfpSet A, uint64_t n_reads, int ss, const uint32_t* __restrict__ best_in,
+                                                                    const uint64_t* __restrict__ off, uint32_t* __restrict__ ids,
+                                                                    uint32_t* __restrict__ nuniq, uint64_t* __restrict__ key, uint32_t* __restrict__ frag) {
+  const uint64_t i = (uint64_t)blockIdx.x * FFP_BLOCK + threadIdx.x;
+  if (i >= n_reads) return;
+  frag[i] = (uint32_t)i;
+  const uint64_t o = off[i], n = off[i + 1] - o;
+  if (n == 0) { nuniq[i] = 0; key[i] = ~0ULL; return; }
+  uint32_t* L = ids + o;
+  uint64_t k = 0;
+  abd_each_best_single(I, A, i, ss, best_in[i], [&](uint64_t j) { if (k < n) L[k] = (uint32_t)j; k++; });
+  abd_finish_list(L, n, &nuniq[i], &key[i]);
 }
 
 // sorted position r heads a class iff its fragment's list is not its predecessor's
@@ -177,6 +250,62 @@ __global__ void abd_members_kernel(uint64_t n_classes, const uint64_t* __restric
   const uint64_t o = class_off[c], n = class_off[c + 1] - o;
   for (uint64_t p = 0; p < n; p++) members[o + p] = src[p];
   n_c[c] = first[c + 1] - first[c];
+}
+
+// ---- classes: the fragments (pairs or single reads) whose lists the map stage left -- ids[off[i] .. off[i] + nuniq[i]) sorted, key[i]
+// their hash, frag[i] = i, `mapped` of the n_frag with a list -- sorted by hash, cut where the LIST changes, written into R
+static int abd_emit_classes(shn_ctx* ctx, ShnDevBufs& bufs, uint64_t n_frag, uint64_t mapped, uint64_t n_place, const uint64_t* d_off, const uint32_t* d_ids,
+                            const uint32_t* d_nuniq, uint64_t* d_key, uint64_t* d_key_tmp, uint32_t* d_frag, uint32_t* d_frag_tmp, shn_abundance* R) {
+  hipStream_t s = ctx->stream;
+  uint32_t *d_head = nullptr, *d_size = nullptr, *d_members = nullptr;
+  uint64_t *d_head_scan = nullptr, *d_first = nullptr, *d_class_off = nullptr, *d_nc = nullptr;
+  uint64_t n_classes = 0, n_entries = 0;
+  HIP_TRY(bufs.get(&d_head, mapped * 4));
+  HIP_TRY(bufs.get(&d_head_scan, (mapped + 1) * 8));
+  {
+    TimerRegion treg(ctx, T_ABD_CLASSES);
+    // bytes: 8 sort passes over (key, fragment) pairs (24 B a pair and pass), then per mapped fragment its list and its predecessor's
+    // (8 B a member at the most: n_place bounds both), ids, counts, offsets (32 B) and the flag (4 B)
+    treg.bytes(8 * n_frag * 24 + mapped * 36 + n_place * 8);
+    int rc = shn_sort_pairs(ctx, d_key, d_frag, d_key_tmp, d_frag_tmp, n_frag, 0, 64);
+    if (rc) return rc;
+    hipLaunchKernelGGL(abd_heads_kernel, dim3((uint32_t)cdiv(mapped, 256)), dim3(256), 0, s, mapped, d_frag, d_off, d_nuniq, d_ids, d_head);
+    // the scan of the head flags: a flag read, a number written (12 B a mapped fragment)
+    treg.bytes(mapped * 12);
+    rc = shn_device_scan_u32(ctx, d_head, mapped, d_head_scan, &n_classes);
+    if (rc) return rc;
+  }
+  HIP_TRY(bufs.get(&d_first, (n_classes + 1) * 8));
+  HIP_TRY(bufs.get(&d_size, n_classes * 4));
+  HIP_TRY(bufs.get(&d_class_off, (n_classes + 1) * 8));
+  HIP_TRY(bufs.get(&d_nc, n_classes * 8));
+  {
+    TimerRegion treg(ctx, T_ABD_CLASSES);
+    // bytes: a mapped fragment's flag (4 B); a head's number and fragment read, its count read, first and size written (28 B a
+    // class); the scan of the sizes (12 B a class)
+    treg.bytes(mapped * 4 + n_classes * 40);
+    hipLaunchKernelGGL(abd_first_kernel, dim3((uint32_t)cdiv(mapped, 256)), dim3(256), 0, s, mapped, n_classes, d_head, d_head_scan, d_frag, d_nuniq,
+                       d_first, d_size);
+    int rc = shn_device_scan_u32(ctx, d_size, n_classes, d_class_off, &n_entries);
+    if (rc) return rc;
+  }
+  HIP_TRY(bufs.get(&d_members, (n_entries + 1) * 4));
+  {
+    TimerRegion treg(ctx, T_ABD_CLASSES);
+    // bytes: per class head, fragment, three offsets read, its count written (52 B); a member read and written (8 B)
+    treg.bytes(mapped * 16 + n_classes * 52 + n_entries * 8);
+    hipLaunchKernelGGL(abd_members_kernel, dim3((uint32_t)cdiv(n_classes, 256)), dim3(256), 0, s, n_classes, d_first, d_frag, d_off, d_ids, d_class_off,
+                       d_members, d_nc);
+  }
+  R->class_off.resize(n_classes + 1);
+  R->n_c.resize(n_classes);
+  R->members.resize(n_entries);
+  HIP_TRY(hipMemcpyAsync(R->class_off.data(), d_class_off, (n_classes + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(R->n_c.data(), d_nc, n_classes * 8, hipMemcpyDeviceToHost, s));
+  if (n_entries) HIP_TRY(hipMemcpyAsync(R->members.data(), d_members, n_entries * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipGetLastError());
+  return SHN_OK;
 }
 
 // Classes of the read pairs of two resident sets on the final transcripts (kallisto's pseudoalignment, `kallisto quant`,
@@ -275,56 +404,98 @@ extern "C" int shn_abundance_classes(shn_ctx* ctx, const uint8_t* text, const ui
     hipLaunchKernelGGL(abd_fill_kernel, dim3(grid), dim3(FFP_BLOCK), 0, s, I, A, B, n_pairs, strand_specific ? 1 : 0, max_span, d_best, d_off, d_ids,
                        d_nuniq, d_key, d_frag);
   }
-
   // ---- classes
-  uint32_t *d_head = nullptr, *d_size = nullptr, *d_members = nullptr;
-  uint64_t *d_head_scan = nullptr, *d_first = nullptr, *d_class_off = nullptr, *d_nc = nullptr;
-  uint64_t n_classes = 0, n_entries = 0;
-  HIP_TRY(bufs.get(&d_head, mapped * 4));
-  HIP_TRY(bufs.get(&d_head_scan, (mapped + 1) * 8));
+  if (int rc = abd_emit_classes(ctx, bufs, n_pairs, mapped, n_place, d_off, d_ids, d_nuniq, d_key, d_key_tmp, d_frag, d_frag_tmp, R)) return rc;
+  return done();
+}
+
+// Classes of the single reads of one resident set on the transcripts (`kallisto quant --single`, filter_kallisto.py:25, replaced by
+// DESIGN.md 3.13 rule 1 and 3.10 rule 3).  No span, so no histogram: the handle reports 0 bins.
+extern "C" int shn_abundance_classes_single(shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off, uint64_t n_tr, const shn_reads* r, int strand_specific,
+                                            shn_abundance** out) {
+  const std::string fn("shn_abundance_classes_single");
+  if (!ctx || !r || !t_off || !out || (n_tr && !text)) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
+  if (n_tr >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many transcripts");
+  const uint64_t n_reads = r->n_reads;
+  if (n_reads >= 0xFFFFFFFEULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many reads in one call");
+  std::vector<uint64_t> rec_off;
+  if (int rc = ffp_record_offsets(fn, t_off, n_tr, &rec_off)) return rc;
+  const uint64_t total = t_off[n_tr], n_rec = rec_off[n_tr];
+  if (total >= 0xFFFFFF00ULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": more than 2^32 transcript bases in one call");
+  shn_abundance* R = new shn_abundance();
+  R->n_tr = n_tr; R->n_frag = n_reads;
+  R->class_off.assign(1, 0);
+  struct Guard { shn_abundance* p; ~Guard() { delete p; } } guard{R};
+  auto done = [&]() { *out = R; guard.p = nullptr; return SHN_OK; };
+  if (n_rec == 0 || n_reads == 0) return done();
+  SHN_ENTER(ctx);
+  shn_stage_begin(ctx);
+  hipStream_t s = ctx->stream;
+  ShnDevBufs bufs(s);
+
+  // ---- index (all transcripts in partition 0)
+  FfpIndex I;
+  uint64_t n_tw = 0;
   {
-    TimerRegion treg(ctx, T_ABD_CLASSES);
-    // bytes: 8 sort passes over (key, fragment) pairs (24 B a pair and pass), then per mapped fragment its list and its predecessor's
-    // (8 B a member at the most: n_place bounds both), ids, counts, offsets (32 B) and the flag (4 B)
-    treg.bytes(8 * n_pairs * 24 + mapped * 36 + n_place * 8);
-    int rc = shn_sort_pairs(ctx, d_key, d_frag, d_key_tmp, d_frag_tmp, n_pairs, 0, 64);
-    if (rc) return rc;
-    hipLaunchKernelGGL(abd_heads_kernel, dim3((uint32_t)cdiv(mapped, 256)), dim3(256), 0, s, mapped, d_frag, d_off, d_nuniq, d_ids, d_head);
-    // the scan of the head flags: a flag read, a number written (12 B a mapped fragment)
-    treg.bytes(mapped * 12);
-    rc = shn_device_scan_u32(ctx, d_head, mapped, d_head_scan, &n_classes);
+    std::vector<uint32_t> t_part(n_tr, 0);
+    int rc = ffp_index_build(fn, ctx, bufs, T_ABD_INDEX, text, t_off, t_part.data(), n_tr, 1, rec_off, &I, &n_tw);
     if (rc) return rc;
   }
-  HIP_TRY(bufs.get(&d_first, (n_classes + 1) * 8));
-  HIP_TRY(bufs.get(&d_size, n_classes * 4));
-  HIP_TRY(bufs.get(&d_class_off, (n_classes + 1) * 8));
-  HIP_TRY(bufs.get(&d_nc, n_classes * 8));
+
+  // ---- map: minimum cost + placements per read, scan, lists
+  uint32_t *d_best = nullptr, *d_cnt = nullptr, *d_flag = nullptr, *d_ids = nullptr, *d_nuniq = nullptr, *d_frag = nullptr, *d_frag_tmp = nullptr;
+  uint64_t *d_off = nullptr, *d_key = nullptr, *d_key_tmp = nullptr;
+  unsigned long long* d_mapped = nullptr;
+  HIP_TRY(bufs.get(&d_best, n_reads * 4));
+  HIP_TRY(bufs.get(&d_cnt, n_reads * 4));
+  HIP_TRY(bufs.get(&d_flag, 4));
+  HIP_TRY(bufs.get(&d_off, (n_reads + 1) * 8));
+  HIP_TRY(bufs.get(&d_mapped, 8));
+  HIP_TRY(hipMemsetAsync(d_flag, 0, 4, s));
+  HIP_TRY(hipMemsetAsync(d_mapped, 0, 8, s));
+  FfpSet A;
+  uint64_t rc_bytes = 0, n_place = 0;
+  const uint32_t grid = (uint32_t)cdiv(n_reads, FFP_BLOCK);
+  const uint64_t per_read = r->n_words * 8 / n_reads * (strand_specific ? 1 : 2);
   {
-    TimerRegion treg(ctx, T_ABD_CLASSES);
-    // bytes: a mapped fragment's flag (4 B); a head's number and fragment read, its count read, first and size written (28 B a
-    // class); the scan of the sizes (12 B a class)
-    treg.bytes(mapped * 4 + n_classes * 40);
-    hipLaunchKernelGGL(abd_first_kernel, dim3((uint32_t)cdiv(mapped, 256)), dim3(256), 0, s, mapped, n_classes, d_head, d_head_scan, d_frag, d_nuniq,
-                       d_first, d_size);
-    int rc = shn_device_scan_u32(ctx, d_size, n_classes, d_class_off, &n_entries);
+    TimerRegion treg(ctx, T_ABD_MAP);
+    int rc = ffp_set(ctx, bufs, r, !strand_specific, &A, &rc_bytes);
+    if (rc) return rc;
+    // bytes: every read in each orientation used (2 bits a base), minimum cost and count written (8 B); the index and the text are
+    // re-read from the caches and priced once; what the reverse complement cost is added above
+    treg.bytes(rc_bytes + n_reads * (per_read + 8) + n_rec * 12 + n_tw * 8);
+    hipLaunchKernelGGL(abd_count_single_kernel, dim3(grid), dim3(FFP_BLOCK), 0, s, I, A, n_reads, strand_specific ? 1 : 0, d_best, d_cnt, d_mapped, d_flag);
+    // the scan of the numbers: a count read, an offset written (12 B a read)
+    treg.bytes(n_reads * 12);
+    rc = shn_device_scan_u32(ctx, d_cnt, n_reads, d_off, &n_place);             // (synchronises)
     if (rc) return rc;
   }
-  HIP_TRY(bufs.get(&d_members, (n_entries + 1) * 4));
-  {
-    TimerRegion treg(ctx, T_ABD_CLASSES);
-    // bytes: per class head, fragment, three offsets read, its count written (52 B); a member read and written (8 B)
-    treg.bytes(mapped * 16 + n_classes * 52 + n_entries * 8);
-    hipLaunchKernelGGL(abd_members_kernel, dim3((uint32_t)cdiv(n_classes, 256)), dim3(256), 0, s, n_classes, d_first, d_frag, d_off, d_ids, d_class_off,
-                       d_members, d_nc);
-  }
-  R->class_off.resize(n_classes + 1);
-  R->n_c.resize(n_classes);
-  R->members.resize(n_entries);
-  HIP_TRY(hipMemcpyAsync(R->class_off.data(), d_class_off, (n_classes + 1) * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(R->n_c.data(), d_nc, n_classes * 8, hipMemcpyDeviceToHost, s));
-  if (n_entries) HIP_TRY(hipMemcpyAsync(R->members.data(), d_members, n_entries * 4, hipMemcpyDeviceToHost, s));
+  uint32_t flag = 0;
+  unsigned long long mapped = 0;
+  HIP_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&mapped, d_mapped, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipGetLastError());
+  if (flag) return shn_fail(SHN_ERR_OVERFLOW, fn + ": a read has 2^32 or more placements of its minimum cost");
+  if (n_place >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": " + std::to_string(n_place) + " placements in one call (2^32 - 1 at most)");
+  R->mapped = mapped;
+  if (mapped == 0) return done();
+  HIP_TRY(bufs.get(&d_ids, (n_place + 1) * 4));
+  HIP_TRY(bufs.get(&d_nuniq, n_reads * 4));
+  HIP_TRY(bufs.get(&d_key, (n_reads + 1) * 8));
+  HIP_TRY(bufs.get(&d_key_tmp, (n_reads + 1) * 8));
+  HIP_TRY(bufs.get(&d_frag, (n_reads + 1) * 4));
+  HIP_TRY(bufs.get(&d_frag_tmp, (n_reads + 1) * 4));
+  {
+    TimerRegion treg(ctx, T_ABD_MAP);
+    // bytes: the reads again, cost and two offsets read (20 B), the ids written, sorted in place and read for the hash (12 B a
+    // placement), count, key and read id written (16 B)
+    treg.bytes(n_reads * (per_read + 36) + n_place * 12 + n_rec * 12 + n_tw * 8);
+    hipLaunchKernelGGL(abd_fill_single_kernel, dim3(grid), dim3(FFP_BLOCK), 0, s, I, A, n_reads, strand_specific ? 1 : 0, d_best, d_off, d_ids, d_nuniq,
+                       d_key, d_frag);
+  }
+  // ---- classes
+  if (int rc = abd_emit_classes(ctx, bufs, n_reads, mapped, n_place, d_off, d_ids, d_nuniq, d_key, d_key_tmp, d_frag, d_frag_tmp, R)) return rc;
   return done();
 }
 
@@ -335,7 +506,7 @@ extern "C" int shn_abundance_sizes(const shn_abundance* a, uint64_t* sizes) {
 }
 
 extern "C" int shn_abundance_export(const shn_abundance* a, uint64_t* class_off, uint32_t* members, uint64_t* n_c, uint64_t* hist) {
-  if (!a || !class_off || !hist || (a->n_c.size() && !n_c) || (a->members.size() && !members))
+  if (!a || !class_off || (a->hist.size() && !hist) || (a->n_c.size() && !n_c) || (a->members.size() && !members))
     return shn_fail(SHN_ERR_ARG, "shn_abundance_export: NULL argument");
   std::copy(a->class_off.begin(), a->class_off.end(), class_off);
   std::copy(a->members.begin(), a->members.end(), members);

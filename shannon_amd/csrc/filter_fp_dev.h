@@ -151,6 +151,34 @@ __device__ __forceinline__ void ffp_min_cost(const FfpIndex& I, uint64_t pkey, c
   ffp_each_placement<false>(I, pkey, x, y, max_span, best, [&](uint32_t c, uint64_t, uint64_t, uint64_t) { if (c < *best) *best = c; });
 }
 
+// Every placement of the single read x in the partition whose key prefix is pkey (DESIGN.md 3.13 rule 1): x at u on transcript j,
+// u + |x| <= len_j, at most |x| / 30 mismatches.  The first |x| / 30 + 1 seeds find every one of them (they do not overlap and lie
+// inside the read: one of them is free of mismatches); a start is named by the first seed that matches there.  f(cost, j, u) is
+// called for each placement that does not cost more than *best (EXACT == false: not as much -- the pass that looks for the
+// minimum, f may lower *best as it goes).
+template <bool EXACT, class F>
+__device__ __forceinline__ void ffp_each_single(const FfpIndex& I, uint64_t pkey, const FfpRead& x, const uint32_t* best, F&& f) {
+  if (x.L < FFP_SEED) return;
+  const uint32_t thr = x.L / 30;
+  for (uint32_t s = 0; s <= thr; s++) {
+    uint64_t seed;
+    if (!ffp_seed_of(x, s, &seed)) continue;
+    const uint64_t key = pkey | seed;
+    for (uint64_t r = shn_lower_bound(I.keys, I.n_rec, key); r < I.n_rec && I.keys[r] == key; r++) {
+      const uint64_t g = I.vals[r];
+      const uint64_t j = shn_segment_of(I.t_off, I.n_tr, g);               // (an empty transcript holds no base)
+      const uint64_t a = I.t_off[j], b = I.t_off[j + 1];
+      if (g < a + (uint64_t)s * FFP_SEED) continue;
+      const uint64_t u = g - (uint64_t)s * FFP_SEED;
+      if (u + x.L > b || ffp_named_before(x, I.tw, u, s)) continue;
+      const uint32_t lim = *best < thr ? *best : thr;                       // (the count gives up above both bounds)
+      const uint32_t c = ffp_hamming(x, I.tw, u, lim);
+      if (c > lim || (!EXACT && c >= *best)) continue;
+      f(c, j, u - a);
+    }
+  }
+}
+
 // ---- host side (filter_fp.hip): what both callers prepare the same way
 // the device view of a resident read set; want_rc: its reverse complement written beside it (rc_bytes += what that read and wrote)
 int ffp_set(shn_ctx* ctx, ShnDevBufs& bufs, const shn_reads* r, bool want_rc, FfpSet* out, uint64_t* rc_bytes);

@@ -473,6 +473,25 @@ void shn_abundance_destroy(shn_abundance* a);
  *   alpha[m] (host, written), *rounds = rounds run */
 int shn_abundance_em(shn_ctx* ctx, const uint64_t* class_off, const uint32_t* members, const uint64_t* n_c, uint64_t n_classes, const double* eff,
                      uint64_t m, double* alpha, uint32_t* rounds);
+/* Bootstrap replicates of the abundances (python -m shannon_amd.quant -b B --seed S).
+ * shn_abundance_resample -- rule 1: replicate b makes N = sum n_c draws; draw t is Philox4x32-10 of the counter (t, b, 0, 0) under the
+ * key (seed & 0xFFFFFFFF, seed >> 32), u = o0 | o1 << 32, r = (u * N) >> 64, and lands in the class c with cum[c] <= r < cum[c + 1]
+ * (cum: the exclusive prefix sum of n_c).  Integer atomics only: the counts do not depend on the order of the adds.
+ *   n_c[n_classes] (host), counts_out[B][n_classes] (host, written; every row sums to N; all zeros for N == 0)
+ * Refused before anything is launched: B == 0 (SHN_ERR_ARG); N >= 2^32 or B >= 2^32 (SHN_ERR_OVERFLOW). */
+int shn_abundance_resample(shn_ctx* ctx, const uint64_t* n_c, uint64_t n_classes, uint64_t B, uint64_t seed, uint64_t* counts_out);
+/* shn_abundance_em_batch -- shn_abundance_em for the B count vectors n_c[B][n_classes] over the same classes and eff: alpha_out[b][] and
+ * rounds_out[b] are bit for bit what shn_abundance_em returns for row b.  The transposition is built once; a round is two launches over
+ * (row x live replicate); after every 50 rounds the replicates that are done leave the launches.  max_live caps the replicates
+ * resident at once (0: as many as 1 GiB of alpha, w, d and counts hold, 32,768 at the most); the chunking changes no bit.  The
+ * refusals of shn_abundance_em, and B == 0.
+ *   alpha_out[B][m], rounds_out[B] (host, written) */
+int shn_abundance_em_batch(shn_ctx* ctx, const uint64_t* class_off, const uint32_t* members, const uint64_t* n_c, uint64_t n_classes, const double* eff,
+                           uint64_t m, uint64_t B, uint64_t max_live, double* alpha_out, uint32_t* rounds_out);
+/* shn_abundance_bootstrap -- resample, then the batched EM, the counts staying on the device; n_c[n_classes] are the classes' own
+ * counts; counts_out[B][n_classes] may be NULL.  The refusals of both calls above. */
+int shn_abundance_bootstrap(shn_ctx* ctx, const uint64_t* class_off, const uint32_t* members, const uint64_t* n_c, uint64_t n_classes, const double* eff,
+                            uint64_t m, uint64_t B, uint64_t seed, uint64_t max_live, double* alpha_out, uint32_t* rounds_out, uint64_t* counts_out);
 
 /* ---- K-mer seed scans of reads against graph nodes -----------------------------------------------
  * Replace the per-read Python loops of Read.find_bridging_reads (mbgraph.py:88-111) and known_paths

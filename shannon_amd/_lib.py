@@ -80,6 +80,9 @@ SIGNATURES = {
     "shn_abundance_export": (C.c_int, [vp, vp, vp, vp, vp]),
     "shn_abundance_destroy": (None, [vp]),
     "shn_abundance_em": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp]),
+    "shn_abundance_resample": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp]),
+    "shn_abundance_em_batch": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp]),
+    "shn_abundance_bootstrap": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, vp]),
     "shn_lp_solve_batch": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]),
     "shn_lp_set_rule": (C.c_int, [vp, C.c_int]),
     "shn_lp_stats": (C.c_int, [vp, vp, C.c_int]),

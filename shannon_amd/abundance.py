@@ -19,7 +19,16 @@ Single reads (the command is shannon_amd/quant.py):
     eff_lengths_model  effective lengths from the fixed fragment-length model (mean, sd), in double
     quantify_single    names + sequences + one resident read set -> table
 
-`eff_lengths`, `eff_lengths_model`, `abundance_tsv` and `decide` need neither the library nor a GPU.
+Bootstrap replicates (quant.py's -b B --seed S; quantify / quantify_single with bootstraps=B):
+
+    resample           B resampled count vectors of the classes (shn_abundance_resample)
+    em_batch           the EM on a matrix of count vectors at once, every row bit for bit `em`'s (shn_abundance_em_batch)
+    bootstrap          both, the counts staying on the device (shn_abundance_bootstrap)
+    bootstrap_summary  mean, sd, min, max per transcript over the replicates' est_counts
+    bootstrap_summary_tsv, replicate_table  the texts of bootstrap_summary.tsv and, through abundance_tsv, of bs_abundance_<b>.tsv
+
+`eff_lengths`, `eff_lengths_model`, `abundance_tsv`, `decide`, `bootstrap_summary`, `bootstrap_summary_tsv` and `replicate_table` need
+neither the library nor a GPU.
 """
 import ctypes as C
 import io
@@ -125,6 +134,134 @@ def em(ctx, class_off, members, n_c, eff):
     return alpha[:m], int(rounds.value)
 
 
+def _em_arrays(who, class_off, members, eff, n_count_cols):
+    """the classes and eff as the library takes them, with em's own checks"""
+    class_off = np.ascontiguousarray(class_off, dtype=np.uint64)
+    members = np.ascontiguousarray(members, dtype=np.uint32)
+    eff = np.ascontiguousarray(eff, dtype=np.float64)
+    n_classes = len(class_off) - 1
+    if n_classes < 0 or n_count_cols != n_classes:
+        raise ValueError("abundance.%s: class_off has %d entries for %d class counts" % (who, len(class_off), n_count_cols))
+    if n_classes and int(class_off[-1]) > len(members):
+        raise ValueError("abundance.%s: class_off ends at %d, %d members given" % (who, int(class_off[-1]), len(members)))
+    return class_off, members, eff, n_classes
+
+
+def _replicates(who, B):
+    B = int(B)
+    if not 1 <= B < 1 << 32:
+        raise ValueError("abundance.%s: %d replicates (1 .. 2^32 - 1)" % (who, B))
+    return B
+
+
+def _seed(who, seed):
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("abundance.%s: seed %d outside 0 .. 2^64 - 1" % (who, seed))
+    return seed
+
+
+def resample(ctx, n_c, B, seed):
+    """rule 1 of DESIGN.md 3.14 (shn_abundance_resample): uint64[B][classes], row b the class counts of bootstrap replicate b"""
+    from . import _lib
+    n_c = np.ascontiguousarray(n_c, dtype=np.uint64)
+    B, seed = _replicates("resample", B), _seed("resample", seed)
+    out = np.zeros((B, len(n_c)), dtype=np.uint64)
+    _lib.check(_lib.lib().shn_abundance_resample(ctx.h, n_c.ctypes.data if len(n_c) else None, len(n_c), B, seed, out.ctypes.data if len(n_c) else None))
+    return out
+
+
+def em_batch(ctx, class_off, members, n_c_matrix, eff, max_live=0):
+    """rule 4 for every row of n_c_matrix[B][classes] at once (shn_abundance_em_batch) -> (alpha float64[B][m], rounds uint32[B]), row b
+    bit for bit em's answer on n_c_matrix[b]; max_live caps the replicates resident at once (0: the library's budget)"""
+    from . import _lib
+    n_c_matrix = np.ascontiguousarray(n_c_matrix, dtype=np.uint64)
+    if n_c_matrix.ndim != 2:
+        raise ValueError("abundance.em_batch: the counts are no matrix [replicates][classes]")
+    class_off, members, eff, n_classes = _em_arrays("em_batch", class_off, members, eff, n_c_matrix.shape[1])
+    B, m = _replicates("em_batch", n_c_matrix.shape[0]), len(eff)
+    alpha = np.zeros((B, max(m, 1)), dtype=np.float64)
+    rounds = np.zeros(B, dtype=np.uint32)
+    _lib.check(_lib.lib().shn_abundance_em_batch(ctx.h, class_off.ctypes.data, members.ctypes.data if len(members) else None,
+                                                 n_c_matrix.ctypes.data if n_classes else None, n_classes, eff.ctypes.data if m else None, m, B,
+                                                 int(max_live), alpha.ctypes.data, rounds.ctypes.data))
+    return alpha[:, :m], rounds
+
+
+def bootstrap(ctx, class_off, members, n_c, eff, B, seed, max_live=0, want_counts=False):
+    """resample, then em_batch, the counts staying on the device (shn_abundance_bootstrap) -> (alpha float64[B][m], rounds uint32[B],
+    counts uint64[B][classes] or None)"""
+    from . import _lib
+    n_c = np.ascontiguousarray(n_c, dtype=np.uint64)
+    class_off, members, eff, n_classes = _em_arrays("bootstrap", class_off, members, eff, len(n_c))
+    B, seed, m = _replicates("bootstrap", B), _seed("bootstrap", seed), len(eff)
+    alpha = np.zeros((B, max(m, 1)), dtype=np.float64)
+    rounds = np.zeros(B, dtype=np.uint32)
+    counts = np.zeros((B, n_classes), dtype=np.uint64) if want_counts else None
+    _lib.check(_lib.lib().shn_abundance_bootstrap(ctx.h, class_off.ctypes.data, members.ctypes.data if len(members) else None,
+                                                  n_c.ctypes.data if n_classes else None, n_classes, eff.ctypes.data if m else None, m, B, seed,
+                                                  int(max_live), alpha.ctypes.data, rounds.ctypes.data,
+                                                  counts.ctypes.data if want_counts and n_classes else None))
+    return alpha[:, :m], rounds, counts
+
+
+def bootstrap_summary(est_counts_matrix):
+    """rule 3 of DESIGN.md 3.14 on est_counts[B][m], per transcript over x_b = est_counts[b][j]: {"bs_mean": (x_0 + x_1 + ... in that
+    order) / B, "bs_sd": sqrt(sum of (x_b - bs_mean)^2, in order, / (B - 1)), 0.0 for B = 1, "bs_min", "bs_max"} (lists); host only"""
+    rows = [[float(x) for x in row] for row in est_counts_matrix]
+    B = len(rows)
+    if B < 1:
+        raise ValueError("abundance.bootstrap_summary: no replicates")
+    out = {"bs_mean": [], "bs_sd": [], "bs_min": [], "bs_max": []}
+    for j in range(len(rows[0])):
+        xs = [row[j] for row in rows]
+        total = 0.0
+        for x in xs:
+            total += x
+        mean = total / B
+        ss = 0.0
+        for x in xs:
+            ss += (x - mean) * (x - mean)
+        out["bs_mean"].append(mean)
+        out["bs_sd"].append(math.sqrt(ss / (B - 1)) if B > 1 else 0.0)
+        out["bs_min"].append(min(xs))
+        out["bs_max"].append(max(xs))
+    return out
+
+
+def _no_targets(bootstraps, seed):
+    """the bootstrap columns of a table without transcripts"""
+    if bootstraps is None:
+        return {}
+    return {"bs_est_counts": [[] for _ in range(bootstraps)], "bs_tpm": [[] for _ in range(bootstraps)], "bs_rounds": [0] * bootstraps, "bs_mean": [],
+            "bs_sd": [], "bs_min": [], "bs_max": [], "bootstraps": bootstraps, "seed": seed}
+
+
+def _add_bootstraps(ctx, table, cl, eff, bootstraps, seed):
+    """the bootstrap columns of quantify / quantify_single: "bs_est_counts" and "bs_tpm" (B lists), "bs_rounds", the summary"""
+    alpha, rounds, _ = bootstrap(ctx, cl["class_off"], cl["members"], cl["n_c"], eff, bootstraps, seed)
+    table["bs_est_counts"] = [a.tolist() for a in alpha]
+    table["bs_tpm"] = [tpm_of(a, eff) for a in alpha]
+    table["bs_rounds"] = [int(r) for r in rounds]
+    table.update(bootstrap_summary(table["bs_est_counts"]))
+    table["bootstraps"], table["seed"] = len(table["bs_rounds"]), int(seed)
+    return table
+
+
+def bootstrap_summary_tsv(table):
+    """the text of bootstrap_summary.tsv: target_id est_counts bs_mean bs_sd bs_min bs_max, the floats written with repr"""
+    out = ["target_id\test_counts\tbs_mean\tbs_sd\tbs_min\tbs_max\n"]
+    for row in zip(table["names"], table["est_counts"], table["bs_mean"], table["bs_sd"], table["bs_min"], table["bs_max"]):
+        out.append("%s\t%s\n" % (row[0], "\t".join(repr(float(x)) for x in row[1:])))
+    return "".join(out)
+
+
+def replicate_table(table, b):
+    """replicate b of a table with bootstraps as a table of its own (for abundance_tsv: bs_abundance_<b>.tsv)"""
+    return {"names": table["names"], "length": table["length"], "eff_length": table["eff_length"], "est_counts": table["bs_est_counts"][b],
+            "tpm": table["bs_tpm"][b]}
+
+
 def tpm_of(alpha, eff):
     """tpm_j = 1e6 (alpha_j / eff_j) / sum_k (alpha_k / eff_k), the sum in index order; all zeros when nothing is mapped"""
     rho = [float(a) / float(e) for a, e in zip(alpha, eff)]
@@ -134,21 +271,25 @@ def tpm_of(alpha, eff):
     return [1e6 * r / total if total > 0.0 else 0.0 for r in rho]
 
 
-def quantify(ctx, names, seqs, d1, d2, strand_specific, max_span=MAX_SPAN):
+def quantify(ctx, names, seqs, d1, d2, strand_specific, max_span=MAX_SPAN, bootstraps=None, seed=0):
     """the abundance table of the transcripts (names[j], seqs[j]) under the pairs of the resident sets d1 / d2 (device.Reads, the mates
     as the user gave them): {"names", "length", "eff_length", "est_counts", "tpm"} (lists, in the order given) + "mapped",
-    "fragments", "classes", "rounds", "hist"."""
+    "fragments", "classes", "rounds", "hist".  bootstraps=B adds B replicates under `seed`: "bs_est_counts" and "bs_tpm" (B
+    lists), "bs_rounds", "bs_mean", "bs_sd", "bs_min", "bs_max"; None: nothing of that runs."""
     if len(names) != len(seqs):
         raise ValueError("quantify: %d names for %d sequences" % (len(names), len(seqs)))
+    if bootstraps is not None:
+        bootstraps, seed = _replicates("quantify", bootstraps), _seed("quantify", seed)
     lens = [len(s) for s in seqs]
     if not seqs:
         return {"names": [], "length": [], "eff_length": [], "est_counts": [], "tpm": [], "mapped": 0, "fragments": len(d1), "classes": 0,
-                "rounds": 0, "hist": np.zeros(max_span + 1, np.uint64)}
+                "rounds": 0, "hist": np.zeros(max_span + 1, np.uint64), **_no_targets(bootstraps, seed)}
     cl = classes(ctx, seqs, d1, d2, strand_specific, max_span)
     eff = eff_lengths(lens, cl["hist"])
     alpha, rounds = em(ctx, cl["class_off"], cl["members"], cl["n_c"], eff)
-    return {"names": list(names), "length": lens, "eff_length": eff.tolist(), "est_counts": alpha.tolist(), "tpm": tpm_of(alpha, eff),
-            "mapped": cl["mapped"], "fragments": cl["fragments"], "classes": len(cl["n_c"]), "rounds": rounds, "hist": cl["hist"]}
+    table = {"names": list(names), "length": lens, "eff_length": eff.tolist(), "est_counts": alpha.tolist(), "tpm": tpm_of(alpha, eff),
+             "mapped": cl["mapped"], "fragments": cl["fragments"], "classes": len(cl["n_c"]), "rounds": rounds, "hist": cl["hist"]}
+    return table if bootstraps is None else _add_bootstraps(ctx, table, cl, eff, bootstraps, seed)
 
 
 def eff_lengths_model(lens, mean=MODEL_MEAN, sd=MODEL_SD):
@@ -177,20 +318,23 @@ def eff_lengths_model(lens, mean=MODEL_MEAN, sd=MODEL_SD):
     return np.array(out, dtype=np.float64)
 
 
-def quantify_single(ctx, names, seqs, d, strand_specific, mean=MODEL_MEAN, sd=MODEL_SD):
+def quantify_single(ctx, names, seqs, d, strand_specific, mean=MODEL_MEAN, sd=MODEL_SD, bootstraps=None, seed=0):
     """`quantify` for the single reads of the resident set d: classes_single, eff_lengths_model, em, tpm -- the same
-    table, "fragments" the reads, "hist" empty"""
+    table, "fragments" the reads, "hist" empty; bootstraps / seed as there"""
     if len(names) != len(seqs):
         raise ValueError("quantify_single: %d names for %d sequences" % (len(names), len(seqs)))
+    if bootstraps is not None:
+        bootstraps, seed = _replicates("quantify_single", bootstraps), _seed("quantify_single", seed)
     lens = [len(s) for s in seqs]
     if not seqs:
         return {"names": [], "length": [], "eff_length": [], "est_counts": [], "tpm": [], "mapped": 0, "fragments": len(d), "classes": 0,
-                "rounds": 0, "hist": np.zeros(0, np.uint64)}
+                "rounds": 0, "hist": np.zeros(0, np.uint64), **_no_targets(bootstraps, seed)}
     eff = eff_lengths_model(lens, mean, sd)
     cl = classes_single(ctx, seqs, d, strand_specific)
     alpha, rounds = em(ctx, cl["class_off"], cl["members"], cl["n_c"], eff)
-    return {"names": list(names), "length": lens, "eff_length": eff.tolist(), "est_counts": alpha.tolist(), "tpm": tpm_of(alpha, eff),
-            "mapped": cl["mapped"], "fragments": cl["fragments"], "classes": len(cl["n_c"]), "rounds": rounds, "hist": cl["hist"]}
+    table = {"names": list(names), "length": lens, "eff_length": eff.tolist(), "est_counts": alpha.tolist(), "tpm": tpm_of(alpha, eff),
+             "mapped": cl["mapped"], "fragments": cl["fragments"], "classes": len(cl["n_c"]), "rounds": rounds, "hist": cl["hist"]}
+    return table if bootstraps is None else _add_bootstraps(ctx, table, cl, eff, bootstraps, seed)
 
 
 def abundance_tsv(table):

@@ -681,3 +681,372 @@ extern "C" int shn_abundance_em(shn_ctx* ctx, const uint64_t* class_off, const u
   *rounds = round;
   return SHN_OK;
 }
+
+// ----------------------------------------------------------------------------------------------------------------- bootstrap
+// quant -b B --seed S: B resampled count vectors of the classes, and the EM above on all of them at once.
+//
+//   resample  replicate b makes N = sum n_c draws; draw t = Philox4x32-10 of counter (t, b, 0, 0) under the key (seed lo, seed hi), u = o0 |
+//             o1 << 32, r = the high word of u * N, the class c with cum[c] <= r < cum[c + 1] (shn_segment_of on the exclusive prefix sum:
+//             an empty class shares its offset with the next one, which wins -- it is never drawn).  A block takes ABD_RS_DRAWS
+//             consecutive draws of one replicate.  Up to ABD_RS_LDS classes it counts them in LDS (32-bit integer atomics) and adds
+//             its non-empty bins to counts[b][] (64-bit integer atomics); above that a wave combines its equal destinations (one lane
+//             per distinct class adds the number of lanes that drew it) before the global add.  Integers only: the order of the adds
+//             does not show.
+//   EM        the transposed CSR once, as shn_abundance_em builds it; alpha, w, d and the counts as doubles laid out [slot][row] for the
+//             replicates resident at once; a round is ONE d launch and ONE alpha launch over (row x live replicate), blockIdx.y = the
+//             position in the list of live slots.  The loops, the shuffle tree and the expressions are those of abd_em_d_kernel /
+//             abd_em_alpha_kernel, so a replicate's bits are shn_abundance_em's on its counts.  A moved flag per slot; after 50
+//             rounds the host reads the flags once and strikes the replicates that are done from the list.
+#define ABD_RS_DRAWS 4096u     // draws a block makes for one replicate (16 a thread)
+#define ABD_RS_LDS 8192u       // classes a block counts in LDS (32 KiB of 32-bit bins)
+#define ABD_EMB_SLOTS 32768u   // replicates resident at once at the most (blockIdx.y)
+#define ABD_EMB_BUDGET (1ULL << 30)   // bytes of alpha, w, d and counts of the resident replicates that max_live == 0 allows
+
+struct AbdPhilox { uint32_t c0, c1, c2, c3; };
+__device__ __forceinline__ AbdPhilox abd_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+  for (int r = 0; r < 10; r++) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return AbdPhilox{c0, c1, c2, c3};
+}
+
+// class of draw t of replicate b
+__device__ __forceinline__ uint32_t abd_draw(uint64_t t, uint32_t b, uint32_t k0, uint32_t k1, uint64_t N, const uint64_t* __restrict__ cum,
+                                             uint64_t n_classes) {
+  const AbdPhilox o = abd_philox((uint32_t)t, b, 0u, 0u, k0, k1);
+  const uint64_t u = (uint64_t)o.c0 | (uint64_t)o.c1 << 32;
+  return (uint32_t)shn_segment_of(cum, n_classes, __umul64hi(u, N));
+}
+
+// work item wi = (replicate wi / chunks, draws [chunk * ABD_RS_DRAWS, ...) of it); LDS: n_classes bins when lds != 0
+__global__ __launch_bounds__(FFP_BLOCK) void abd_resample_kernel(uint64_t N, uint64_t n_classes, uint64_t B, uint64_t chunks, uint32_t k0, uint32_t k1,
+                                                                 const uint64_t* __restrict__ cum, int lds, unsigned long long* __restrict__ counts) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t abd_rs[];
+  for (uint64_t wi = blockIdx.x; wi < B * chunks; wi += gridDim.x) {
+    const uint64_t b = wi / chunks, t0 = (wi - b * chunks) * ABD_RS_DRAWS;
+    const uint64_t t1 = t0 + ABD_RS_DRAWS < N ? t0 + ABD_RS_DRAWS : N;
+    unsigned long long* out = counts + b * n_classes;
+    if (lds) {
+      for (uint32_t c = threadIdx.x; c < n_classes; c += FFP_BLOCK) abd_rs[c] = 0;
+      __syncthreads();
+      for (uint64_t t = t0 + threadIdx.x; t < t1; t += FFP_BLOCK) atomicAdd(&abd_rs[abd_draw(t, (uint32_t)b, k0, k1, N, cum, n_classes)], 1u);
+      __syncthreads();
+      for (uint32_t c = threadIdx.x; c < n_classes; c += FFP_BLOCK)
+        if (abd_rs[c]) atomicAdd(&out[c], (unsigned long long)abd_rs[c]);
+      __syncthreads();
+    } else {
+      for (uint64_t base = t0; base < t1; base += FFP_BLOCK) {          // (the same trip count for every lane of a wave)
+        const uint64_t t = base + threadIdx.x;
+        const bool on = t < t1;
+        const uint32_t c = on ? abd_draw(t, (uint32_t)b, k0, k1, N, cum, n_classes) : 0u;
+        unsigned long long todo = __ballot(on);
+        const uint32_t lane = threadIdx.x & 63;
+        while (todo) {                                                  // one turn per distinct class among the wave's draws
+          const int lead = __ffsll((long long)todo) - 1;
+          const uint32_t cl = (uint32_t)__shfl((int)c, lead, 64);
+          const unsigned long long same = __ballot(on && c == cl) & todo;
+          if (lane == (uint32_t)lead) atomicAdd(&out[cl], (unsigned long long)__popcll(same));
+          todo &= ~same;
+        }
+      }
+    }
+  }
+}
+
+// the counts of rule 1 into d_counts[B][n_classes] (device); N = sum n_c < 2^32, B < 2^32 (the callers refuse anything else)
+static int abd_resample_run(shn_ctx* ctx, ShnDevBufs& bufs, const uint64_t* n_c, uint64_t n_classes, uint64_t N, uint64_t B, uint64_t seed,
+                            unsigned long long* d_counts) {
+  hipStream_t s = ctx->stream;
+  if (B * n_classes) HIP_TRY(hipMemsetAsync(d_counts, 0, B * n_classes * 8, s));
+  if (N == 0 || n_classes == 0) return SHN_OK;
+  std::vector<uint64_t> cum(n_classes + 1, 0);
+  for (uint64_t c = 0; c < n_classes; c++) cum[c + 1] = cum[c] + n_c[c];
+  uint64_t* d_cum = nullptr;
+  HIP_TRY(bufs.get(&d_cum, (n_classes + 1) * 8));
+  HIP_TRY(hipMemcpyAsync(d_cum, cum.data(), (n_classes + 1) * 8, hipMemcpyHostToDevice, s));
+  const uint64_t chunks = cdiv(N, ABD_RS_DRAWS);
+  const int lds = n_classes <= ABD_RS_LDS;
+  {
+    TimerRegion treg(ctx, T_ABD_RESAMPLE);
+    // bytes: the draws come from registers; the prefix sum is searched in the caches and priced once; a bin of every replicate is
+    // zeroed and, at the least, added to once (16 B)
+    treg.bytes((n_classes + 1) * 8 + B * n_classes * 16);
+    hipLaunchKernelGGL(abd_resample_kernel, dim3(shn_grid(B * chunks, 1)), dim3(FFP_BLOCK), lds ? n_classes * 4 : 0, s, N, n_classes, B, chunks,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), d_cum, lds, d_counts);
+  }
+  HIP_TRY(hipStreamSynchronize(s));                                     // (cum is a host vector)
+  HIP_TRY(hipGetLastError());
+  return SHN_OK;
+}
+
+// N = sum n_c, refused at 2^32 (and B at 2^32): before anything is launched
+static int abd_resample_check(const std::string& fn, const uint64_t* n_c, uint64_t n_classes, uint64_t B, uint64_t* N) {
+  if (B == 0) return shn_fail(SHN_ERR_ARG, fn + ": no replicates (B is 0)");
+  if (B >= (1ULL << 32)) return shn_fail(SHN_ERR_OVERFLOW, fn + ": 2^32 or more replicates");
+  if (n_classes >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many classes");
+  uint64_t n = 0;
+  for (uint64_t c = 0; c < n_classes; c++) {
+    if (n_c[c] >= (1ULL << 32) || n + n_c[c] >= (1ULL << 32)) return shn_fail(SHN_ERR_OVERFLOW, fn + ": 2^32 or more fragments in the classes");
+    n += n_c[c];
+  }
+  *N = n;
+  return SHN_OK;
+}
+
+extern "C" int shn_abundance_resample(shn_ctx* ctx, const uint64_t* n_c, uint64_t n_classes, uint64_t B, uint64_t seed, uint64_t* counts_out) {
+  const std::string fn("shn_abundance_resample");
+  if (!ctx || (n_classes && (!n_c || !counts_out))) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
+  uint64_t N = 0;
+  if (int rc = abd_resample_check(fn, n_c, n_classes, B, &N)) return rc;
+  if (n_classes == 0) return SHN_OK;
+  if (N == 0) { std::fill(counts_out, counts_out + B * n_classes, 0ULL); return SHN_OK; }
+  SHN_ENTER(ctx);
+  shn_stage_begin(ctx);
+  hipStream_t s = ctx->stream;
+  ShnDevBufs bufs(s);
+  unsigned long long* d_counts = nullptr;
+  HIP_TRY(bufs.get(&d_counts, B * n_classes * 8));
+  if (int rc = abd_resample_run(ctx, bufs, n_c, n_classes, N, B, seed, d_counts)) return rc;
+  HIP_TRY(hipMemcpyAsync(counts_out, d_counts, B * n_classes * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipGetLastError());
+  return SHN_OK;
+}
+
+// ---- the batched EM
+// the refusals of shn_abundance_em, under the caller's name
+static int abd_em_check(const std::string& fn, const uint64_t* class_off, const uint32_t* members, uint64_t n_classes, const double* eff, uint64_t m) {
+  if (m == 0) return shn_fail(SHN_ERR_ARG, fn + ": no transcripts (m is 0)");
+  if (!class_off || !eff) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
+  if (m >= 0xFFFFFFFFULL || n_classes >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many transcripts or classes");
+  if (class_off[0] != 0) return shn_fail(SHN_ERR_ARG, fn + ": class_off[0] is not 0");
+  for (uint64_t c = 0; c < n_classes; c++)
+    if (class_off[c + 1] < class_off[c]) return shn_fail(SHN_ERR_ARG, fn + ": class_off not monotone");
+  const uint64_t n_entries = class_off[n_classes];
+  if (n_entries >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many class members");
+  if (n_entries && !members) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
+  for (uint64_t e = 0; e < n_entries; e++)
+    if (members[e] >= m) return shn_fail(SHN_ERR_ARG, fn + ": a class names transcript " + std::to_string(members[e]) + " of " + std::to_string(m));
+  for (uint64_t j = 0; j < m; j++)
+    if (!(eff[j] > 0.0)) return shn_fail(SHN_ERR_ARG, fn + ": eff of transcript " + std::to_string(j) + " is not above 0");
+  return SHN_OK;
+}
+
+// the classes, their transposition and eff on the device: what every replicate shares
+struct AbdEmDev {
+  uint64_t n_classes = 0, n_entries = 0, m = 0;
+  uint64_t *coff = nullptr, *troff = nullptr;
+  uint32_t *mem = nullptr, *trcls = nullptr;
+  double* eff = nullptr;
+};
+
+static int abd_em_setup(shn_ctx* ctx, ShnDevBufs& bufs, const uint64_t* class_off, const uint32_t* members, uint64_t n_classes, const double* eff,
+                        uint64_t m, AbdEmDev* E) {
+  hipStream_t s = ctx->stream;
+  const uint64_t n_entries = class_off[n_classes];
+  E->n_classes = n_classes; E->n_entries = n_entries; E->m = m;
+  uint64_t *d_key = nullptr, *d_key_tmp = nullptr;
+  uint32_t *d_val = nullptr, *d_val_tmp = nullptr, *d_cls = nullptr;
+  HIP_TRY(bufs.get(&E->coff, (n_classes + 1) * 8));
+  HIP_TRY(bufs.get(&E->mem, (n_entries + 1) * 4));
+  HIP_TRY(bufs.get(&E->eff, m * 8));
+  HIP_TRY(bufs.get(&E->troff, (m + 1) * 8));
+  HIP_TRY(bufs.get(&E->trcls, (n_entries + 1) * 4));
+  HIP_TRY(bufs.get(&d_key, (n_entries + 1) * 8));
+  HIP_TRY(bufs.get(&d_key_tmp, (n_entries + 1) * 8));
+  HIP_TRY(bufs.get(&d_val, (n_entries + 1) * 4));
+  HIP_TRY(bufs.get(&d_val_tmp, (n_entries + 1) * 4));
+  HIP_TRY(bufs.get(&d_cls, (n_entries + 1) * 4));
+  HIP_TRY(hipMemcpyAsync(E->coff, class_off, (n_classes + 1) * 8, hipMemcpyHostToDevice, s));
+  if (n_entries) HIP_TRY(hipMemcpyAsync(E->mem, members, n_entries * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(E->eff, eff, m * 8, hipMemcpyHostToDevice, s));
+  int key_bits = 1;
+  while (key_bits < 32 && (m >> key_bits)) key_bits++;
+  TimerRegion treg(ctx, T_ABD_EM_BATCH);
+  // bytes, the transposition (once for all replicates): as shn_abundance_em prices it, without the per-replicate alpha and w
+  treg.bytes(n_entries * (32 + 24 * (uint64_t)((key_bits + 7) / 8)) + (m + 1) * 8);
+  if (n_entries) {
+    hipLaunchKernelGGL(abd_entries_kernel, dim3((uint32_t)cdiv(n_entries, 256)), dim3(256), 0, s, n_entries, n_classes, E->coff, E->mem, d_key, d_val, d_cls);
+    int rc = shn_sort_pairs(ctx, d_key, d_val, d_key_tmp, d_val_tmp, n_entries, 0, key_bits);
+    if (rc) return rc;
+  }
+  const uint64_t n_t = n_entries > m + 1 ? n_entries : m + 1;
+  hipLaunchKernelGGL(abd_transpose_kernel, dim3((uint32_t)cdiv(n_t, 256)), dim3(256), 0, s, n_entries, m, d_key, d_val, d_cls, E->troff, E->trcls);
+  return SHN_OK;
+}
+
+// slot s < n_slots: the counts of replicate b0 + s as doubles, alpha = 1 / m, w = alpha / eff
+__global__ void abd_emb_init_kernel(uint64_t n_slots, uint64_t m, uint64_t n_classes, const unsigned long long* __restrict__ counts,
+                                    const double* __restrict__ eff, double* __restrict__ ncd, double* __restrict__ alpha, double* __restrict__ w) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_slots * n_classes) ncd[i] = (double)counts[i];
+  if (i < n_slots * m) {
+    const double a = 1.0 / (double)m;
+    alpha[i] = a;
+    w[i] = a / eff[i % m];
+  }
+}
+
+// abd_em_d_kernel for the slot live[blockIdx.y]
+__global__ __launch_bounds__(FFP_BLOCK) void abd_emb_d_kernel(uint64_t n_classes, uint64_t m, const uint64_t* __restrict__ class_off,
+                                                              const uint32_t* __restrict__ members, const uint32_t* __restrict__ live,
+                                                              const double* __restrict__ w_all, double* __restrict__ d_all) {
+  const uint64_t c = (uint64_t)blockIdx.x * (FFP_BLOCK / 64) + (threadIdx.x >> 6);
+  if (c >= n_classes) return;                               // (the whole wave)
+  const uint64_t slot = live[blockIdx.y];
+  const double* __restrict__ w = w_all + slot * m;
+  const uint32_t lane = threadIdx.x & 63;
+  double x = 0.0;
+  for (uint64_t e = class_off[c] + lane, end = class_off[c + 1]; e < end; e += 64) x += w[members[e]];
+  x = abd_wave_sum(x);
+  if (lane == 0) d_all[slot * n_classes + c] = x;
+}
+
+// abd_em_alpha_kernel for the slot live[blockIdx.y]; check != 0: moved[slot] is raised
+__global__ __launch_bounds__(FFP_BLOCK) void abd_emb_alpha_kernel(uint64_t m, uint64_t n_classes, const uint64_t* __restrict__ tr_off,
+                                                                  const uint32_t* __restrict__ tr_cls, const uint32_t* __restrict__ live,
+                                                                  const double* __restrict__ ncd_all, const double* __restrict__ d_all,
+                                                                  const double* __restrict__ eff, double* __restrict__ alpha_all,
+                                                                  double* __restrict__ w_all, int check, uint32_t* __restrict__ moved) {
+  const uint64_t j = (uint64_t)blockIdx.x * (FFP_BLOCK / 64) + (threadIdx.x >> 6);
+  if (j >= m) return;                                       // (the whole wave)
+  const uint64_t slot = live[blockIdx.y];
+  const double* __restrict__ n_c = ncd_all + slot * n_classes;
+  const double* __restrict__ d = d_all + slot * n_classes;
+  double* __restrict__ alpha = alpha_all + slot * m;
+  double* __restrict__ w = w_all + slot * m;
+  const uint32_t lane = threadIdx.x & 63;
+  const double wj = w[j];
+  double x = 0.0;
+  for (uint64_t t = tr_off[j] + lane, end = tr_off[j + 1]; t < end; t += 64) {
+    const uint32_t c = tr_cls[t];
+    const double dc = d[c];
+    if (dc != 0.0) x += n_c[c] * wj / dc;
+  }
+  x = abd_wave_sum(x);
+  if (lane == 0) {
+    const double old = alpha[j];
+    alpha[j] = x;
+    w[j] = x / eff[j];
+    if (check && x > 1e-2 && fabs(x - old) > 1e-2 * x) moved[slot] = 1u;
+  }
+}
+
+// rule 4 for the B count vectors d_counts[B][n_classes] (device) -> alpha_out[B][m], rounds_out[B] (host)
+static int abd_em_batch_run(shn_ctx* ctx, ShnDevBufs& bufs, const AbdEmDev& E, const unsigned long long* d_counts, uint64_t B, uint64_t max_live,
+                            double* alpha_out, uint32_t* rounds_out) {
+  hipStream_t s = ctx->stream;
+  const uint64_t m = E.m, n_classes = E.n_classes, n_entries = E.n_entries;
+  const uint64_t per_slot = (2 * m + 2 * n_classes) * 8;
+  uint64_t L = ABD_EMB_BUDGET / per_slot;
+  if (L < 1) L = 1;
+  if (L > ABD_EMB_SLOTS) L = ABD_EMB_SLOTS;
+  if (max_live && max_live < L) L = max_live;
+  if (B < L) L = B;
+  double *d_ncd = nullptr, *d_alpha = nullptr, *d_w = nullptr, *d_d = nullptr;
+  uint32_t *d_live = nullptr, *d_moved = nullptr;
+  HIP_TRY(bufs.get(&d_ncd, (L * n_classes + 1) * 8));
+  HIP_TRY(bufs.get(&d_d, (L * n_classes + 1) * 8));
+  HIP_TRY(bufs.get(&d_alpha, L * m * 8));
+  HIP_TRY(bufs.get(&d_w, L * m * 8));
+  HIP_TRY(bufs.get(&d_live, L * 4));
+  HIP_TRY(bufs.get(&d_moved, L * 4));
+  const uint32_t waves = FFP_BLOCK / 64;
+  std::vector<uint32_t> live, moved(L);
+  for (uint64_t b0 = 0; b0 < B; b0 += L) {
+    const uint64_t n_slots = B - b0 < L ? B - b0 : L;
+    live.resize(n_slots);
+    for (uint64_t k = 0; k < n_slots; k++) live[k] = (uint32_t)k;
+    HIP_TRY(hipMemcpyAsync(d_live, live.data(), n_slots * 4, hipMemcpyHostToDevice, s));
+    {
+      TimerRegion treg(ctx, T_ABD_EM_BATCH);
+      // bytes: a count read and written as a double (16 B a class and replicate), alpha and w written, eff read (24 B a transcript)
+      treg.bytes(n_slots * (n_classes * 16 + m * 24));
+      const uint64_t n_i = n_slots * (n_classes > m ? n_classes : m);
+      hipLaunchKernelGGL(abd_emb_init_kernel, dim3((uint32_t)cdiv(n_i, 256)), dim3(256), 0, s, n_slots, m, n_classes, d_counts + b0 * n_classes, E.eff,
+                         d_ncd, d_alpha, d_w);
+    }
+    uint32_t round = 0;
+    while (!live.empty()) {                                   // a block of 50 rounds of the live replicates, the last with the test; one read of the flags
+      const uint32_t n_live = (uint32_t)live.size();
+      HIP_TRY(hipMemsetAsync(d_moved, 0, n_slots * 4, s));
+      {
+        TimerRegion treg(ctx, T_ABD_EM_BATCH);
+        // bytes of a round and live replicate: as shn_abundance_em prices a round (the members and offsets are shared, and re-read
+        // from the caches by every replicate's waves: priced per replicate all the same)
+        treg.bytes(50 * (uint64_t)n_live * (n_classes * 24 + n_entries * 32 + m * 56));
+        for (int k = 0; k < 50; k++) {
+          if (n_classes)
+            hipLaunchKernelGGL(abd_emb_d_kernel, dim3((uint32_t)cdiv(n_classes, waves), n_live), dim3(FFP_BLOCK), 0, s, n_classes, m, E.coff, E.mem, d_live,
+                               d_w, d_d);
+          hipLaunchKernelGGL(abd_emb_alpha_kernel, dim3((uint32_t)cdiv(m, waves), n_live), dim3(FFP_BLOCK), 0, s, m, n_classes, E.troff, E.trcls, d_live,
+                             d_ncd, d_d, E.eff, d_alpha, d_w, k == 49 ? 1 : 0, d_moved);
+        }
+      }
+      round += 50;
+      HIP_TRY(hipMemcpyAsync(moved.data(), d_moved, n_slots * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      HIP_TRY(hipGetLastError());
+      size_t keep = 0;
+      for (uint32_t slot : live) {
+        if (moved[slot] && round < 10000) live[keep++] = slot;
+        else rounds_out[b0 + slot] = round;
+      }
+      if (keep != live.size()) {
+        live.resize(keep);
+        if (keep) HIP_TRY(hipMemcpyAsync(d_live, live.data(), keep * 4, hipMemcpyHostToDevice, s));
+      }
+    }
+    HIP_TRY(hipMemcpyAsync(alpha_out + b0 * m, d_alpha, n_slots * m * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+  }
+  for (uint64_t i = 0; i < B * m; i++)
+    if (alpha_out[i] < 1e-8) alpha_out[i] = 0.0;
+  return SHN_OK;
+}
+
+// shn_abundance_em for B count vectors at once: DESIGN.md 3.14 rule 2
+extern "C" int shn_abundance_em_batch(shn_ctx* ctx, const uint64_t* class_off, const uint32_t* members, const uint64_t* n_c, uint64_t n_classes,
+                                      const double* eff, uint64_t m, uint64_t B, uint64_t max_live, double* alpha_out, uint32_t* rounds_out) {
+  const std::string fn("shn_abundance_em_batch");
+  if (int rc = abd_em_check(fn, class_off, members, n_classes, eff, m)) return rc;
+  if (!ctx || !alpha_out || !rounds_out || (n_classes && !n_c)) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
+  if (B == 0) return shn_fail(SHN_ERR_ARG, fn + ": no replicates (B is 0)");
+  if (B >= (1ULL << 32)) return shn_fail(SHN_ERR_OVERFLOW, fn + ": 2^32 or more replicates");
+  SHN_ENTER(ctx);
+  shn_stage_begin(ctx);
+  hipStream_t s = ctx->stream;
+  ShnDevBufs bufs(s);
+  AbdEmDev E;
+  if (int rc = abd_em_setup(ctx, bufs, class_off, members, n_classes, eff, m, &E)) return rc;
+  unsigned long long* d_counts = nullptr;
+  HIP_TRY(bufs.get(&d_counts, (B * n_classes + 1) * 8));
+  if (n_classes) HIP_TRY(hipMemcpyAsync(d_counts, n_c, B * n_classes * 8, hipMemcpyHostToDevice, s));
+  return abd_em_batch_run(ctx, bufs, E, d_counts, B, max_live, alpha_out, rounds_out);
+}
+
+// resample, then the batched EM, the counts staying on the device: DESIGN.md 3.14
+extern "C" int shn_abundance_bootstrap(shn_ctx* ctx, const uint64_t* class_off, const uint32_t* members, const uint64_t* n_c, uint64_t n_classes,
+                                       const double* eff, uint64_t m, uint64_t B, uint64_t seed, uint64_t max_live, double* alpha_out,
+                                       uint32_t* rounds_out, uint64_t* counts_out) {
+  const std::string fn("shn_abundance_bootstrap");
+  if (int rc = abd_em_check(fn, class_off, members, n_classes, eff, m)) return rc;
+  if (!ctx || !alpha_out || !rounds_out || (n_classes && !n_c)) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
+  uint64_t N = 0;
+  if (int rc = abd_resample_check(fn, n_c, n_classes, B, &N)) return rc;
+  SHN_ENTER(ctx);
+  shn_stage_begin(ctx);
+  hipStream_t s = ctx->stream;
+  ShnDevBufs bufs(s);
+  AbdEmDev E;
+  if (int rc = abd_em_setup(ctx, bufs, class_off, members, n_classes, eff, m, &E)) return rc;
+  unsigned long long* d_counts = nullptr;
+  HIP_TRY(bufs.get(&d_counts, (B * n_classes + 1) * 8));
+  if (int rc = abd_resample_run(ctx, bufs, n_c, n_classes, N, B, seed, d_counts)) return rc;
+  if (counts_out && n_classes) HIP_TRY(hipMemcpyAsync(counts_out, d_counts, B * n_classes * 8, hipMemcpyDeviceToHost, s));
+  return abd_em_batch_run(ctx, bufs, E, d_counts, B, max_live, alpha_out, rounds_out);
+}

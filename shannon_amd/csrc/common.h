@@ -65,7 +65,9 @@ enum {
   // --compare (compare.hip): both texts packed + the index of the oriented targets' 16-mers, the candidate diagonals (count, scan,
   // fill, sort, unique), the wave-per-diagonal scoring, best per pair + the rows; the chained rows (block order, the wave-per-group
   // chaining, the pair's orientation, rows and blocks)
-  T_CMP_INDEX, T_CMP_SEEDS, T_CMP_SCORE, T_CMP_ROWS, T_CMP_CHAIN, T_N = 64
+  T_CMP_INDEX, T_CMP_SEEDS, T_CMP_SCORE, T_CMP_ROWS, T_CMP_CHAIN,
+  // quant -b (abundance.hip): the bootstrap replicates' class counts, the EM over all live replicates at once
+  T_ABD_RESAMPLE, T_ABD_EM_BATCH, T_N = 72     // (T_N: device.TIMER_SLOTS)
 };
 
 // grow-only device workspace slot (process-wide ones: g_shn_ws below; per-context ones: shn_ctx::cws)

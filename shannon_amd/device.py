@@ -6,6 +6,7 @@ from . import _lib
 ENC_ASCII, ENC_CODES = 0, 1
 ALPHA = "ACGT"
 ALPHA_BYTES = np.frombuffer(b"ACGTN", dtype=np.uint8)        # (code 4 = a base outside ACGT)
+TIMER_SLOTS = 72      # T_N of csrc/common.h: a slot without a name is skipped
 
 
 class Context(object):
@@ -27,7 +28,7 @@ class Context(object):
     def timers(self):
         """{name: (ms, n_regions)} of HIP-event timed kernel groups since the last reset."""
         out = {}
-        for slot in range(64):
+        for slot in range(TIMER_SLOTS):
             name = _lib.lib().shn_timer_name(slot).decode()
             if not name:
                 continue
@@ -40,7 +41,7 @@ class Context(object):
     def timer_bytes(self):
         """{name: algorithmic bytes} the launch sites of the timed kernels have declared since the last reset (shn_timer_bytes)"""
         out = {}
-        for slot in range(64):
+        for slot in range(TIMER_SLOTS):
             name = _lib.lib().shn_timer_name(slot).decode()
             if not name:
                 continue

@@ -2,6 +2,7 @@
 (filter_kallisto.py:23-31 -- `kallisto index` + `kallisto quant`, with `--single -l 200 -s 20` for one read file).
 
     python -m shannon_amd.quant TRANSCRIPTS.fasta -o DIR (--single R | --left R1 --right R2) [-s] [--cutoff C] [-l MEAN] [--sd SD]
+                                [-b B [--seed S]]
 
 Paired reads go through abundance.quantify, unchanged: abundance.tsv is what a --kallisto_cutoff run writes for the
 same transcripts and pairs.  Single reads go through abundance.quantify_single.  Written into DIR:
@@ -9,6 +10,14 @@ same transcripts and pairs.  Single reads go through abundance.quantify_single (
     abundance.tsv    abundance.abundance_tsv of the table: kallisto's header, the floats written with repr
     quant_log.txt    reads or pairs, mapped, classes, EM rounds, L, and the abundance.* kernel groups' times and priced bytes
     filtered.fasta   with --cutoff C: abundance.decide on the text of abundance.tsv and of TRANSCRIPTS.fasta
+
+With -b B (bootstrap replicates of the abundances under the 64-bit seed S, 0 unless given: DESIGN.md 3.14) also:
+
+    bs_abundance_<b>.tsv   b = 0..B-1: abundance.abundance_tsv of replicate b's table (kallisto's --plaintext layout)
+    bootstrap_summary.tsv  target_id est_counts bs_mean bs_sd bs_min bs_max, the floats written with repr
+    quant_log.txt          one more line: B, the seed, the smallest and the largest round count of the replicates
+
+abundance.tsv and filtered.fasta are byte for byte those of the run without -b.
 
     targets       (names, sequences) of the FASTA text; a duplicate id, an empty id or an empty sequence raises QuantError
     load_reads    a read file -> a resident device.Reads (the device ingest, else record by record)
@@ -18,16 +27,19 @@ same transcripts and pairs.  Single reads go through abundance.quantify_single (
 `targets` and the argument checks of `main` need neither the library nor a GPU."""
 import json
 import os
+import re
 import sys
 
-USAGE = ("usage: python -m shannon_amd.quant TRANSCRIPTS.fasta -o DIR (--single R | --left R1 --right R2) [-s] [--cutoff C] [-l MEAN] [--sd SD]\n"
+USAGE = ("usage: python -m shannon_amd.quant TRANSCRIPTS.fasta -o DIR (--single R | --left R1 --right R2) [-s] [--cutoff C] [-l MEAN] [--sd SD] [-b B [--seed S]]\n"
          "  TRANSCRIPTS.fasta  the transcripts to quantify (2-line or multi-line FASTA; the id is the header's first token)\n"
          "  -o DIR             where abundance.tsv, quant_log.txt and filtered.fasta go\n"
          "  --single R         single-end reads (FASTA or FASTQ)\n"
          "  --left R1 --right R2  paired reads, mates in the same order\n"
          "  -s                 strand-specific: single reads are placed forward only, pairs as (R1, RC(R2)) only\n"
          "  --cutoff C         also write filtered.fasta: the transcripts with est_counts / eff_length * L >= C\n"
-         "  -l MEAN, --sd SD   single-end only: mean and standard deviation of the fragment-length model (200, 20)\n")
+         "  -l MEAN, --sd SD   single-end only: mean and standard deviation of the fragment-length model (200, 20)\n"
+         "  -b B               also B >= 1 bootstrap replicates: bs_abundance_<b>.tsv and bootstrap_summary.tsv\n"
+         "  --seed S           with -b: the seed of the resampling, an integer in 0 .. 2^64 - 1 (0)\n")
 
 
 class QuantError(Exception):
@@ -88,9 +100,11 @@ def load_reads(ctx, path):
     return device.Reads.from_strings(ctx, _read_records(path))
 
 
-def quantify_files(fasta, out_dir, single=None, left=None, right=None, strand_specific=False, cutoff=None, mean=None, sd=None, ctx=None):
+def quantify_files(fasta, out_dir, single=None, left=None, right=None, strand_specific=False, cutoff=None, mean=None, sd=None, ctx=None, bootstraps=None,
+                   seed=0):
     """The command's work: the table of the transcripts of `fasta` under the reads of `single`, or the pairs of `left` / `right`,
-    written into out_dir (the module's head says what).  Returns the table with "L", "paired" and, with a cutoff, "kept"."""
+    written into out_dir (the module's head says what).  Returns the table with "L", "paired" and, with a cutoff, "kept"; with bootstraps=B, the
+    replicates' columns (abundance.quantify)."""
     from . import abundance, device, _lib
     with open(fasta) as f:
         fasta_text = f.read()
@@ -107,11 +121,11 @@ def quantify_files(fasta, out_dir, single=None, left=None, right=None, strand_sp
             raise QuantError("%s holds %d reads, %s holds %d: not mates of each other" % (left, len(sets[0]), right, len(sets[1])))
         ctx.timer_reset()
         if paired:
-            table = abundance.quantify(ctx, names, seqs, sets[0], sets[1], strand_specific)
+            table = abundance.quantify(ctx, names, seqs, sets[0], sets[1], strand_specific, bootstraps=bootstraps, seed=seed)
             table["L"] = abundance.fragment_bases(sets[0], sets[1])
         else:
             table = abundance.quantify_single(ctx, names, seqs, sets[0], strand_specific, abundance.MODEL_MEAN if mean is None else mean,
-                                              abundance.MODEL_SD if sd is None else sd)
+                                              abundance.MODEL_SD if sd is None else sd, bootstraps=bootstraps, seed=seed)
             n = len(sets[0])
             table["L"] = int(_lib.lib().shn_reads_total_bases(sets[0].h)) / n if n else 0.0      # (shannon.py:613 with one file)
         tm, tb = ctx.timers(), ctx.timer_bytes()
@@ -137,6 +151,14 @@ def quantify_files(fasta, out_dir, single=None, left=None, right=None, strand_sp
             f.write(kept_text)
         table["kept"] = sum(1 for line in kept_text.splitlines() if line.startswith(">"))
         log.append("--cutoff %s: %d of %d transcripts kept" % (repr(float(cutoff)), table["kept"], len(names)))
+    if bootstraps is not None:
+        for b in range(table["bootstraps"]):
+            with open(os.path.join(out_dir, "bs_abundance_%d.tsv" % b), "w") as f:
+                f.write(abundance.abundance_tsv(abundance.replicate_table(table, b)))
+        with open(os.path.join(out_dir, "bootstrap_summary.tsv"), "w") as f:
+            f.write(abundance.bootstrap_summary_tsv(table))
+        log.append("-b %d --seed %d: EM rounds of the replicates %d .. %d" % (table["bootstraps"], table["seed"], min(table["bs_rounds"]),
+                                                                               max(table["bs_rounds"])))
     log.append("abundance kernels: " + json.dumps({k: {"ms": round(v[0], 4), "regions": v[1], "bytes": tb.get(k, 0)}
                                                     for k, v in sorted(tm.items()) if k.startswith("abundance.")}))
     with open(os.path.join(out_dir, "quant_log.txt"), "w") as f:
@@ -146,7 +168,8 @@ def quantify_files(fasta, out_dir, single=None, left=None, right=None, strand_sp
 
 def parse_args(argv):
     """argv (the program's name first) -> a dict of quantify_files' arguments, or a message (a usage error)"""
-    takes = {"-o": "out_dir", "--single": "single", "--left": "left", "--right": "right", "--cutoff": "cutoff", "-l": "mean", "--sd": "sd"}
+    takes = {"-o": "out_dir", "--single": "single", "--left": "left", "--right": "right", "--cutoff": "cutoff", "-l": "mean", "--sd": "sd",
+             "-b": "bootstraps", "--seed": "seed"}
     o = {"strand_specific": False}
     rest = []
     a = list(argv[1:])
@@ -185,6 +208,15 @@ def parse_args(argv):
                 return "%s is not a finite number" % o[k]
     if "sd" in o and not o["sd"] > 0.0:
         return "--sd must be above 0"
+    if "seed" in o and "bootstraps" not in o:
+        return "--seed belongs to -b B: without replicates nothing is drawn"
+    for k, flag, lo, hi in (("bootstraps", "-b", 1, (1 << 32) - 1), ("seed", "--seed", 0, (1 << 64) - 1)):
+        if k in o:
+            if not re.fullmatch("-?[0-9]+", o[k]):
+                return "%s %s is not an integer" % (flag, o[k])
+            o[k] = int(o[k], 10)
+            if not lo <= o[k] <= hi:
+                return "%s %d is outside %d .. %d" % (flag, o[k], lo, hi)
     for k in ("fasta", "single", "left", "right"):
         if k in o and not os.path.isfile(o[k]):
             return "%s: no such file" % o[k]

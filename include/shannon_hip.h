@@ -469,7 +469,9 @@ void shn_abundance_destroy(shn_abundance* a);
  * on classes given as HOST arrays: alpha_j = 1 / m, then rounds of d_c = sum_{j in c} alpha_j / eff_j, alpha'_j = sum_{c with j}
  * n_c (alpha_j / eff_j) / d_c in IEEE double with a fixed order of every sum (DESIGN.md 3.10 rule 4); tested after rounds 50, 100, ...,
  * ends after 10,000 at the latest; alpha_j < 1e-8 is returned as 0.  Refused before anything is launched: m == 0, a class_off that
- * is not monotone or does not start at 0, a member >= m, an eff that is not above 0.
+ * is not monotone or does not start at 0, a member >= m, an eff that is not above 0 -- one set of checks and one construction of the
+ * transposed classes, shared with shn_abundance_em_batch and shn_abundance_bootstrap below; the rounds run in kernels of its own (a
+ * slot index less than the batched ones), and the bits of both are pinned by tests/golden/abundance_em_bits.json.
  *   alpha[m] (host, written), *rounds = rounds run */
 int shn_abundance_em(shn_ctx* ctx, const uint64_t* class_off, const uint32_t* members, const uint64_t* n_c, uint64_t n_classes, const double* eff,
                      uint64_t m, double* alpha, uint32_t* rounds);

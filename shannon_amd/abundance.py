@@ -93,6 +93,23 @@ def _export(lib, h):
     return {"class_off": class_off, "members": members[:n_entries], "n_c": n_c[:n_classes], "hist": hist, "mapped": mapped, "fragments": n_frag}
 
 
+def _eff_from_prefix(lens, cnt, tot):
+    """the tail of both rules 2 over prefix sums (cnt[k], tot[k]: the sums over s < k of the weights and of s times the weights, for
+    len(cnt) - 1 bins): eff_j = len_j - tot[k] / cnt[k] + 1 with k = min(len_j, bins - 1) + 1 -- one division, then rounded to double
+    -- or len_j when that is < 1 or cnt[k] is 0"""
+    out = []
+    for n in lens:
+        n = int(n)
+        k = min(n, len(cnt) - 2) + 1
+        eff = float(n)
+        if k > 0 and cnt[k] > 0:
+            e = float(n) - tot[k] / cnt[k] + 1.0
+            if e >= 1.0:
+                eff = e
+        out.append(eff)
+    return np.array(out, dtype=np.float64)
+
+
 def eff_lengths(lens, hist):
     """rule 2: eff_j = len_j - mu_{len_j} + 1, mu_l = (sum of s h[s] over s <= l) / (sum of h[s] over s <= l), the two sums as
     integers and their quotient rounded once to double; eff_j = len_j when that is < 1 or when no span is <= len_j."""
@@ -101,31 +118,15 @@ def eff_lengths(lens, hist):
     for s, x in enumerate(h):
         cnt[s + 1] = cnt[s] + x
         tot[s + 1] = tot[s] + s * x
-    out = []
-    for n in lens:
-        n = int(n)
-        k = min(n, len(h) - 1) + 1
-        eff = float(n)
-        if k > 0 and cnt[k]:
-            e = float(n) - tot[k] / cnt[k] + 1.0
-            if e >= 1.0:
-                eff = e
-        out.append(eff)
-    return np.array(out, dtype=np.float64)
+    return _eff_from_prefix(lens, cnt, tot)
 
 
 def em(ctx, class_off, members, n_c, eff):
     """rule 4 (shn_abundance_em) on host arrays -> (alpha float64[m], rounds)"""
     from . import _lib
-    class_off = np.ascontiguousarray(class_off, dtype=np.uint64)
-    members = np.ascontiguousarray(members, dtype=np.uint32)
     n_c = np.ascontiguousarray(n_c, dtype=np.uint64)
-    eff = np.ascontiguousarray(eff, dtype=np.float64)
-    n_classes, m = len(class_off) - 1, len(eff)
-    if n_classes < 0 or len(n_c) != n_classes:
-        raise ValueError("abundance.em: class_off has %d entries for %d class counts" % (len(class_off), len(n_c)))
-    if n_classes and int(class_off[-1]) > len(members):
-        raise ValueError("abundance.em: class_off ends at %d, %d members given" % (int(class_off[-1]), len(members)))
+    class_off, members, eff, n_classes = _em_arrays("em", class_off, members, eff, len(n_c))
+    m = len(eff)
     alpha = np.zeros(max(m, 1), dtype=np.float64)
     rounds = C.c_uint32(0)
     _lib.check(_lib.lib().shn_abundance_em(ctx.h, class_off.ctypes.data, members.ctypes.data if len(members) else None,
@@ -271,25 +272,33 @@ def tpm_of(alpha, eff):
     return [1e6 * r / total if total > 0.0 else 0.0 for r in rho]
 
 
+def _quantify(who, ctx, names, seqs, fragments, no_hist, classes_and_eff, bootstraps, seed):
+    """what quantify and quantify_single share: the checks, the table without transcripts (`fragments` given, "hist": no_hist), then
+    classes_and_eff(lens) -> (classes, eff) in the caller's order, em, the table, the bootstrap columns"""
+    if len(names) != len(seqs):
+        raise ValueError("%s: %d names for %d sequences" % (who, len(names), len(seqs)))
+    if bootstraps is not None:
+        bootstraps, seed = _replicates(who, bootstraps), _seed(who, seed)
+    lens = [len(s) for s in seqs]
+    if not seqs:
+        return {"names": [], "length": [], "eff_length": [], "est_counts": [], "tpm": [], "mapped": 0, "fragments": fragments, "classes": 0,
+                "rounds": 0, "hist": no_hist, **_no_targets(bootstraps, seed)}
+    cl, eff = classes_and_eff(lens)
+    alpha, rounds = em(ctx, cl["class_off"], cl["members"], cl["n_c"], eff)
+    table = {"names": list(names), "length": lens, "eff_length": eff.tolist(), "est_counts": alpha.tolist(), "tpm": tpm_of(alpha, eff),
+             "mapped": cl["mapped"], "fragments": cl["fragments"], "classes": len(cl["n_c"]), "rounds": rounds, "hist": cl["hist"]}
+    return table if bootstraps is None else _add_bootstraps(ctx, table, cl, eff, bootstraps, seed)
+
+
 def quantify(ctx, names, seqs, d1, d2, strand_specific, max_span=MAX_SPAN, bootstraps=None, seed=0):
     """the abundance table of the transcripts (names[j], seqs[j]) under the pairs of the resident sets d1 / d2 (device.Reads, the mates
     as the user gave them): {"names", "length", "eff_length", "est_counts", "tpm"} (lists, in the order given) + "mapped",
     "fragments", "classes", "rounds", "hist".  bootstraps=B adds B replicates under `seed`: "bs_est_counts" and "bs_tpm" (B
     lists), "bs_rounds", "bs_mean", "bs_sd", "bs_min", "bs_max"; None: nothing of that runs."""
-    if len(names) != len(seqs):
-        raise ValueError("quantify: %d names for %d sequences" % (len(names), len(seqs)))
-    if bootstraps is not None:
-        bootstraps, seed = _replicates("quantify", bootstraps), _seed("quantify", seed)
-    lens = [len(s) for s in seqs]
-    if not seqs:
-        return {"names": [], "length": [], "eff_length": [], "est_counts": [], "tpm": [], "mapped": 0, "fragments": len(d1), "classes": 0,
-                "rounds": 0, "hist": np.zeros(max_span + 1, np.uint64), **_no_targets(bootstraps, seed)}
-    cl = classes(ctx, seqs, d1, d2, strand_specific, max_span)
-    eff = eff_lengths(lens, cl["hist"])
-    alpha, rounds = em(ctx, cl["class_off"], cl["members"], cl["n_c"], eff)
-    table = {"names": list(names), "length": lens, "eff_length": eff.tolist(), "est_counts": alpha.tolist(), "tpm": tpm_of(alpha, eff),
-             "mapped": cl["mapped"], "fragments": cl["fragments"], "classes": len(cl["n_c"]), "rounds": rounds, "hist": cl["hist"]}
-    return table if bootstraps is None else _add_bootstraps(ctx, table, cl, eff, bootstraps, seed)
+    def classes_and_eff(lens):                                  # the classes first: eff needs their span histogram
+        cl = classes(ctx, seqs, d1, d2, strand_specific, max_span)
+        return cl, eff_lengths(lens, cl["hist"])
+    return _quantify("quantify", ctx, names, seqs, len(d1), np.zeros(max_span + 1, np.uint64), classes_and_eff, bootstraps, seed)
 
 
 def eff_lengths_model(lens, mean=MODEL_MEAN, sd=MODEL_SD):
@@ -305,36 +314,16 @@ def eff_lengths_model(lens, mean=MODEL_MEAN, sd=MODEL_SD):
         g = math.exp(-0.5 * (z * z))
         cnt[s + 1] = cnt[s] + g
         tot[s + 1] = tot[s] + float(s) * g
-    out = []
-    for n in lens:
-        n = int(n)
-        k = min(n, MODEL_BINS - 1) + 1
-        eff = float(n)
-        if k > 0 and cnt[k] > 0.0:
-            e = float(n) - tot[k] / cnt[k] + 1.0
-            if e >= 1.0:
-                eff = e
-        out.append(eff)
-    return np.array(out, dtype=np.float64)
+    return _eff_from_prefix(lens, cnt, tot)
 
 
 def quantify_single(ctx, names, seqs, d, strand_specific, mean=MODEL_MEAN, sd=MODEL_SD, bootstraps=None, seed=0):
     """`quantify` for the single reads of the resident set d: classes_single, eff_lengths_model, em, tpm -- the same
     table, "fragments" the reads, "hist" empty; bootstraps / seed as there"""
-    if len(names) != len(seqs):
-        raise ValueError("quantify_single: %d names for %d sequences" % (len(names), len(seqs)))
-    if bootstraps is not None:
-        bootstraps, seed = _replicates("quantify_single", bootstraps), _seed("quantify_single", seed)
-    lens = [len(s) for s in seqs]
-    if not seqs:
-        return {"names": [], "length": [], "eff_length": [], "est_counts": [], "tpm": [], "mapped": 0, "fragments": len(d), "classes": 0,
-                "rounds": 0, "hist": np.zeros(0, np.uint64), **_no_targets(bootstraps, seed)}
-    eff = eff_lengths_model(lens, mean, sd)
-    cl = classes_single(ctx, seqs, d, strand_specific)
-    alpha, rounds = em(ctx, cl["class_off"], cl["members"], cl["n_c"], eff)
-    table = {"names": list(names), "length": lens, "eff_length": eff.tolist(), "est_counts": alpha.tolist(), "tpm": tpm_of(alpha, eff),
-             "mapped": cl["mapped"], "fragments": cl["fragments"], "classes": len(cl["n_c"]), "rounds": rounds, "hist": cl["hist"]}
-    return table if bootstraps is None else _add_bootstraps(ctx, table, cl, eff, bootstraps, seed)
+    def classes_and_eff(lens):                                  # eff first, as before: a bad sd is refused before anything runs
+        eff = eff_lengths_model(lens, mean, sd)
+        return classes_single(ctx, seqs, d, strand_specific), eff
+    return _quantify("quantify_single", ctx, names, seqs, len(d), np.zeros(0, np.uint64), classes_and_eff, bootstraps, seed)
 
 
 def abundance_tsv(table):

@@ -308,6 +308,117 @@ static int abd_emit_classes(shn_ctx* ctx, ShnDevBufs& bufs, uint64_t n_frag, uin
   return SHN_OK;
 }
 
+// ---- the host side of map + classes, for read pairs and for single reads
+// what an entry point's count and fill launches are handed
+struct AbdMap {
+  hipStream_t s;
+  uint32_t grid;
+  FfpIndex I;
+  FfpSet A, B;                          // (B: pairs only)
+  uint64_t n;                           // fragments
+  int ss;
+  uint32_t *best, *cnt, *flag, *ids, *nuniq, *frag;
+  uint64_t *off, *key;
+  unsigned long long *hist, *mapped;    // (hist: n_bins of them; none: NULL)
+};
+
+// The classes of the n fragments of r1 (single reads: r2 == NULL) or (r1, r2) (mates, r1->n_reads == r2->n_reads) on the transcripts,
+// under the caller's name fn: the refusals, the index over one partition, count -> scan -> fill, the classes, *out.  n_bins: the bins of
+// the span histogram count() fills (0: none, the handle reports 0 bins); many / one: what the messages call the fragments; count(M) and
+// fill(M) launch the entry point's two kernels on M.grid blocks of FFP_BLOCK.
+template <class Count, class Fill>
+static int abd_classes_run(const std::string& fn, shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off, uint64_t n_tr, const shn_reads* r1,
+                           const shn_reads* r2, int strand_specific, uint64_t n_bins, const char* many, const char* one, Count&& count, Fill&& fill,
+                           shn_abundance** out) {
+  if (n_tr >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many transcripts");
+  const uint64_t n_frag = r1->n_reads;
+  if (n_frag >= 0xFFFFFFFEULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many " + many + " in one call");
+  std::vector<uint64_t> rec_off;
+  if (int rc = ffp_record_offsets(fn, t_off, n_tr, &rec_off)) return rc;
+  const uint64_t total = t_off[n_tr], n_rec = rec_off[n_tr];
+  if (total >= 0xFFFFFF00ULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": more than 2^32 transcript bases in one call");
+  shn_abundance* R = new shn_abundance();
+  R->n_tr = n_tr; R->n_frag = n_frag;
+  R->hist.assign((size_t)n_bins, 0);
+  R->class_off.assign(1, 0);
+  struct Guard { shn_abundance* p; ~Guard() { delete p; } } guard{R};
+  auto done = [&]() { *out = R; guard.p = nullptr; return SHN_OK; };
+  if (n_rec == 0 || n_frag == 0) return done();
+  SHN_ENTER(ctx);
+  shn_stage_begin(ctx);
+  hipStream_t s = ctx->stream;
+  ShnDevBufs bufs(s);
+
+  // ---- index (all transcripts in partition 0)
+  AbdMap M{};
+  M.s = s; M.n = n_frag; M.ss = strand_specific ? 1 : 0; M.grid = (uint32_t)cdiv(n_frag, FFP_BLOCK);
+  uint64_t n_tw = 0;
+  {
+    std::vector<uint32_t> t_part(n_tr, 0);
+    int rc = ffp_index_build(fn, ctx, bufs, T_ABD_INDEX, text, t_off, t_part.data(), n_tr, 1, rec_off, &M.I, &n_tw);
+    if (rc) return rc;
+  }
+
+  // ---- map: minimum cost + placements per fragment (+ span histogram), scan, lists
+  uint32_t* d_frag_tmp = nullptr;
+  uint64_t* d_key_tmp = nullptr;
+  HIP_TRY(bufs.get(&M.best, n_frag * 4));
+  HIP_TRY(bufs.get(&M.cnt, n_frag * 4));
+  HIP_TRY(bufs.get(&M.flag, 4));
+  HIP_TRY(bufs.get(&M.off, (n_frag + 1) * 8));
+  HIP_TRY(bufs.get(&M.mapped, 8));
+  HIP_TRY(hipMemsetAsync(M.flag, 0, 4, s));
+  HIP_TRY(hipMemsetAsync(M.mapped, 0, 8, s));
+  if (n_bins) {
+    HIP_TRY(bufs.get(&M.hist, n_bins * 8));
+    HIP_TRY(hipMemsetAsync(M.hist, 0, n_bins * 8, s));
+  }
+  uint64_t rc_bytes = 0, n_place = 0;
+  const uint64_t per_frag = (r1->n_words + (r2 ? r2->n_words : 0)) * 8 / n_frag * (strand_specific ? 1 : 2);
+  {
+    TimerRegion treg(ctx, T_ABD_MAP);
+    int rc = ffp_set(ctx, bufs, r1, !strand_specific, &M.A, &rc_bytes);
+    if (!rc && r2) rc = ffp_set(ctx, bufs, r2, true, &M.B, &rc_bytes);
+    if (rc) return rc;
+    // bytes: the read or both mates of every fragment in each orientation used (2 bits a base), minimum cost and count written (8 B);
+    // the index and the text are re-read from the caches and priced once; a block's non-empty bins (at most 8 B each, not priced);
+    // what the reverse complements cost is added above
+    treg.bytes(rc_bytes + n_frag * (per_frag + 8) + n_rec * 12 + n_tw * 8);
+    count(M);
+    // the scan of the numbers: a count read, an offset written (12 B a fragment)
+    treg.bytes(n_frag * 12);
+    rc = shn_device_scan_u32(ctx, M.cnt, n_frag, M.off, &n_place);             // (synchronises)
+    if (rc) return rc;
+  }
+  uint32_t flag = 0;
+  unsigned long long mapped = 0;
+  HIP_TRY(hipMemcpyAsync(&flag, M.flag, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&mapped, M.mapped, 8, hipMemcpyDeviceToHost, s));
+  if (n_bins) HIP_TRY(hipMemcpyAsync(R->hist.data(), M.hist, n_bins * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipGetLastError());
+  if (flag) return shn_fail(SHN_ERR_OVERFLOW, fn + ": " + one + " has 2^32 or more placements of its minimum cost");
+  if (n_place >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": " + std::to_string(n_place) + " placements in one call (2^32 - 1 at most)");
+  R->mapped = mapped;
+  if (mapped == 0) return done();
+  HIP_TRY(bufs.get(&M.ids, (n_place + 1) * 4));
+  HIP_TRY(bufs.get(&M.nuniq, n_frag * 4));
+  HIP_TRY(bufs.get(&M.key, (n_frag + 1) * 8));
+  HIP_TRY(bufs.get(&d_key_tmp, (n_frag + 1) * 8));
+  HIP_TRY(bufs.get(&M.frag, (n_frag + 1) * 4));
+  HIP_TRY(bufs.get(&d_frag_tmp, (n_frag + 1) * 4));
+  {
+    TimerRegion treg(ctx, T_ABD_MAP);
+    // bytes: the reads again, cost and two offsets read (20 B), the ids written, sorted in place and read for the hash (12 B a
+    // placement), count, key and fragment id written (16 B)
+    treg.bytes(n_frag * (per_frag + 36) + n_place * 12 + n_rec * 12 + n_tw * 8);
+    fill(M);
+  }
+  // ---- classes
+  if (int rc = abd_emit_classes(ctx, bufs, n_frag, mapped, n_place, M.off, M.ids, M.nuniq, M.key, d_key_tmp, M.frag, d_frag_tmp, R)) return rc;
+  return done();
+}
+
 // Classes of the read pairs of two resident sets on the final transcripts (kallisto's pseudoalignment, `kallisto quant`,
 // filter_kallisto.py:29, replaced by DESIGN.md 3.10 rules 1-3).
 extern "C" int shn_abundance_classes(shn_ctx* ctx, const uint8_t* text, const uint64_t* t_off, uint64_t n_tr, const shn_reads* r1, const shn_reads* r2,
@@ -317,96 +428,18 @@ extern "C" int shn_abundance_classes(shn_ctx* ctx, const uint8_t* text, const ui
   if (r1->n_reads != r2->n_reads) return shn_fail(SHN_ERR_ARG, fn + ": the two read sets are not mates of each other (different sizes)");
   if (max_span > ABD_MAX_SPAN) return shn_fail(SHN_ERR_ARG, fn + ": max_span " + std::to_string(max_span) + " above the " + std::to_string(ABD_MAX_SPAN) +
                                                                 " bins the span histogram holds");
-  if (n_tr >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many transcripts");
-  const uint64_t n_pairs = r1->n_reads;
-  if (n_pairs >= 0xFFFFFFFEULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many read pairs in one call");
-  std::vector<uint64_t> rec_off;
-  if (int rc = ffp_record_offsets(fn, t_off, n_tr, &rec_off)) return rc;
-  const uint64_t total = t_off[n_tr], n_rec = rec_off[n_tr];
-  if (total >= 0xFFFFFF00ULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": more than 2^32 transcript bases in one call");
-  shn_abundance* R = new shn_abundance();
-  R->n_tr = n_tr; R->n_frag = n_pairs;
-  R->hist.assign((size_t)max_span + 1, 0);
-  R->class_off.assign(1, 0);
-  struct Guard { shn_abundance* p; ~Guard() { delete p; } } guard{R};
-  auto done = [&]() { *out = R; guard.p = nullptr; return SHN_OK; };
-  if (n_rec == 0 || n_pairs == 0) return done();
-  SHN_ENTER(ctx);
-  shn_stage_begin(ctx);
-  hipStream_t s = ctx->stream;
-  ShnDevBufs bufs(s);
-
-  // ---- index (all transcripts in partition 0)
-  FfpIndex I;
-  uint64_t n_tw = 0;
-  {
-    std::vector<uint32_t> t_part(n_tr, 0);
-    int rc = ffp_index_build(fn, ctx, bufs, T_ABD_INDEX, text, t_off, t_part.data(), n_tr, 1, rec_off, &I, &n_tw);
-    if (rc) return rc;
-  }
-
-  // ---- map: minimum cost + placements per fragment + span histogram, scan, lists
-  uint32_t *d_best = nullptr, *d_cnt = nullptr, *d_flag = nullptr, *d_ids = nullptr, *d_nuniq = nullptr, *d_frag = nullptr, *d_frag_tmp = nullptr;
-  uint64_t *d_off = nullptr, *d_key = nullptr, *d_key_tmp = nullptr;
-  unsigned long long *d_hist = nullptr, *d_mapped = nullptr;
   const uint64_t n_bins = (uint64_t)max_span + 1;
-  HIP_TRY(bufs.get(&d_best, n_pairs * 4));
-  HIP_TRY(bufs.get(&d_cnt, n_pairs * 4));
-  HIP_TRY(bufs.get(&d_flag, 4));
-  HIP_TRY(bufs.get(&d_off, (n_pairs + 1) * 8));
-  HIP_TRY(bufs.get(&d_hist, n_bins * 8));
-  HIP_TRY(bufs.get(&d_mapped, 8));
-  HIP_TRY(hipMemsetAsync(d_flag, 0, 4, s));
-  HIP_TRY(hipMemsetAsync(d_hist, 0, n_bins * 8, s));
-  HIP_TRY(hipMemsetAsync(d_mapped, 0, 8, s));
-  FfpSet A, B;
-  uint64_t rc_bytes = 0, n_place = 0;
-  const uint32_t grid = (uint32_t)cdiv(n_pairs, FFP_BLOCK);
-  const uint64_t per_pair = (r1->n_words + r2->n_words) * 8 / n_pairs * (strand_specific ? 1 : 2);
-  {
-    TimerRegion treg(ctx, T_ABD_MAP);
-    int rc = ffp_set(ctx, bufs, r1, !strand_specific, &A, &rc_bytes);
-    if (!rc) rc = ffp_set(ctx, bufs, r2, true, &B, &rc_bytes);
-    if (rc) return rc;
-    // bytes: both mates of every fragment in each orientation used (2 bits a base), minimum cost and count written (8 B); the index
-    // and the text are re-read from the caches and priced once; a block's non-empty bins (at most 8 B each, not priced); what the
-    // reverse complements cost is added above
-    treg.bytes(rc_bytes + n_pairs * (per_pair + 8) + n_rec * 12 + n_tw * 8);
-    hipLaunchKernelGGL(abd_count_kernel, dim3(grid), dim3(FFP_BLOCK), n_bins * 4, s, I, A, B, n_pairs, strand_specific ? 1 : 0, max_span, d_best, d_cnt,
-                       d_hist, d_mapped, d_flag);
-    // the scan of the numbers: a count read, an offset written (12 B a fragment)
-    treg.bytes(n_pairs * 12);
-    rc = shn_device_scan_u32(ctx, d_cnt, n_pairs, d_off, &n_place);             // (synchronises)
-    if (rc) return rc;
-  }
-  uint32_t flag = 0;
-  unsigned long long mapped = 0;
-  HIP_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(&mapped, d_mapped, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(R->hist.data(), d_hist, n_bins * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(hipGetLastError());
-  if (flag) return shn_fail(SHN_ERR_OVERFLOW, fn + ": a fragment has 2^32 or more placements of its minimum cost");
-  if (n_place >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": " + std::to_string(n_place) + " placements in one call (2^32 - 1 at most)");
-  R->mapped = mapped;
-  if (mapped == 0) return done();
-  HIP_TRY(bufs.get(&d_ids, (n_place + 1) * 4));
-  HIP_TRY(bufs.get(&d_nuniq, n_pairs * 4));
-  HIP_TRY(bufs.get(&d_key, (n_pairs + 1) * 8));
-  HIP_TRY(bufs.get(&d_key_tmp, (n_pairs + 1) * 8));
-  HIP_TRY(bufs.get(&d_frag, (n_pairs + 1) * 4));
-  HIP_TRY(bufs.get(&d_frag_tmp, (n_pairs + 1) * 4));
-  {
-    TimerRegion treg(ctx, T_ABD_MAP);
-    // bytes: the mates again, cost and two offsets read (20 B), the ids written, sorted in place and read for the hash (12 B a
-    // placement), count, key and fragment id written (16 B)
-    treg.bytes(n_pairs * (per_pair + 36) + n_place * 12 + n_rec * 12 + n_tw * 8);
-    hipLaunchKernelGGL(abd_fill_kernel, dim3(grid), dim3(FFP_BLOCK), 0, s, I, A, B, n_pairs, strand_specific ? 1 : 0, max_span, d_best, d_off, d_ids,
-                       d_nuniq, d_key, d_frag);
-  }
-  // ---- classes
-  if (int rc = abd_emit_classes(ctx, bufs, n_pairs, mapped, n_place, d_off, d_ids, d_nuniq, d_key, d_key_tmp, d_frag, d_frag_tmp, R)) return rc;
-  return done();
+  return abd_classes_run(
+      fn, ctx, text, t_off, n_tr, r1, r2, strand_specific, n_bins, "read pairs", "a fragment",
+      [&](const AbdMap& M) {
+        hipLaunchKernelGGL(abd_count_kernel, dim3(M.grid), dim3(FFP_BLOCK), n_bins * 4, M.s, M.I, M.A, M.B, M.n, M.ss, max_span, M.best, M.cnt, M.hist, M.mapped,
+                           M.flag);
+      },
+      [&](const AbdMap& M) {
+        hipLaunchKernelGGL(abd_fill_kernel, dim3(M.grid), dim3(FFP_BLOCK), 0, M.s, M.I, M.A, M.B, M.n, M.ss, max_span, M.best, M.off, M.ids, M.nuniq, M.key,
+                           M.frag);
+      },
+      out);
 }
 
 // Classes of the single reads of one resident set on the transcripts (`kallisto quant --single`, filter_kallisto.py:25, replaced by
@@ -415,89 +448,17 @@ extern "C" int shn_abundance_classes_single(shn_ctx* ctx, const uint8_t* text, c
                                             shn_abundance** out) {
   const std::string fn("shn_abundance_classes_single");
   if (!ctx || !r || !t_off || !out || (n_tr && !text)) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
-  if (n_tr >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many transcripts");
-  const uint64_t n_reads = r->n_reads;
-  if (n_reads >= 0xFFFFFFFEULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many reads in one call");
-  std::vector<uint64_t> rec_off;
-  if (int rc = ffp_record_offsets(fn, t_off, n_tr, &rec_off)) return rc;
-  const uint64_t total = t_off[n_tr], n_rec = rec_off[n_tr];
-  if (total >= 0xFFFFFF00ULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": more than 2^32 transcript bases in one call");
-  shn_abundance* R = new shn_abundance();
-  R->n_tr = n_tr; R->n_frag = n_reads;
-  R->class_off.assign(1, 0);
-  struct Guard { shn_abundance* p; ~Guard() { delete p; } } guard{R};
-  auto done = [&]() { *out = R; guard.p = nullptr; return SHN_OK; };
-  if (n_rec == 0 || n_reads == 0) return done();
-  SHN_ENTER(ctx);
-  shn_stage_begin(ctx);
-  hipStream_t s = ctx->stream;
-  ShnDevBufs bufs(s);
-
-  // ---- index (all transcripts in partition 0)
-  FfpIndex I;
-  uint64_t n_tw = 0;
-  {
-    std::vector<uint32_t> t_part(n_tr, 0);
-    int rc = ffp_index_build(fn, ctx, bufs, T_ABD_INDEX, text, t_off, t_part.data(), n_tr, 1, rec_off, &I, &n_tw);
-    if (rc) return rc;
-  }
-
-  // ---- map: minimum cost + placements per read, scan, lists
-  uint32_t *d_best = nullptr, *d_cnt = nullptr, *d_flag = nullptr, *d_ids = nullptr, *d_nuniq = nullptr, *d_frag = nullptr, *d_frag_tmp = nullptr;
-  uint64_t *d_off = nullptr, *d_key = nullptr, *d_key_tmp = nullptr;
-  unsigned long long* d_mapped = nullptr;
-  HIP_TRY(bufs.get(&d_best, n_reads * 4));
-  HIP_TRY(bufs.get(&d_cnt, n_reads * 4));
-  HIP_TRY(bufs.get(&d_flag, 4));
-  HIP_TRY(bufs.get(&d_off, (n_reads + 1) * 8));
-  HIP_TRY(bufs.get(&d_mapped, 8));
-  HIP_TRY(hipMemsetAsync(d_flag, 0, 4, s));
-  HIP_TRY(hipMemsetAsync(d_mapped, 0, 8, s));
-  FfpSet A;
-  uint64_t rc_bytes = 0, n_place = 0;
-  const uint32_t grid = (uint32_t)cdiv(n_reads, FFP_BLOCK);
-  const uint64_t per_read = r->n_words * 8 / n_reads * (strand_specific ? 1 : 2);
-  {
-    TimerRegion treg(ctx, T_ABD_MAP);
-    int rc = ffp_set(ctx, bufs, r, !strand_specific, &A, &rc_bytes);
-    if (rc) return rc;
-    // bytes: every read in each orientation used (2 bits a base), minimum cost and count written (8 B); the index and the text are
-    // re-read from the caches and priced once; what the reverse complement cost is added above
-    treg.bytes(rc_bytes + n_reads * (per_read + 8) + n_rec * 12 + n_tw * 8);
-    hipLaunchKernelGGL(abd_count_single_kernel, dim3(grid), dim3(FFP_BLOCK), 0, s, I, A, n_reads, strand_specific ? 1 : 0, d_best, d_cnt, d_mapped, d_flag);
-    // the scan of the numbers: a count read, an offset written (12 B a read)
-    treg.bytes(n_reads * 12);
-    rc = shn_device_scan_u32(ctx, d_cnt, n_reads, d_off, &n_place);             // (synchronises)
-    if (rc) return rc;
-  }
-  uint32_t flag = 0;
-  unsigned long long mapped = 0;
-  HIP_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(&mapped, d_mapped, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(hipGetLastError());
-  if (flag) return shn_fail(SHN_ERR_OVERFLOW, fn + ": a read has 2^32 or more placements of its minimum cost");
-  if (n_place >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": " + std::to_string(n_place) + " placements in one call (2^32 - 1 at most)");
-  R->mapped = mapped;
-  if (mapped == 0) return done();
-  HIP_TRY(bufs.get(&d_ids, (n_place + 1) * 4));
-  HIP_TRY(bufs.get(&d_nuniq, n_reads * 4));
-  HIP_TRY(bufs.get(&d_key, (n_reads + 1) * 8));
-  HIP_TRY(bufs.get(&d_key_tmp, (n_reads + 1) * 8));
-  HIP_TRY(bufs.get(&d_frag, (n_reads + 1) * 4));
-  HIP_TRY(bufs.get(&d_frag_tmp, (n_reads + 1) * 4));
-  {
-    TimerRegion treg(ctx, T_ABD_MAP);
-    // bytes: the reads again, cost and two offsets read (20 B), the ids written, sorted in place and read for the hash (12 B a
-    // placement), count, key and read id written (16 B)
-    treg.bytes(n_reads * (per_read + 36) + n_place * 12 + n_rec * 12 + n_tw * 8);
-    hipLaunchKernelGGL(abd_fill_single_kernel, dim3(grid), dim3(FFP_BLOCK), 0, s, I, A, n_reads, strand_specific ? 1 : 0, d_best, d_off, d_ids, d_nuniq,
-                       d_key, d_frag);
-  }
-  // ---- classes
-  if (int rc = abd_emit_classes(ctx, bufs, n_reads, mapped, n_place, d_off, d_ids, d_nuniq, d_key, d_key_tmp, d_frag, d_frag_tmp, R)) return rc;
-  return done();
+  return abd_classes_run(
+      fn, ctx, text, t_off, n_tr, r, nullptr, strand_specific, 0, "reads", "a read",
+      [](const AbdMap& M) {
+        hipLaunchKernelGGL(abd_count_single_kernel, dim3(M.grid), dim3(FFP_BLOCK), 0, M.s, M.I, M.A, M.n, M.ss, M.best, M.cnt, M.mapped, M.flag);
+      },
+      [](const AbdMap& M) {
+        hipLaunchKernelGGL(abd_fill_single_kernel, dim3(M.grid), dim3(FFP_BLOCK), 0, M.s, M.I, M.A, M.n, M.ss, M.best, M.off, M.ids, M.nuniq, M.key, M.frag);
+      },
+      out);
 }
+
 
 extern "C" int shn_abundance_sizes(const shn_abundance* a, uint64_t* sizes) {
   if (!a || !sizes) return shn_fail(SHN_ERR_ARG, "shn_abundance_sizes: NULL argument");
@@ -518,6 +479,10 @@ extern "C" int shn_abundance_export(const shn_abundance* a, uint64_t* class_off,
 extern "C" void shn_abundance_destroy(shn_abundance* a) { delete a; }
 
 // ------------------------------------------------------------------------------------------------------------------------ EM
+// DESIGN.md 3.10 rule 4.  The refusals (abd_em_check) and the classes on the device with their transposition (abd_em_setup) are shared
+// by shn_abundance_em -- one count vector, kernels of its own: abd_em_* -- and the batched EM of the bootstrap replicates (DESIGN.md
+// 3.14 rule 2: abd_emb_*, the same loops with a slot index).  tests/golden/abundance_em_bits.json pins both to the same bits.
+
 // the sum of a wave's partial sums in lane 0: strides 32, 16, 8, 4, 2, 1, lane l takes lane l + stride
 __device__ __forceinline__ double abd_wave_sum(double x) {
   for (int off = 32; off; off >>= 1) x += __shfl_down(x, off, 64);
@@ -540,6 +505,72 @@ __global__ void abd_transpose_kernel(uint64_t n_entries, uint64_t m, const uint6
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t < n_entries) tr_cls[t] = cls[val[t]];
   if (t <= m) tr_off[t] = shn_lower_bound(key, n_entries, t);
+}
+
+// the refusals every EM entry point shares, under the caller's name
+static int abd_em_check(const std::string& fn, const uint64_t* class_off, const uint32_t* members, uint64_t n_classes, const double* eff, uint64_t m) {
+  if (m == 0) return shn_fail(SHN_ERR_ARG, fn + ": no transcripts (m is 0)");
+  if (!class_off || !eff) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
+  if (m >= 0xFFFFFFFFULL || n_classes >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many transcripts or classes");
+  if (class_off[0] != 0) return shn_fail(SHN_ERR_ARG, fn + ": class_off[0] is not 0");
+  for (uint64_t c = 0; c < n_classes; c++)
+    if (class_off[c + 1] < class_off[c]) return shn_fail(SHN_ERR_ARG, fn + ": class_off not monotone");
+  const uint64_t n_entries = class_off[n_classes];
+  if (n_entries >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many class members");
+  if (n_entries && !members) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
+  for (uint64_t e = 0; e < n_entries; e++)
+    if (members[e] >= m) return shn_fail(SHN_ERR_ARG, fn + ": a class names transcript " + std::to_string(members[e]) + " of " + std::to_string(m));
+  for (uint64_t j = 0; j < m; j++)
+    if (!(eff[j] > 0.0)) return shn_fail(SHN_ERR_ARG, fn + ": eff of transcript " + std::to_string(j) + " is not above 0");
+  return SHN_OK;
+}
+
+// the classes, their transposition and eff on the device: what every replicate shares
+struct AbdEmDev {
+  uint64_t n_classes = 0, n_entries = 0, m = 0;
+  uint64_t *coff = nullptr, *troff = nullptr;
+  uint32_t *mem = nullptr, *trcls = nullptr;
+  double* eff = nullptr;
+};
+
+// timer: the slot the caller reports under, T_ABD_EM or T_ABD_EM_BATCH; then(region): what the caller launches in the same region
+template <class Then>
+static int abd_em_setup(shn_ctx* ctx, ShnDevBufs& bufs, int timer, const uint64_t* class_off, const uint32_t* members, uint64_t n_classes,
+                        const double* eff, uint64_t m, AbdEmDev* E, Then&& then) {
+  hipStream_t s = ctx->stream;
+  const uint64_t n_entries = class_off[n_classes];
+  E->n_classes = n_classes; E->n_entries = n_entries; E->m = m;
+  uint64_t *d_key = nullptr, *d_key_tmp = nullptr;
+  uint32_t *d_val = nullptr, *d_val_tmp = nullptr, *d_cls = nullptr;
+  HIP_TRY(bufs.get(&E->coff, (n_classes + 1) * 8));
+  HIP_TRY(bufs.get(&E->mem, (n_entries + 1) * 4));
+  HIP_TRY(bufs.get(&E->eff, m * 8));
+  HIP_TRY(bufs.get(&E->troff, (m + 1) * 8));
+  HIP_TRY(bufs.get(&E->trcls, (n_entries + 1) * 4));
+  HIP_TRY(bufs.get(&d_key, (n_entries + 1) * 8));
+  HIP_TRY(bufs.get(&d_key_tmp, (n_entries + 1) * 8));
+  HIP_TRY(bufs.get(&d_val, (n_entries + 1) * 4));
+  HIP_TRY(bufs.get(&d_val_tmp, (n_entries + 1) * 4));
+  HIP_TRY(bufs.get(&d_cls, (n_entries + 1) * 4));
+  HIP_TRY(hipMemcpyAsync(E->coff, class_off, (n_classes + 1) * 8, hipMemcpyHostToDevice, s));
+  if (n_entries) HIP_TRY(hipMemcpyAsync(E->mem, members, n_entries * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(E->eff, eff, m * 8, hipMemcpyHostToDevice, s));
+  int key_bits = 1;
+  while (key_bits < 32 && (m >> key_bits)) key_bits++;
+  TimerRegion treg(ctx, timer);
+  // bytes, the transposition (once for all replicates): an entry read (4 B + its class's offsets from the caches) and written as key,
+  // value, class (16 B), every sort pass reads and writes the pairs (24 B), the sorted entry's class gathered and written (12 B); 8 B a
+  // transcript offset
+  treg.bytes(n_entries * (32 + 24 * (uint64_t)((key_bits + 7) / 8)) + (m + 1) * 8);
+  if (n_entries) {
+    hipLaunchKernelGGL(abd_entries_kernel, dim3((uint32_t)cdiv(n_entries, 256)), dim3(256), 0, s, n_entries, n_classes, E->coff, E->mem, d_key, d_val, d_cls);
+    int rc = shn_sort_pairs(ctx, d_key, d_val, d_key_tmp, d_val_tmp, n_entries, 0, key_bits);
+    if (rc) return rc;
+  }
+  const uint64_t n_t = n_entries > m + 1 ? n_entries : m + 1;
+  hipLaunchKernelGGL(abd_transpose_kernel, dim3((uint32_t)cdiv(n_t, 256)), dim3(256), 0, s, n_entries, m, d_key, d_val, d_cls, E->troff, E->trcls);
+  then(treg);
+  return SHN_OK;
 }
 
 __global__ void abd_em_init_kernel(uint64_t m, const double* __restrict__ eff, double* __restrict__ alpha, double* __restrict__ w) {
@@ -592,64 +623,29 @@ __global__ __launch_bounds__(FFP_BLOCK) void abd_em_alpha_kernel(uint64_t m, con
 extern "C" int shn_abundance_em(shn_ctx* ctx, const uint64_t* class_off, const uint32_t* members, const uint64_t* n_c, uint64_t n_classes,
                                 const double* eff, uint64_t m, double* alpha, uint32_t* rounds) {
   const std::string fn("shn_abundance_em");
-  if (m == 0) return shn_fail(SHN_ERR_ARG, fn + ": no transcripts (m is 0)");
-  if (!ctx || !class_off || !eff || !alpha || !rounds || (n_classes && !n_c)) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
-  if (m >= 0xFFFFFFFFULL || n_classes >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many transcripts or classes");
-  if (class_off[0] != 0) return shn_fail(SHN_ERR_ARG, fn + ": class_off[0] is not 0");
-  for (uint64_t c = 0; c < n_classes; c++)
-    if (class_off[c + 1] < class_off[c]) return shn_fail(SHN_ERR_ARG, fn + ": class_off not monotone");
-  const uint64_t n_entries = class_off[n_classes];
-  if (n_entries >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many class members");
-  if (n_entries && !members) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
-  for (uint64_t e = 0; e < n_entries; e++)
-    if (members[e] >= m) return shn_fail(SHN_ERR_ARG, fn + ": a class names transcript " + std::to_string(members[e]) + " of " + std::to_string(m));
-  for (uint64_t j = 0; j < m; j++)
-    if (!(eff[j] > 0.0)) return shn_fail(SHN_ERR_ARG, fn + ": eff of transcript " + std::to_string(j) + " is not above 0");
+  if (int rc = abd_em_check(fn, class_off, members, n_classes, eff, m)) return rc;
+  if (!ctx || !alpha || !rounds || (n_classes && !n_c)) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
   std::vector<double> ncd(n_classes);
   for (uint64_t c = 0; c < n_classes; c++) ncd[c] = (double)n_c[c];
   SHN_ENTER(ctx);
   shn_stage_begin(ctx);
   hipStream_t s = ctx->stream;
   ShnDevBufs bufs(s);
-  uint64_t *d_coff = nullptr, *d_key = nullptr, *d_key_tmp = nullptr, *d_troff = nullptr;
-  uint32_t *d_mem = nullptr, *d_val = nullptr, *d_val_tmp = nullptr, *d_cls = nullptr, *d_trcls = nullptr, *d_moved = nullptr;
-  double *d_nc = nullptr, *d_eff = nullptr, *d_alpha = nullptr, *d_w = nullptr, *d_d = nullptr;
-  HIP_TRY(bufs.get(&d_coff, (n_classes + 1) * 8));
-  HIP_TRY(bufs.get(&d_mem, (n_entries + 1) * 4));
+  uint32_t* d_moved = nullptr;
+  double *d_nc = nullptr, *d_alpha = nullptr, *d_w = nullptr, *d_d = nullptr;
   HIP_TRY(bufs.get(&d_nc, (n_classes + 1) * 8));
-  HIP_TRY(bufs.get(&d_eff, m * 8));
   HIP_TRY(bufs.get(&d_alpha, m * 8));
   HIP_TRY(bufs.get(&d_w, m * 8));
   HIP_TRY(bufs.get(&d_d, (n_classes + 1) * 8));
-  HIP_TRY(bufs.get(&d_key, (n_entries + 1) * 8));
-  HIP_TRY(bufs.get(&d_key_tmp, (n_entries + 1) * 8));
-  HIP_TRY(bufs.get(&d_val, (n_entries + 1) * 4));
-  HIP_TRY(bufs.get(&d_val_tmp, (n_entries + 1) * 4));
-  HIP_TRY(bufs.get(&d_cls, (n_entries + 1) * 4));
-  HIP_TRY(bufs.get(&d_trcls, (n_entries + 1) * 4));
-  HIP_TRY(bufs.get(&d_troff, (m + 1) * 8));
   HIP_TRY(bufs.get(&d_moved, 4));
-  HIP_TRY(hipMemcpyAsync(d_coff, class_off, (n_classes + 1) * 8, hipMemcpyHostToDevice, s));
-  if (n_entries) HIP_TRY(hipMemcpyAsync(d_mem, members, n_entries * 4, hipMemcpyHostToDevice, s));
   if (n_classes) HIP_TRY(hipMemcpyAsync(d_nc, ncd.data(), n_classes * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_eff, eff, m * 8, hipMemcpyHostToDevice, s));
-  int key_bits = 1;
-  while (key_bits < 32 && (m >> key_bits)) key_bits++;
-  {
-    TimerRegion treg(ctx, T_ABD_EM);
-    // bytes, transposition: an entry read (4 B + its class's offsets from the caches) and written as key, value, class (16 B), every sort
-    // pass reads and writes the pairs (24 B), the sorted entry's class gathered and written (12 B); 8 B a transcript offset; 24 B a
-    // transcript for alpha, w, eff
-    treg.bytes(n_entries * (32 + 24 * (uint64_t)((key_bits + 7) / 8)) + (m + 1) * 8 + m * 24);
-    if (n_entries) {
-      hipLaunchKernelGGL(abd_entries_kernel, dim3((uint32_t)cdiv(n_entries, 256)), dim3(256), 0, s, n_entries, n_classes, d_coff, d_mem, d_key, d_val, d_cls);
-      int rc = shn_sort_pairs(ctx, d_key, d_val, d_key_tmp, d_val_tmp, n_entries, 0, key_bits);
-      if (rc) return rc;
-    }
-    const uint64_t n_t = n_entries > m + 1 ? n_entries : m + 1;
-    hipLaunchKernelGGL(abd_transpose_kernel, dim3((uint32_t)cdiv(n_t, 256)), dim3(256), 0, s, n_entries, m, d_key, d_val, d_cls, d_troff, d_trcls);
-    hipLaunchKernelGGL(abd_em_init_kernel, dim3((uint32_t)cdiv(m, 256)), dim3(256), 0, s, m, d_eff, d_alpha, d_w);
-  }
+  AbdEmDev E;
+  int rc = abd_em_setup(ctx, bufs, T_ABD_EM, class_off, members, n_classes, eff, m, &E, [&](TimerRegion& treg) {
+    treg.bytes(m * 24);                                       // alpha and w written, eff read
+    hipLaunchKernelGGL(abd_em_init_kernel, dim3((uint32_t)cdiv(m, 256)), dim3(256), 0, s, m, E.eff, d_alpha, d_w);
+  });
+  if (rc) return rc;
+  const uint64_t n_entries = E.n_entries;
   const uint32_t waves = FFP_BLOCK / 64;
   uint32_t round = 0;
   for (;;) {                                                  // a block of 50 rounds, the last of them with the test; one read of the flag
@@ -661,8 +657,8 @@ extern "C" int shn_abundance_em(shn_ctx* ctx, const uint64_t* class_off, const u
       treg.bytes(50 * (n_classes * 24 + n_entries * 32 + m * 56));
       for (int k = 0; k < 50; k++) {
         if (n_classes)
-          hipLaunchKernelGGL(abd_em_d_kernel, dim3((uint32_t)cdiv(n_classes, waves)), dim3(FFP_BLOCK), 0, s, n_classes, d_coff, d_mem, d_w, d_d);
-        hipLaunchKernelGGL(abd_em_alpha_kernel, dim3((uint32_t)cdiv(m, waves)), dim3(FFP_BLOCK), 0, s, m, d_troff, d_trcls, d_nc, d_d, d_eff, d_alpha, d_w,
+          hipLaunchKernelGGL(abd_em_d_kernel, dim3((uint32_t)cdiv(n_classes, waves)), dim3(FFP_BLOCK), 0, s, n_classes, E.coff, E.mem, d_w, d_d);
+        hipLaunchKernelGGL(abd_em_alpha_kernel, dim3((uint32_t)cdiv(m, waves)), dim3(FFP_BLOCK), 0, s, m, E.troff, E.trcls, d_nc, d_d, E.eff, d_alpha, d_w,
                            k == 49 ? 1 : 0, d_moved);
       }
     }
@@ -817,67 +813,6 @@ extern "C" int shn_abundance_resample(shn_ctx* ctx, const uint64_t* n_c, uint64_
 }
 
 // ---- the batched EM
-// the refusals of shn_abundance_em, under the caller's name
-static int abd_em_check(const std::string& fn, const uint64_t* class_off, const uint32_t* members, uint64_t n_classes, const double* eff, uint64_t m) {
-  if (m == 0) return shn_fail(SHN_ERR_ARG, fn + ": no transcripts (m is 0)");
-  if (!class_off || !eff) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
-  if (m >= 0xFFFFFFFFULL || n_classes >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many transcripts or classes");
-  if (class_off[0] != 0) return shn_fail(SHN_ERR_ARG, fn + ": class_off[0] is not 0");
-  for (uint64_t c = 0; c < n_classes; c++)
-    if (class_off[c + 1] < class_off[c]) return shn_fail(SHN_ERR_ARG, fn + ": class_off not monotone");
-  const uint64_t n_entries = class_off[n_classes];
-  if (n_entries >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many class members");
-  if (n_entries && !members) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
-  for (uint64_t e = 0; e < n_entries; e++)
-    if (members[e] >= m) return shn_fail(SHN_ERR_ARG, fn + ": a class names transcript " + std::to_string(members[e]) + " of " + std::to_string(m));
-  for (uint64_t j = 0; j < m; j++)
-    if (!(eff[j] > 0.0)) return shn_fail(SHN_ERR_ARG, fn + ": eff of transcript " + std::to_string(j) + " is not above 0");
-  return SHN_OK;
-}
-
-// the classes, their transposition and eff on the device: what every replicate shares
-struct AbdEmDev {
-  uint64_t n_classes = 0, n_entries = 0, m = 0;
-  uint64_t *coff = nullptr, *troff = nullptr;
-  uint32_t *mem = nullptr, *trcls = nullptr;
-  double* eff = nullptr;
-};
-
-static int abd_em_setup(shn_ctx* ctx, ShnDevBufs& bufs, const uint64_t* class_off, const uint32_t* members, uint64_t n_classes, const double* eff,
-                        uint64_t m, AbdEmDev* E) {
-  hipStream_t s = ctx->stream;
-  const uint64_t n_entries = class_off[n_classes];
-  E->n_classes = n_classes; E->n_entries = n_entries; E->m = m;
-  uint64_t *d_key = nullptr, *d_key_tmp = nullptr;
-  uint32_t *d_val = nullptr, *d_val_tmp = nullptr, *d_cls = nullptr;
-  HIP_TRY(bufs.get(&E->coff, (n_classes + 1) * 8));
-  HIP_TRY(bufs.get(&E->mem, (n_entries + 1) * 4));
-  HIP_TRY(bufs.get(&E->eff, m * 8));
-  HIP_TRY(bufs.get(&E->troff, (m + 1) * 8));
-  HIP_TRY(bufs.get(&E->trcls, (n_entries + 1) * 4));
-  HIP_TRY(bufs.get(&d_key, (n_entries + 1) * 8));
-  HIP_TRY(bufs.get(&d_key_tmp, (n_entries + 1) * 8));
-  HIP_TRY(bufs.get(&d_val, (n_entries + 1) * 4));
-  HIP_TRY(bufs.get(&d_val_tmp, (n_entries + 1) * 4));
-  HIP_TRY(bufs.get(&d_cls, (n_entries + 1) * 4));
-  HIP_TRY(hipMemcpyAsync(E->coff, class_off, (n_classes + 1) * 8, hipMemcpyHostToDevice, s));
-  if (n_entries) HIP_TRY(hipMemcpyAsync(E->mem, members, n_entries * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(E->eff, eff, m * 8, hipMemcpyHostToDevice, s));
-  int key_bits = 1;
-  while (key_bits < 32 && (m >> key_bits)) key_bits++;
-  TimerRegion treg(ctx, T_ABD_EM_BATCH);
-  // bytes, the transposition (once for all replicates): as shn_abundance_em prices it, without the per-replicate alpha and w
-  treg.bytes(n_entries * (32 + 24 * (uint64_t)((key_bits + 7) / 8)) + (m + 1) * 8);
-  if (n_entries) {
-    hipLaunchKernelGGL(abd_entries_kernel, dim3((uint32_t)cdiv(n_entries, 256)), dim3(256), 0, s, n_entries, n_classes, E->coff, E->mem, d_key, d_val, d_cls);
-    int rc = shn_sort_pairs(ctx, d_key, d_val, d_key_tmp, d_val_tmp, n_entries, 0, key_bits);
-    if (rc) return rc;
-  }
-  const uint64_t n_t = n_entries > m + 1 ? n_entries : m + 1;
-  hipLaunchKernelGGL(abd_transpose_kernel, dim3((uint32_t)cdiv(n_t, 256)), dim3(256), 0, s, n_entries, m, d_key, d_val, d_cls, E->troff, E->trcls);
-  return SHN_OK;
-}
-
 // slot s < n_slots: the counts of replicate b0 + s as doubles, alpha = 1 / m, w = alpha / eff
 __global__ void abd_emb_init_kernel(uint64_t n_slots, uint64_t m, uint64_t n_classes, const unsigned long long* __restrict__ counts,
                                     const double* __restrict__ eff, double* __restrict__ ncd, double* __restrict__ alpha, double* __restrict__ w) {
@@ -1022,7 +957,7 @@ extern "C" int shn_abundance_em_batch(shn_ctx* ctx, const uint64_t* class_off, c
   hipStream_t s = ctx->stream;
   ShnDevBufs bufs(s);
   AbdEmDev E;
-  if (int rc = abd_em_setup(ctx, bufs, class_off, members, n_classes, eff, m, &E)) return rc;
+  if (int rc = abd_em_setup(ctx, bufs, T_ABD_EM_BATCH, class_off, members, n_classes, eff, m, &E, [](TimerRegion&) {})) return rc;
   unsigned long long* d_counts = nullptr;
   HIP_TRY(bufs.get(&d_counts, (B * n_classes + 1) * 8));
   if (n_classes) HIP_TRY(hipMemcpyAsync(d_counts, n_c, B * n_classes * 8, hipMemcpyHostToDevice, s));
@@ -1043,7 +978,7 @@ extern "C" int shn_abundance_bootstrap(shn_ctx* ctx, const uint64_t* class_off, 
   hipStream_t s = ctx->stream;
   ShnDevBufs bufs(s);
   AbdEmDev E;
-  if (int rc = abd_em_setup(ctx, bufs, class_off, members, n_classes, eff, m, &E)) return rc;
+  if (int rc = abd_em_setup(ctx, bufs, T_ABD_EM_BATCH, class_off, members, n_classes, eff, m, &E, [](TimerRegion&) {})) return rc;
   unsigned long long* d_counts = nullptr;
   HIP_TRY(bufs.get(&d_counts, (B * n_classes + 1) * 8));
   if (int rc = abd_resample_run(ctx, bufs, n_c, n_classes, N, B, seed, d_counts)) return rc;

@@ -16,6 +16,7 @@ The rule, for final transcripts T_0..T_{m-1} and N read pairs:
      |alpha'_j - alpha_j| > 1e-2 alpha'_j; stop after 10,000 rounds; alpha_j < 1e-8 -> 0.
   5. cov_j = alpha_j / eff_j * L, L = (bases of reads_1 + bases of reads_2) / N; kept iff cov_j >= cutoff.
 """
+import functools
 import numpy as np
 import filter_fp_cases as fc
 
@@ -222,3 +223,37 @@ def em_cases():
         rng = np.random.Generator(np.random.PCG64(seed + 1000))
         out["random, %d transcripts" % m] = (lists + [[j] for j in range(m)], n_c + [int(x) for x in rng.integers(20, 400, m)], eff, m)
     return out
+
+
+def union_case():
+    """"shared pair", "a class of 65" and "random, 40 transcripts" side by side on 2 + 70 + 40 transcripts; rows: the counts of the first
+    alone, of the second alone, of the third alone, of all three, and none at all"""
+    cases = em_cases()
+    lists, eff, blocks, base = [], [], [], 0
+    for name in ("shared pair", "a class of 65", "random, 40 transcripts"):
+        L, n_c, e, m = cases[name]
+        lists += [[j + base for j in M] for M in L]
+        eff += [float(x) for x in e]
+        blocks.append([int(x) for x in n_c])
+        base += m
+    z = [[0] * len(b) for b in blocks]
+    rows = [blocks[0] + z[1] + z[2], z[0] + blocks[1] + z[2], z[0] + z[1] + blocks[2], blocks[0] + blocks[1] + blocks[2], z[0] + z[1] + z[2]]
+    return lists, np.array(rows, dtype=np.uint64), np.array(eff), base
+
+
+@functools.lru_cache(maxsize=None)
+def em_golden_case(name):
+    """the rows tests/golden/abundance_em_bits.json records for `name` (an em_cases() name, or "union"): (class lists, count matrix, eff,
+    labels) -- the case's own n_c ("n_c") and the 65 bootstrap rows of bootstrap_cases.brute_counts_np(n_c, 65, 7) ("b0" ..); "union":
+    union_case()'s five rows ("u0" ..)"""
+    import bootstrap_cases as bc
+    if name == "union":
+        lists, matrix, eff, _m = union_case()
+        return lists, matrix, eff, ["u%d" % k for k in range(len(matrix))]
+    lists, n_c, eff, _m = em_cases()[name]
+    matrix = np.concatenate([np.array([n_c], dtype=np.uint64), bc.brute_counts_np(n_c, 65, 7)])
+    return lists, matrix, np.asarray(eff, dtype=np.float64), ["n_c"] + ["b%d" % b for b in range(65)]
+
+
+def em_golden_names():
+    return sorted(em_cases()) + ["union"]

@@ -191,3 +191,15 @@ def test_shared_exon_case_has_the_set_sizes_it_names():
     T, r1, r2, want = ac.shared_exon_case()
     classes, _hist, mapped = ac.brute_classes(ac.brute_fragments(T, r1, r2, True))
     assert {len(C): n for C, n in classes.items()} == want == {65: 5, 64: 4, 2: 3, 1: 6} and mapped == len(r1) - 1
+
+
+def test_em_bits_fixture_covers_every_em_case():
+    """tests/golden/abundance_em_bits.json (the GPU test's reference): every em_cases() entry with its own n_c and 65 bootstrap rows, the
+    union case with its five"""
+    with open(os.path.join(ROOT, "tests", "golden", "abundance_em_bits.json")) as f:
+        cases = json.load(f)["cases"]
+    assert sorted(cases) == sorted(ac.em_golden_names()) == sorted(list(ac.em_cases()) + ["union"])
+    for name, rows in cases.items():
+        assert [r[0] for r in rows] == (["u%d" % k for k in range(5)] if name == "union" else ["n_c"] + ["b%d" % b for b in range(65)]), name
+        assert all(r[1] % 50 == 0 and 50 <= r[1] <= 10000 and len(r[2]) == 64 and int(r[2], 16) >= 0 for r in rows), name
+    assert ac.em_golden_case("union")[3] == [r[0] for r in cases["union"]] and ac.em_golden_case("shared pair")[1].shape == (66, 3)

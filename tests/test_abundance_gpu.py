@@ -2,6 +2,8 @@
 brute force of tests/abundance_cases.py (written from the rule): compatibility sets, span histogram and classes are
 integers and compared exactly; the EM's alpha to a relative 1e-9 (absolute 1e-12) with the rounds used equal; then the flag through
 the command line."""
+import hashlib
+import json
 import os
 import numpy as np
 import pytest
@@ -200,6 +202,35 @@ def test_em_against_the_brute_force(ctx, em_reference, name):
     assert np.all(err <= ATOL + RTOL * np.abs(want))
     again, again_rounds = gpu_em(ctx, lists, n_c, eff)        # determinism: the same call twice, the same bits
     assert again_rounds == got_rounds and got.tobytes() == again.tobytes()
+
+
+@pytest.fixture(scope="module")
+def em_bits():
+    """tests/golden/abundance_em_bits.json: per case and row [label, rounds, SHA-256 of alpha.tobytes()], recorded from abundance.em while
+    the single-replicate EM still had kernels of its own (tests/golden/make_abundance_em_golden.py)"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "abundance_em_bits.json")) as f:
+        return json.load(f)["cases"]
+
+
+@pytest.mark.parametrize("name", ac.em_golden_names())
+def test_em_and_em_batch_give_the_recorded_bits(ctx, em_bits, name):
+    """no tolerance: the one EM there is returns, row by row through em and all rows at once through em_batch (the budget's residency and
+    one replicate at a time), the rounds and the bits recorded before the two were one implementation"""
+    from shannon_amd import abundance
+    lists, matrix, eff, labels = ac.em_golden_case(name)
+    off, mem = ac.csr(lists)
+    want = em_bits[name]
+    assert [w[0] for w in want] == labels
+
+    def rows(alpha, rounds):
+        return [[label, int(r), hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()] for label, a, r in zip(labels, alpha, rounds)]
+    got = [abundance.em(ctx, off, mem, n_c, eff) for n_c in matrix]
+    assert all(a.dtype == np.float64 and a.shape == (len(eff),) for a, _ in got)
+    assert rows([a for a, _ in got], [r for _, r in got]) == want, "em"
+    for max_live in (0, 1):
+        alpha, rounds = abundance.em_batch(ctx, off, mem, matrix, eff, max_live=max_live)
+        assert alpha.dtype == np.float64 and alpha.shape == (len(matrix), len(eff))
+        assert rows(alpha, rounds) == want, "em_batch, max_live %d" % max_live
 
 
 def test_em_closed_form_and_special_rows(ctx):

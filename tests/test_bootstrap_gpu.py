@@ -87,26 +87,10 @@ def test_em_batch_equals_em_per_replicate(ctx, name):
     check_batch(ctx, off, mem, matrix, eff, want, name)
 
 
-def union_case():
-    """"shared pair", "a class of 65" and "random, 40 transcripts" side by side on 2 + 70 + 40 transcripts; rows: the counts of the first
-    alone, of the second alone, of the third alone, of all three, and none at all"""
-    cases = ac.em_cases()
-    lists, eff, blocks, base = [], [], [], 0
-    for name in ("shared pair", "a class of 65", "random, 40 transcripts"):
-        L, n_c, e, m = cases[name]
-        lists += [[j + base for j in M] for M in L]
-        eff += [float(x) for x in e]
-        blocks.append([int(x) for x in n_c])
-        base += m
-    z = [[0] * len(b) for b in blocks]
-    rows = [blocks[0] + z[1] + z[2], z[0] + blocks[1] + z[2], z[0] + z[1] + blocks[2], blocks[0] + blocks[1] + blocks[2], z[0] + z[1] + z[2]]
-    return lists, np.array(rows, dtype=np.uint64), np.array(eff), base
-
-
 def test_em_batch_replicates_that_stop_at_different_rounds(ctx):
     """the replicates leave the launches at their own rounds (DESIGN.md 3.10 records 50, 100 and 150 rounds for the three inputs), one of
     them with all-zero counts, and the ones still running are not disturbed"""
-    lists, matrix, eff, m = union_case()
+    lists, matrix, eff, m = ac.union_case()
     off, mem = ac.csr(lists)
     want = oracle(ctx, off, mem, matrix, eff)
     print("rounds of the hand-made replicates: %s" % want[1].tolist())

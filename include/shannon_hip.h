@@ -494,6 +494,19 @@ int shn_abundance_em_batch(shn_ctx* ctx, const uint64_t* class_off, const uint32
  * counts; counts_out[B][n_classes] may be NULL.  The refusals of both calls above. */
 int shn_abundance_bootstrap(shn_ctx* ctx, const uint64_t* class_off, const uint32_t* members, const uint64_t* n_c, uint64_t n_classes, const double* eff,
                             uint64_t m, uint64_t B, uint64_t seed, uint64_t max_live, double* alpha_out, uint32_t* rounds_out, uint64_t* counts_out);
+/* shn_abundance_merge -- the classes of the union of several read sets from the sets' own classes (a sample in several read files or
+ * on several ranks: python -m shannon_amd.quant).  The input is ONE CSR of weighted lists on HOST arrays: the classes
+ * of all parts one after the other, every list strictly ascending, n_c its weight.  A list's key is the 63-bit hash
+ * shn_abundance_classes gives a fragment with the same list; the lists are sorted by key (stable), a sorted position heads a merged class
+ * iff its LIST differs from its predecessor's, element by element, and a merged class's n_c is the exact 64-bit sum of its lists'
+ * weights.  Integers only.  hash_bits: 63; 1..62 keeps that many low bits of the key, so that a test can make different lists share a
+ * key.  Refused before anything is launched: m == 0, hash_bits outside 1..63, a class_off that is not monotone or does not start at 0,
+ * an empty list, a member >= m, a list that is not strictly ascending (SHN_ERR_ARG); n_lists >= 2^32, weights whose sum does not fit
+ * in 64 bits (SHN_ERR_OVERFLOW).  n_lists == 0 gives 0 classes; a weight of 0 is kept.
+ *   out   a handle read with shn_abundance_sizes / _export / _destroy: transcripts m, fragments = mapped = the sum of the weights,
+ *         classes, members, 0 bins */
+int shn_abundance_merge(shn_ctx* ctx, const uint64_t* class_off, const uint32_t* members, const uint64_t* n_c, uint64_t n_lists, uint64_t m,
+                        uint32_t hash_bits, shn_abundance** out);
 
 /* ---- K-mer seed scans of reads against graph nodes -----------------------------------------------
  * Replace the per-read Python loops of Read.find_bridging_reads (mbgraph.py:88-111) and known_paths

@@ -83,6 +83,7 @@ SIGNATURES = {
     "shn_abundance_resample": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp]),
     "shn_abundance_em_batch": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp]),
     "shn_abundance_bootstrap": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, vp]),
+    "shn_abundance_merge": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, vpp]),
     "shn_lp_solve_batch": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]),
     "shn_lp_set_rule": (C.c_int, [vp, C.c_int]),
     "shn_lp_stats": (C.c_int, [vp, vp, C.c_int]),

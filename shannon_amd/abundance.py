@@ -27,8 +27,15 @@ Bootstrap replicates (quant.py's -b B --seed S; quantify / quant
     bootstrap_summary  mean, sd, min, max per transcript over the replicates' est_counts
     bootstrap_summary_tsv, replicate_table  the texts of bootstrap_summary.tsv and, through abundance_tsv, of bs_abundance_<b>.tsv
 
-`eff_lengths`, `eff_lengths_model`, `abundance_tsv`, `decide`, `bootstrap_summary`, `bootstrap_summary_tsv` and `replicate_table` need
-neither the library nor a GPU.
+Reads in several parts -- the lane files of a sample, the slices of N ranks (quant.py's comma lists and --gpus N):
+
+    list_key           the 63-bit key of a member list, in plain integers
+    merge_classes      the class dicts of the parts -> the classes of all their reads (shn_abundance_merge)
+    quantify_classes   class dicts of parts -> table: merge_classes, then the tail of quantify / quantify_single
+    quantify_parts     resident read sets, one part at a time -> table
+
+`eff_lengths`, `eff_lengths_model`, `abundance_tsv`, `decide`, `bootstrap_summary`, `bootstrap_summary_tsv`, `replicate_table` and
+`list_key` need neither the library nor a GPU.
 """
 import ctypes as C
 import io
@@ -91,6 +98,66 @@ def _export(lib, h):
     finally:
         lib.shn_abundance_destroy(h)
     return {"class_off": class_off, "members": members[:n_entries], "n_c": n_c[:n_classes], "hist": hist, "mapped": mapped, "fragments": n_frag}
+
+
+_M64 = (1 << 64) - 1
+
+
+def _mix(h, v):
+    """abd_mix of csrc/abundance.hip in plain integers"""
+    h ^= (v + 0x9E3779B97F4A7C15) & _M64
+    h ^= h >> 33
+    h = h * 0xFF51AFD7ED558CCD & _M64
+    h ^= h >> 33
+    h = h * 0xC4CEB9FE1A85EC53 & _M64
+    h ^= h >> 33
+    return h
+
+
+def list_key(members):
+    """the 63-bit key of an ascending member list: what abd_finish_list gives a fragment with this list -- the mix of 0
+    and the length, then of every member in order, shifted right by one.  Plain integers: needs neither the library nor a GPU."""
+    members = [int(j) for j in members]
+    h = _mix(0, len(members))
+    for j in members:
+        h = _mix(h, j)
+    return h >> 1
+
+
+def merge_classes(ctx, parts, m, hash_bits=63):
+    """DESIGN.md 3.15 (shn_abundance_merge): the class dicts of P >= 1 read sets on the same m transcripts -> one dict of the same shape,
+    the classes of the union of the reads: the parts' classes as weighted lists, in part order, merged on the device; "hist", "mapped"
+    and "fragments" are the parts' sums.  Parts whose "hist" differ in length (another max_span, pairs beside single reads) are
+    refused.  One part goes through the device too."""
+    from . import _lib
+    parts = list(parts)
+    if not parts:
+        raise ValueError("abundance.merge_classes: no parts")
+    bins = set(len(p["hist"]) for p in parts)
+    if len(bins) != 1:
+        raise ValueError("abundance.merge_classes: the parts' histograms have %s bins: not built with one max_span" % sorted(bins))
+    sizes = [len(p["n_c"]) for p in parts]
+    for p, n in zip(parts, sizes):
+        if len(p["class_off"]) != n + 1 or int(p["class_off"][0]) != 0 or int(p["class_off"][-1]) != len(p["members"]):
+            raise ValueError("abundance.merge_classes: a part's class_off does not fit its n_c and members")
+    n_lists = sum(sizes)
+    class_off = np.zeros(n_lists + 1, dtype=np.uint64)                 # one CSR: every part's offsets rebased behind the parts before it
+    at = base = 0
+    for p, n in zip(parts, sizes):
+        class_off[at + 1:at + n + 1] = np.asarray(p["class_off"][1:], dtype=np.uint64) + np.uint64(base)
+        at, base = at + n, base + len(p["members"])
+    members = np.ascontiguousarray(np.concatenate([np.asarray(p["members"], dtype=np.uint32) for p in parts]))
+    n_c = np.ascontiguousarray(np.concatenate([np.asarray(p["n_c"], dtype=np.uint64) for p in parts]))
+    h = C.c_void_p()
+    lib = _lib.lib()
+    _lib.check(lib.shn_abundance_merge(ctx.h, class_off.ctypes.data, members.ctypes.data if len(members) else None, n_c.ctypes.data if n_lists else None,
+                                       n_lists, int(m), int(hash_bits), C.byref(h)))
+    out = _export(lib, h)
+    hist = np.zeros(bins.pop(), dtype=np.uint64)
+    for p in parts:
+        hist += np.asarray(p["hist"], dtype=np.uint64)
+    out["hist"], out["mapped"], out["fragments"] = hist, sum(int(p["mapped"]) for p in parts), sum(int(p["fragments"]) for p in parts)
+    return out
 
 
 def _eff_from_prefix(lens, cnt, tot):
@@ -324,6 +391,43 @@ def quantify_single(ctx, names, seqs, d, strand_specific, mean=MODEL_MEAN, sd=MO
         eff = eff_lengths_model(lens, mean, sd)
         return classes_single(ctx, seqs, d, strand_specific), eff
     return _quantify("quantify_single", ctx, names, seqs, len(d), np.zeros(0, np.uint64), classes_and_eff, bootstraps, seed)
+
+
+def quantify_classes(ctx, names, seqs, class_parts, paired, mean=MODEL_MEAN, sd=MODEL_SD, bootstraps=None, seed=0, hash_bits=63):
+    """the table of `quantify` (paired) / `quantify_single` from the class dicts of P >= 1 parts of the reads (`classes` / `classes_single`
+    of each part on these transcripts, from this process or from other ranks): merge_classes, then the same tail -- eff_lengths on the
+    summed histogram or eff_lengths_model, em, tpm, the bootstrap columns.  While no two different lists share a key the merged classes
+    are those of the reads in one set, and so is every number of the table.  Adds "parts" and "lists" (the lists that
+    went into the merge)."""
+    class_parts = list(class_parts)
+    if not class_parts:
+        raise ValueError("quantify_classes: no parts")
+
+    def classes_and_eff(lens):
+        eff = None if paired else eff_lengths_model(lens, mean, sd)
+        cl = merge_classes(ctx, class_parts, len(seqs), hash_bits)
+        return cl, (eff_lengths(lens, cl["hist"]) if paired else eff)
+    table = _quantify("quantify_classes", ctx, names, seqs, sum(int(p["fragments"]) for p in class_parts),
+                      np.zeros(len(class_parts[0]["hist"]), np.uint64), classes_and_eff, bootstraps, seed)
+    table["parts"], table["lists"] = len(class_parts), sum(len(p["n_c"]) for p in class_parts)
+    return table
+
+
+def quantify_parts(ctx, names, seqs, parts_of_reads, strand_specific, max_span=MAX_SPAN, mean=MODEL_MEAN, sd=MODEL_SD, bootstraps=None, seed=0):
+    """`quantify` / `quantify_single` for reads that come in P >= 1 parts (the lane files of one sample): parts_of_reads yields (d1, d2)
+    -- mates -- or (d,) -- single reads -- resident sets, one kind throughout; every part's classes are built before the next part is
+    asked for, so a generator may load a part, hand it over and close it: one part is resident at a time.  Then quantify_classes."""
+    class_parts, paired = [], None
+    for sets in parts_of_reads:
+        sets = tuple(sets)
+        if len(sets) not in (1, 2) or (paired is not None and paired != (len(sets) == 2)):
+            raise ValueError("quantify_parts: a part is one read set or two mates, the same for every part")
+        if paired is None:
+            paired = len(sets) == 2
+            if not paired:
+                eff_lengths_model([], mean, sd)                     # (a bad sd is refused before anything runs)
+        class_parts.append(classes(ctx, seqs, sets[0], sets[1], strand_specific, max_span) if paired else classes_single(ctx, seqs, sets[0], strand_specific))
+    return quantify_classes(ctx, names, seqs, class_parts, paired, mean, sd, bootstraps, seed)
 
 
 def abundance_tsv(table):

@@ -19,6 +19,9 @@
 //            over the classes of j of n_c (alpha_j / eff_j) / d_c.  Every sum has ONE order: lane l adds the row's terms l, l + 64,
 //            l + 128, ... in that order, starting from 0, then the 64 partial sums meet in the shuffle tree of strides 32, 16, 8, 4, 2, 1
 //            (lane l takes lane l + stride).  No floating-point atomic anywhere: two runs give the same bits.
+//   merge    (quant on several read files or ranks) the classes of several read sets as weighted lists: a key per
+//            list -- the map stage's hash of the same list --, then `classes` with a list in a fragment's place and n_c = the sum of
+//            a class's weights.  Integers only.
 #include "filter_fp_dev.h"
 
 #define ABD_MAX_SPAN 8191u     // bins of the span histogram a block keeps in LDS (32 KiB); a larger max_span is refused
@@ -252,10 +255,27 @@ __global__ void abd_members_kernel(uint64_t n_classes, const uint64_t* __restric
   n_c[c] = first[c + 1] - first[c];
 }
 
+// class c of weighted lists (shn_abundance_merge): n_c[c] = the sum of weight[frag[r]] over its sorted positions r in [first[c], first[c + 1]),
+// a wave a class: lane l adds the positions first[c] + l, + 64, ..., then the 64 sums meet in the shuffle tree.  64-bit integer adds: exact
+// in any order, no atomics.
+__global__ __launch_bounds__(FFP_BLOCK) void abd_weights_kernel(uint64_t n_classes, const uint64_t* __restrict__ first, const uint32_t* __restrict__ frag,
+                                                                const uint64_t* __restrict__ weight, uint64_t* __restrict__ n_c) {
+  const uint64_t c = (uint64_t)blockIdx.x * (FFP_BLOCK / 64) + (threadIdx.x >> 6);
+  if (c >= n_classes) return;                               // (the whole wave)
+  const uint32_t lane = threadIdx.x & 63;
+  unsigned long long x = 0;
+  for (uint64_t r = first[c] + lane, end = first[c + 1]; r < end; r += 64) x += weight[frag[r]];
+  for (int off = 32; off; off >>= 1) x += __shfl_down(x, off, 64);
+  if (lane == 0) n_c[c] = x;
+}
+
 // ---- classes: the fragments (pairs or single reads) whose lists the map stage left -- ids[off[i] .. off[i] + nuniq[i]) sorted, key[i]
-// their hash, frag[i] = i, `mapped` of the n_frag with a list -- sorted by hash, cut where the LIST changes, written into R
-static int abd_emit_classes(shn_ctx* ctx, ShnDevBufs& bufs, uint64_t n_frag, uint64_t mapped, uint64_t n_place, const uint64_t* d_off, const uint32_t* d_ids,
-                            const uint32_t* d_nuniq, uint64_t* d_key, uint64_t* d_key_tmp, uint32_t* d_frag, uint32_t* d_frag_tmp, shn_abundance* R) {
+// their hash, frag[i] = i, `mapped` of the n_frag with a list -- sorted by hash, cut where the LIST changes, written into R.  timer: the
+// group the launches report under.  d_weight == NULL: n_c[c] = the fragments of class c; else (shn_abundance_merge: the "fragments" are
+// weighted lists) the sum of their weight[].
+static int abd_emit_classes(shn_ctx* ctx, ShnDevBufs& bufs, int timer, uint64_t n_frag, uint64_t mapped, uint64_t n_place, const uint64_t* d_off,
+                            const uint32_t* d_ids, const uint32_t* d_nuniq, uint64_t* d_key, uint64_t* d_key_tmp, uint32_t* d_frag, uint32_t* d_frag_tmp,
+                            const uint64_t* d_weight, shn_abundance* R) {
   hipStream_t s = ctx->stream;
   uint32_t *d_head = nullptr, *d_size = nullptr, *d_members = nullptr;
   uint64_t *d_head_scan = nullptr, *d_first = nullptr, *d_class_off = nullptr, *d_nc = nullptr;
@@ -263,7 +283,7 @@ static int abd_emit_classes(shn_ctx* ctx, ShnDevBufs& bufs, uint64_t n_frag, uin
   HIP_TRY(bufs.get(&d_head, mapped * 4));
   HIP_TRY(bufs.get(&d_head_scan, (mapped + 1) * 8));
   {
-    TimerRegion treg(ctx, T_ABD_CLASSES);
+    TimerRegion treg(ctx, timer);
     // bytes: 8 sort passes over (key, fragment) pairs (24 B a pair and pass), then per mapped fragment its list and its predecessor's
     // (8 B a member at the most: n_place bounds both), ids, counts, offsets (32 B) and the flag (4 B)
     treg.bytes(8 * n_frag * 24 + mapped * 36 + n_place * 8);
@@ -280,7 +300,7 @@ static int abd_emit_classes(shn_ctx* ctx, ShnDevBufs& bufs, uint64_t n_frag, uin
   HIP_TRY(bufs.get(&d_class_off, (n_classes + 1) * 8));
   HIP_TRY(bufs.get(&d_nc, n_classes * 8));
   {
-    TimerRegion treg(ctx, T_ABD_CLASSES);
+    TimerRegion treg(ctx, timer);
     // bytes: a mapped fragment's flag (4 B); a head's number and fragment read, its count read, first and size written (28 B a
     // class); the scan of the sizes (12 B a class)
     treg.bytes(mapped * 4 + n_classes * 40);
@@ -291,11 +311,17 @@ static int abd_emit_classes(shn_ctx* ctx, ShnDevBufs& bufs, uint64_t n_frag, uin
   }
   HIP_TRY(bufs.get(&d_members, (n_entries + 1) * 4));
   {
-    TimerRegion treg(ctx, T_ABD_CLASSES);
+    TimerRegion treg(ctx, timer);
     // bytes: per class head, fragment, three offsets read, its count written (52 B); a member read and written (8 B)
     treg.bytes(mapped * 16 + n_classes * 52 + n_entries * 8);
     hipLaunchKernelGGL(abd_members_kernel, dim3((uint32_t)cdiv(n_classes, 256)), dim3(256), 0, s, n_classes, d_first, d_frag, d_off, d_ids, d_class_off,
                        d_members, d_nc);
+    if (d_weight) {
+      // bytes: per list its index and weight read (12 B); per class two positions read, the sum written (24 B)
+      treg.bytes(mapped * 12 + n_classes * 24);
+      hipLaunchKernelGGL(abd_weights_kernel, dim3((uint32_t)cdiv(n_classes, FFP_BLOCK / 64)), dim3(FFP_BLOCK), 0, s, n_classes, d_first, d_frag, d_weight,
+                         d_nc);
+    }
   }
   R->class_off.resize(n_classes + 1);
   R->n_c.resize(n_classes);
@@ -415,7 +441,8 @@ static int abd_classes_run(const std::string& fn, shn_ctx* ctx, const uint8_t* t
     fill(M);
   }
   // ---- classes
-  if (int rc = abd_emit_classes(ctx, bufs, n_frag, mapped, n_place, M.off, M.ids, M.nuniq, M.key, d_key_tmp, M.frag, d_frag_tmp, R)) return rc;
+  if (int rc = abd_emit_classes(ctx, bufs, T_ABD_CLASSES, n_frag, mapped, n_place, M.off, M.ids, M.nuniq, M.key, d_key_tmp, M.frag, d_frag_tmp, nullptr, R))
+    return rc;
   return done();
 }
 
@@ -459,6 +486,91 @@ extern "C" int shn_abundance_classes_single(shn_ctx* ctx, const uint8_t* text, c
       out);
 }
 
+// ---- merge: the classes of several read sets on the same transcripts, given as one CSR of weighted lists, become the
+// classes of the union of the reads.  A list takes the place abd_emit_classes gives a fragment: off = class_off, ids = members.
+// list i: nuniq[i] = its length, key[i] = the low hash_bits bits of the key abd_finish_list gives the same list, frag[i] = i
+__global__ void abd_list_keys_kernel(uint64_t n_lists, const uint64_t* __restrict__ off, const uint32_t* __restrict__ ids, uint64_t mask,
+                                     uint32_t* __restrict__ nuniq, uint64_t* __restrict__ key, uint32_t* __restrict__ frag) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_lists) return;
+  const uint64_t o = off[i], u = off[i + 1] - o;
+  uint64_t h = abd_mix(0, u);
+  for (uint64_t p = 0; p < u; p++) h = abd_mix(h, ids[o + p]);
+  nuniq[i] = (uint32_t)u;
+  key[i] = (h >> 1) & mask;
+  frag[i] = (uint32_t)i;
+}
+
+// the refusals of shn_abundance_merge, before anything is launched; *total = the sum of the weights
+static int abd_merge_check(const std::string& fn, const uint64_t* class_off, const uint32_t* members, const uint64_t* n_c, uint64_t n_lists, uint64_t m,
+                           uint32_t hash_bits, uint64_t* total) {
+  if (m == 0) return shn_fail(SHN_ERR_ARG, fn + ": no transcripts (m is 0)");
+  if (hash_bits < 1 || hash_bits > 63) return shn_fail(SHN_ERR_ARG, fn + ": hash_bits " + std::to_string(hash_bits) + " outside 1 .. 63");
+  if (!class_off || (n_lists && !n_c)) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
+  if (m >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many transcripts");
+  if (n_lists >= (1ULL << 32)) return shn_fail(SHN_ERR_OVERFLOW, fn + ": 2^32 or more lists (the sort carries a list's index in 32 bits)");
+  if (class_off[0] != 0) return shn_fail(SHN_ERR_ARG, fn + ": class_off[0] is not 0");
+  for (uint64_t c = 0; c < n_lists; c++) {
+    if (class_off[c + 1] < class_off[c]) return shn_fail(SHN_ERR_ARG, fn + ": class_off not monotone");
+    if (class_off[c + 1] == class_off[c]) return shn_fail(SHN_ERR_ARG, fn + ": list " + std::to_string(c) + " is empty");
+  }
+  const uint64_t n_entries = class_off[n_lists];
+  if (n_entries >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, fn + ": too many list members");
+  if (n_entries && !members) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
+  for (uint64_t c = 0; c < n_lists; c++)
+    for (uint64_t e = class_off[c]; e < class_off[c + 1]; e++) {
+      if (members[e] >= m) return shn_fail(SHN_ERR_ARG, fn + ": a list names transcript " + std::to_string(members[e]) + " of " + std::to_string(m));
+      if (e > class_off[c] && members[e] <= members[e - 1]) return shn_fail(SHN_ERR_ARG, fn + ": list " + std::to_string(c) + " is not strictly ascending");
+    }
+  uint64_t sum = 0;
+  for (uint64_t c = 0; c < n_lists; c++)
+    if (__builtin_add_overflow(sum, n_c[c], &sum)) return shn_fail(SHN_ERR_OVERFLOW, fn + ": the weights' sum does not fit in 64 bits");
+  *total = sum;
+  return SHN_OK;
+}
+
+// The classes of the union of several read sets from the sets' own classes: integers only.
+extern "C" int shn_abundance_merge(shn_ctx* ctx, const uint64_t* class_off, const uint32_t* members, const uint64_t* n_c, uint64_t n_lists, uint64_t m,
+                                   uint32_t hash_bits, shn_abundance** out) {
+  const std::string fn("shn_abundance_merge");
+  uint64_t total = 0;
+  if (int rc = abd_merge_check(fn, class_off, members, n_c, n_lists, m, hash_bits, &total)) return rc;
+  if (!ctx || !out) return shn_fail(SHN_ERR_ARG, fn + ": NULL argument");
+  shn_abundance* R = new shn_abundance();
+  R->n_tr = m; R->n_frag = total; R->mapped = total;
+  R->class_off.assign(1, 0);
+  struct Guard { shn_abundance* p; ~Guard() { delete p; } } guard{R};
+  auto done = [&]() { *out = R; guard.p = nullptr; return SHN_OK; };
+  if (n_lists == 0) return done();
+  SHN_ENTER(ctx);
+  shn_stage_begin(ctx);
+  hipStream_t s = ctx->stream;
+  ShnDevBufs bufs(s);
+  const uint64_t n_entries = class_off[n_lists];
+  uint64_t *d_off = nullptr, *d_w = nullptr, *d_key = nullptr, *d_key_tmp = nullptr;
+  uint32_t *d_ids = nullptr, *d_nuniq = nullptr, *d_frag = nullptr, *d_frag_tmp = nullptr;
+  HIP_TRY(bufs.get(&d_off, (n_lists + 1) * 8));
+  HIP_TRY(bufs.get(&d_ids, (n_entries + 1) * 4));
+  HIP_TRY(bufs.get(&d_w, n_lists * 8));
+  HIP_TRY(bufs.get(&d_nuniq, n_lists * 4));
+  HIP_TRY(bufs.get(&d_key, (n_lists + 1) * 8));
+  HIP_TRY(bufs.get(&d_key_tmp, (n_lists + 1) * 8));
+  HIP_TRY(bufs.get(&d_frag, (n_lists + 1) * 4));
+  HIP_TRY(bufs.get(&d_frag_tmp, (n_lists + 1) * 4));
+  HIP_TRY(hipMemcpyAsync(d_off, class_off, (n_lists + 1) * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_ids, members, n_entries * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_w, n_c, n_lists * 8, hipMemcpyHostToDevice, s));
+  {
+    TimerRegion treg(ctx, T_ABD_MERGE);
+    // bytes: per list two offsets read, length, key and index written (32 B); a member read for the hash (4 B)
+    treg.bytes(n_lists * 32 + n_entries * 4);
+    hipLaunchKernelGGL(abd_list_keys_kernel, dim3((uint32_t)cdiv(n_lists, 256)), dim3(256), 0, s, n_lists, d_off, d_ids, (~0ULL) >> (64 - hash_bits), d_nuniq,
+                       d_key, d_frag);
+  }
+  if (int rc = abd_emit_classes(ctx, bufs, T_ABD_MERGE, n_lists, n_lists, n_entries, d_off, d_ids, d_nuniq, d_key, d_key_tmp, d_frag, d_frag_tmp, d_w, R))
+    return rc;
+  return done();
+}
 
 extern "C" int shn_abundance_sizes(const shn_abundance* a, uint64_t* sizes) {
   if (!a || !sizes) return shn_fail(SHN_ERR_ARG, "shn_abundance_sizes: NULL argument");

@@ -67,7 +67,9 @@ enum {
   // chaining, the pair's orientation, rows and blocks)
   T_CMP_INDEX, T_CMP_SEEDS, T_CMP_SCORE, T_CMP_ROWS, T_CMP_CHAIN,
   // quant -b (abundance.hip): the bootstrap replicates' class counts, the EM over all live replicates at once
-  T_ABD_RESAMPLE, T_ABD_EM_BATCH, T_N = 72     // (T_N: device.TIMER_SLOTS)
+  T_ABD_RESAMPLE, T_ABD_EM_BATCH,
+  // quant on several read files or ranks (abundance.hip): the parts' classes merged -- keys, sort, heads, members, weights
+  T_ABD_MERGE, T_N = 72                        // (T_N: device.TIMER_SLOTS)
 };
 
 // grow-only device workspace slot (process-wide ones: g_shn_ws below; per-context ones: shn_ctx::cws)

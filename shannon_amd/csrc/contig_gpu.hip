@@ -380,7 +380,7 @@ int shn_sorted_windows(shn_ctx* ctx, ShnDevBufs& bufs, const uint8_t* d_bases, c
   unsigned long long bad = 0;
   HIP_TRY(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (bad) return shn_fail(SHN_ERR_ARG, "shn_contig_stage: contig with a base outside ACGT");
+  if (bad) return shn_fail(SHN_ERR_ARG, "contig windows: contig with a base outside ACGT");      // (shared: the contig stage, shn_probe_build)
   if ((rc = shn_sort_pairs(ctx, k1, v1, k2, v2, nv, 0, 2 * k))) return rc;
   *keys = k1; *vals = v1;
   return SHN_OK;

@@ -12,9 +12,10 @@ pytestmark = pytest.mark.gpu
 from cc_reference import reference_labels, same_partition
 
 
-def play_ranks(ctx, table, W, K1, canonical):
+def play_ranks(ctx, table, W, K1, canonical, base0=0):
     """the whole exchange with W ranks in one process.  Returns per rank (keys of the shard in table order, their global labels,
-    (keys, counts) received after the component exchange)."""
+    (keys, counts) received after the component exchange).  base0: added to every rank's base and to id_limit -- the global ids
+    of a job whose earlier shards hold that many k1-mers (64-bit ids through shn_cc_answer, shn_cc_solve and shn_cc_labels)."""
     import torch
     from shannon_amd import device
     dev = torch.device("cuda", 0)
@@ -31,7 +32,7 @@ def play_ranks(ctx, table, W, K1, canonical):
         shards.append(t)
         ccs.append(device.ComponentShards(ctx, t, W, r))
     sizes = [len(t) for t in shards]
-    base = [sum(sizes[:r]) for r in range(W)]
+    base = [base0 + sum(sizes[:r]) for r in range(W)]
     # queries of every rank, grouped by destination
     sent = []
     for r in range(W):
@@ -55,7 +56,7 @@ def play_ranks(ctx, table, W, K1, canonical):
     nodes = torch.empty(2 * max(E, 1), dtype=torch.int64, device=dev)
     labels = torch.empty(2 * max(E, 1), dtype=torch.int64, device=dev)
     torch.cuda.synchronize()
-    nn = device.ComponentShards.solve(ctx, ge.data_ptr(), E, sum(sizes) + 1, nodes.data_ptr(), labels.data_ptr())
+    nn = device.ComponentShards.solve(ctx, ge.data_ptr(), E, base0 + sum(sizes) + 1, nodes.data_ptr(), labels.data_ptr())
     # the same from the edges in another order: the answer must not depend on it
     if E > 1:
         perm = torch.randperm(E, device=dev)
@@ -105,9 +106,16 @@ def play_ranks(ctx, table, W, K1, canonical):
     return out, got
 
 
-@pytest.mark.parametrize("W,n_genes,seed,K,ss", [(2, 3, 11, 25, False), (3, 12, 4, 25, False), (4, 40, 8, 24, False), (8, 12, 5, 31, False),
-                                                 (3, 12, 4, 25, True), (5, 1, 3, 20, False)])
-def test_labels_of_the_shards_are_the_components(W, n_genes, seed, K, ss):
+def _case(W, n_genes, seed, K, ss, base0=0):
+    """(the cases without base0 keep the ids they had before base0 existed)"""
+    name = "%d-%d-%d-%d-%s" % (W, n_genes, seed, K, ss)
+    return pytest.param(W, n_genes, seed, K, ss, base0, id=name if not base0 else "%s-base0=%d" % (name, base0))
+
+
+@pytest.mark.parametrize("W,n_genes,seed,K,ss,base0", [_case(2, 3, 11, 25, False), _case(3, 12, 4, 25, False), _case(4, 40, 8, 24, False),
+                                                       _case(8, 12, 5, 31, False), _case(3, 12, 4, 25, True), _case(5, 1, 3, 20, False),
+                                                       _case(2, 3, 11, 25, False, 2 ** 32 - 5), _case(2, 3, 11, 25, False, 2 ** 40)])
+def test_labels_of_the_shards_are_the_components(W, n_genes, seed, K, ss, base0):
     from shannon_amd import device, synth
     (q1, q2), _ = synth.make_dataset(12000, n_genes, seed=seed)
     ctx = device.Context(0)
@@ -120,10 +128,12 @@ def test_labels_of_the_shards_are_the_components(W, n_genes, seed, K, ss):
         canonical = table.canonical
         assert canonical == (not ss)
         tk, tc = table.download()
-        out, got = play_ranks(ctx, table, W, K + 1, canonical)
+        out, got = play_ranks(ctx, table, W, K + 1, canonical, base0)
         keys = np.concatenate([o[0] for o in out])
         gl = np.concatenate([o[1] for o in out])
         ow = np.concatenate([o[2] for o in out])
+        if base0:                                                    # every label is a global id of this job: ids at and above 2^32
+            assert int(gl.min()) >= base0 and int(gl.max()) < base0 + len(tk) and base0 + len(tk) > 2 ** 32
         assert len(keys) == len(tk) and np.array_equal(np.sort(keys), np.sort(tk))            # the shards partition the table
         ref = reference_labels(keys, K + 1, canonical)
         assert len(np.unique(ref)) > 1 or n_genes == 1               # (one gene at K = 20: its errors hang on it as siblings -- one component)

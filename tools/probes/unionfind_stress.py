@@ -1,4 +1,5 @@
-"""the lock-free union-find alone (shn_cc_solve: every edge united once): long chains and random forests, shuffled, against scipy"""
+"""the lock-free union-find alone (shn_cc_solve: every edge united once): long chains and random forests, shuffled, against scipy.
+Its shapes at test size, once each, are tests/test_cc_solve_gpu.py; this probe stays for 40 repeats at two million nodes."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)

@@ -19,11 +19,13 @@ The result equals the single-GPU pipeline on the concatenated reads (tests/test_
 to exercise the collective choreography with gloo).
 """
 from collections.abc import Mapping
+from contextlib import contextmanager
+from types import SimpleNamespace
 import os
 import numpy as np
 import torch
 import torch.distributed as dist
-from . import exchange, mbgraph, sparse_flow, post, _lib
+from . import exchange, graph_intake, sparse_flow, post, _lib
 
 
 def _all_gather_var(t, group=None, name="table all-gather (owned k1-mer shards)"):
@@ -183,12 +185,79 @@ def deal_partitions(load, W):
     return owner
 
 
-class _NoLock(object):
-    def acquire(self):
-        pass
+class Clock(object):
+    """One rank's stage times and its compute lock.  `with clock.stage(name)`: a stretch of this rank's own compute -- the lock is
+    held, the seconds go to timings[name].  `with clock.collective(name)`, inside a stage or between two: time spent with the other
+    ranks -- the enclosing stage's stopwatch stops and the lock is free until the block is left, by an exception too; the seconds
+    go to timings[name] ("x:...").  So the lock is held exactly while a stage is open and no collective is.
+    lock (development aid; acquire() / release()): with several ranks on ONE GPU it serialises their compute, so the per-stage
+    times are those of a rank that has a GPU to itself.  timings: the dict itself, for callees that keep sub-stage keys in it
+    (run_correction, kmers_for_component).  Clock() alone holds no lock and measures into a dict nobody reads."""
 
-    def release(self):
-        pass
+    def __init__(self, timings=None, lock=None, now=None):
+        import time
+        self.timings = timings if timings is not None else {}
+        self._lock, self._now, self._open = lock, now or time.time, None      # _open: [name, start] of the open stage
+
+    def _add(self, name, since):
+        self.timings[name] = self.timings.get(name, 0.0) + self._now() - since
+
+    def _switch(self, name):
+        """closes the open stage, if there is one (its seconds booked, the lock given back), and opens stage `name`, unless None"""
+        if self._open is not None:
+            self._add(*self._open)
+            self._open = None
+            if self._lock is not None:
+                self._lock.release()
+        if name is not None:
+            if self._lock is not None:
+                self._lock.acquire()
+            self._open = [name, self._now()]
+
+    @contextmanager
+    def stage(self, name):
+        if self._open is not None:
+            raise RuntimeError("Clock: stage %r opened inside stage %r" % (name, self._open[0]))
+        self._switch(name)
+        try:
+            yield
+        finally:
+            self._switch(None)
+
+    @contextmanager
+    def collective(self, name):
+        around = self._open[0] if self._open is not None else None
+        self._switch(None)
+        since = self._now()
+        try:
+            yield
+        finally:
+            self._add(name, since)
+            self._switch(around)
+
+
+class RankOps(object):
+    """What assemble_distributed asks of a rank's compute (GpuOps below: HIP kernels through the C ABI; the CPU tests: the oracle).
+    Required: paired; n_reads(); local_pairs(W, by_minimizer=False) -> (keys, counts, per rank); reduce_pairs(keys, counts);
+    table_from_pairs(keys, counts); extension(table, partition_size, group, presharded=None: or the job's k1-mers, `table` holding
+    this rank's whole components); route(res, K, partition_size, part_vectors) -> {"new_components", "routes", ...};
+    n_nodes(part, name, K); collect(doubled indices) -> a piece of reads; graph(part, name, pieces, K, paired) -> (singles,
+    components); sparse_flow(components, ids, seed).  Set by assemble_distributed: clock, strand_specific, min_weight, min_length,
+    kmer_hard_cutoff.  Two things are looked for, not declared: their absence refuses foreign ops before any collective --
+    supports_strand_specific (true: -s is implemented) and filter_cover / filter_count (--filter_FP: see filter_owned_texts)."""
+    owner_labelling = False       # capability: owned_table(keys, counts), component_table(owned, group) -> (table, k1-mers of the job)
+    resident_rows = False         # capability: an owner's partition routed by its own reads alone is handed over as LocalRows, not collected
+    array_payload = False         # capability: collect() gives arrays (rows + flags, or exchange.RaggedPiece) that travel as bytes, not pickles
+    local_table = None            # capability, () -> table: a one-rank job's counted table as it is.  None: not offered
+    graph_batch = None            # capability, (part, names, owned, mine, K, paired, sample, seed) -> {partition: FASTA} in stages of its
+    #                               own, or None: "one partition at a time through graph(), please".  None: not offered
+    graph_threads = 1             # tuning: threads over the owned partitions on the way through graph()
+    device = None                 # where the rank's tensors live (None: the host); collectives are staged by exchange.coll_device
+    ctx = None                    # device.Context for rank 0's merge (None: the host form)
+    clock = Clock()               # side channel: the driver's Clock, for the ops' own stages and collectives
+    strand_specific = False
+    min_weight, min_length, kmer_hard_cutoff = 3, 75, 1       # (shannon.py:55-57, 237-247)
+
 
 
 def assemble_distributed(ops, K=25, partition_size=500, sample="shannon", seed=0, part_vectors=None, group=None,
@@ -207,9 +276,7 @@ def assemble_distributed(ops, K=25, partition_size=500, sample="shannon", seed=0
     (:596).  The ops say whether they can (`ops.strand_specific`, set here); ops without the attribute `supports_strand_specific`
     are refused rather than run double-stranded.
     timings: seconds per stage, compute ("count", "extension", ...) and collectives ("x:...") apart.
-    lock (development aid): held while this rank computes, released around every collective -- with several ranks on
-    ONE GPU it serialises the compute, so the per-stage compute times are those of a rank that has a GPU to itself."""
-    import time
+    lock (development aid): held while this rank computes, free around every collective and on entry, return and raise (Clock)."""
     ss = not double_stranded
     if filter_fp and not (hasattr(ops, "filter_cover") and hasattr(ops, "filter_count")):
         raise ValueError("assemble_distributed: filter_fp=True needs ops that map read pairs onto transcripts (filter_cover / filter_count: "
@@ -219,208 +286,234 @@ def assemble_distributed(ops, K=25, partition_size=500, sample="shannon", seed=0
                                   "indices, pairs of reads_1 and RC(reads_2)); a strand_specific run needs ops that do (GpuOps does)")
     ops.strand_specific = ss
     ops.min_weight, ops.min_length, ops.kmer_hard_cutoff = int(min_weight), int(min_length), int(kmer_hard_cutoff)
-    T = timings if timings is not None else {}
-    lock = lock or _NoLock()
-    ops.lock = lock
-    ops.timings = T                     # sub-stages of the extension land in the same dict ("ext.*")
+    ops.clock = clock = Clock(timings, lock)
+    # What the stages share.  Left behind by _table: table, n_k1mers, presharded; _extension: res; _route: part, names, n_local, base,
+    # n_glob, allc; _deal_and_collect: cutoffs, owner, payload; _exchange_reads: recv; _graphs: texts, err; the filter: extra.
+    S = SimpleNamespace(ops=ops, clock=clock, group=group, W=dist.get_world_size(group), rank=dist.get_rank(group), K=K, partition_size=partition_size,
+                        sample=sample, seed=seed, part_vectors=part_vectors, ss=ss, presharded=None, err=None, extra=None)
+    _table(S)
+    _extension(S)
+    _route(S)
+    _deal_and_collect(S)
+    _exchange_reads(S)
+    _graphs(S)
+    if filter_fp:
+        S.texts, S.extra, S.err = _filter_step(ops, S.part, S.texts, S.names, S.owner, group, clock, S.err)
+    return _gather_and_merge(S.texts, S.names, S.res, S.n_k1mers, group, clock, error=S.err, device=ops.device, ctx=ops.ctx,
+                             double_stranded=double_stranded, extra=S.extra)
 
-    def tick(name, t0):
-        T[name] = T.get(name, 0.0) + time.time() - t0
 
-    W, rank = dist.get_world_size(group), dist.get_rank(group)
-    # ---- 1. local count + bucket exchange + reduce by key
-    lock.acquire()
-    t0 = time.time()
-    import os
-    forced = os.environ.get("SHN_OWNER_LABELS") == "2" and getattr(ops, "owner_labelling", False)    # (tests: the N-rank path on one rank)
-    if W == 1 and hasattr(ops, "local_table") and not forced:
-        # one rank: nothing to exchange, reduce or gather -- the counted table IS the table (it used to be exported to pairs, reduced
-        # into a table, exported again and rebuilt: two passes through the pairs path, 0.2 s at configs[2])
-        table = ops.local_table()
-        tick("count", t0)
-        gk = None
-    elif getattr(ops, "owner_labelling", False):
-        # No rank ever holds the whole table (BASELINE configs[4]): the k1-mers go to the rank that owns their minimizer, the components
-        # of the k1-mer graph are labelled on those shards (local union-find + one exchange of the edges that cross shards), and whole
-        # components travel to the rank that walks them -- a table of its own per rank, the unsharded extension on it.
-        keys, counts, send = ops.local_pairs(W, by_minimizer=True)
-        tick("count", t0)
-        lock.release()
-        t0 = time.time()
-        rk, rc, _ = exchange.all_to_all_pairs(keys, counts, send, group)
-        del keys, counts
-        tick("x:bucket exchange", t0)
-        lock.acquire()
-        t0 = time.time()
-        owned = ops.owned_table(rk, rc)
+def _table(S):
+    """1. The k1-mer table this rank extends.  Which of the three ways is decided here and nowhere else; SHN_OWNER_LABELS=2 (tests)
+    takes a one-rank job through the owner shards."""
+    forced = os.environ.get("SHN_OWNER_LABELS") == "2" and S.ops.owner_labelling
+    if S.W == 1 and S.ops.local_table is not None and not forced:
+        _table_one_rank(S)
+    elif S.ops.owner_labelling:
+        _table_owner_shards(S)
+    else:
+        _table_replicated(S)
+
+
+def _table_one_rank(S):
+    """One rank: nothing to exchange, reduce or gather -- the counted table IS the table (it used to be exported to pairs, reduced
+    into a table, exported again and rebuilt: two passes through the pairs path, 0.2 s at configs[2]).  No collective."""
+    with S.clock.stage("count"):
+        S.table = S.ops.local_table()
+        S.n_k1mers = len(S.table)
+
+
+def _exchanged_pairs(S, by_minimizer):
+    """local count, then the (key, count) pairs to the ranks that own them.  Collective: the bucket exchange (one all-to-all)."""
+    with S.clock.stage("count"):
+        keys, counts, send = S.ops.local_pairs(S.W, by_minimizer=by_minimizer)
+    with S.clock.collective("x:bucket exchange"):
+        rk, rc, _ = exchange.all_to_all_pairs(keys, counts, send, S.group)
+    return rk, rc
+
+
+def _table_owner_shards(S):
+    """No rank ever holds the whole table (BASELINE configs[4]): the k1-mers go to the rank that owns their minimizer, the components
+    of the k1-mer graph are labelled on those shards (local union-find + one exchange of the edges that cross shards), and whole
+    components travel to the rank that walks them -- a table of its own per rank, the unsharded extension on it.
+    Collectives: the bucket exchange, then those of component_table."""
+    rk, rc = _exchanged_pairs(S, True)
+    with S.clock.stage("reduce"):
+        owned = S.ops.owned_table(rk, rc)
         del rk, rc
-        tick("reduce", t0)
-        table, n_table = ops.component_table(owned, group, tick)
-        gk = None
-        t0 = time.time()
-    else:
-        keys, counts, send = ops.local_pairs(W)
-        tick("count", t0)
-        lock.release()
-        t0 = time.time()
-        rk, rc, _ = exchange.all_to_all_pairs(keys, counts, send, group)
-        tick("x:bucket exchange", t0)
-        lock.acquire()
-        t0 = time.time()
-        ok, oc = ops.reduce_pairs(rk, rc)
-        tick("reduce", t0)
-        lock.release()
-        # ---- 2. replicate the (small) distinct-k1-mer table, extension + partitioning on every rank
-        t0 = time.time()
-        gk, _ = _all_gather_var(ok, group)
-        gc, _ = _all_gather_var(oc, group)
-        tick("x:allgather table", t0)
-        lock.acquire()
-        t0 = time.time()
-        table = ops.table_from_pairs(gk, gc)
-        tick("table", t0)
-    t0 = time.time()
-    if (W > 1 or forced) and getattr(ops, "owner_labelling", False):
-        res = ops.extension(table, partition_size, group, presharded=n_table)
-    else:
-        n_table = len(table) if gk is None else None
-        res = ops.extension(table, partition_size, group) if getattr(ops, "sharded_extension", False) else ops.extension(table, partition_size)
-    if n_table is not None:
-        res.n_k1mers_table = n_table
-    tick("extension", t0)
-    w = getattr(ops, "coll_wait", 0.0)       # the sharded contig stage's object collectives, reported apart
-    if w:
-        T["extension"] -= w
-        T["x:contig gathers"] = T.get("x:contig gathers", 0.0) + w
-    t0 = time.time()
-    part = ops.route(res, K, partition_size, part_vectors)
-    names = list(part["new_components"])
-    P = len(names)
-    # ---- 3. global strand-doubled order + per-partition cap
-    n_local = ops.n_reads()
-    tick("partition+route", t0)
-    lock.release()
-    t0 = time.time()
-    cdev = exchange.coll_device(ops.device, group)
-    nl = torch.tensor([n_local], dtype=torch.int64, device=cdev)
-    nls = [torch.zeros_like(nl) for _ in range(W)]
-    dist.all_gather(nls, nl, group=group)
-    nls = [int(x.item()) for x in nls]
-    base, n_glob = sum(nls[:rank]), sum(nls)
-    cnt = np.zeros((P, 2), dtype=np.int64)          # routed reads of this rank: forward half / RC half
-    for i, nm in enumerate(names):
-        r = part["routes"][nm]
-        f = r.count_below_split() if hasattr(r, "count_below_split") else int(np.searchsorted(r, n_local))
-        cnt[i] = (f, len(r) - f)
-    ct = torch.as_tensor(cnt.reshape(-1), device=cdev)
-    cts = [torch.zeros_like(ct) for _ in range(W)]
-    dist.all_gather(cts, ct, group=group)
-    allc = np.stack([c.cpu().numpy().reshape(P, 2) for c in cts])       # [W, P, 2]
-    tick("x:route counts", t0)
-    lock.acquire()
-    t0 = time.time()
+    S.table, S.n_k1mers = S.ops.component_table(owned, S.group)
+    S.presharded = S.n_k1mers
+
+
+def _table_replicated(S):
+    """The path of rounds 2-4, kept for comparison: every rank reduces the pairs it owns, the (small) distinct-k1-mer table is
+    replicated, extension + partitioning on every rank.  Collectives: the bucket exchange, two all-gathers (keys, counts)."""
+    rk, rc = _exchanged_pairs(S, False)
+    with S.clock.stage("reduce"):
+        ok, oc = S.ops.reduce_pairs(rk, rc)
+    with S.clock.collective("x:allgather table"):
+        gk, _ = _all_gather_var(ok, S.group)
+        gc, _ = _all_gather_var(oc, S.group)
+    with S.clock.stage("table"):
+        S.table = S.ops.table_from_pairs(gk, gc)
+    S.n_k1mers = int(gk.numel())
+
+
+def _extension(S):
+    """2. Greedy extension + contig stage on the rank's table -> S.res.  Collectives: the ops' own, if they shard the work over the
+    group ("x:contig gathers": GpuOps gathers what the shards' contig stages accept)."""
+    with S.clock.stage("extension"):
+        S.res = S.ops.extension(S.table, S.partition_size, S.group, presharded=S.presharded)
+    del S.table
+
+
+def _forward_routes(r, n_local):
+    """how many of a partition's routes (ascending doubled indices) lie in the forward half.  A route is an array or a
+    kmers_for_component.RouteView, which knows: that depends on how the partition was routed, not on the ops."""
+    return r.count_below_split() if hasattr(r, "count_below_split") else int(np.searchsorted(r, n_local))
+
+
+def _route(S):
+    """3a. Partitions, this rank's routes into them, and every rank's routed reads per partition and strand half (S.allc [W, P, 2]):
+    the global strand-doubled order is all ranks' forward reads in rank order, then all ranks' reverse halves.
+    Collectives: two all-gathers of int64 (reads per rank; the counts), "x:route counts"."""
+    ops, group, W = S.ops, S.group, S.W
+    with S.clock.stage("partition+route"):
+        S.part = ops.route(S.res, S.K, S.partition_size, S.part_vectors)
+        S.names = list(S.part["new_components"])
+        P = len(S.names)
+        S.n_local = ops.n_reads()
+        cnt = np.zeros((P, 2), dtype=np.int64)          # routed reads of this rank: forward half / RC half
+        for i, nm in enumerate(S.names):
+            r = S.part["routes"][nm]
+            f = _forward_routes(r, S.n_local)
+            cnt[i] = (f, len(r) - f)
+        with S.clock.collective("x:route counts"):
+            cdev = exchange.coll_device(ops.device, group)
+            nl = torch.tensor([S.n_local], dtype=torch.int64, device=cdev)
+            nls = [torch.zeros_like(nl) for _ in range(W)]
+            dist.all_gather(nls, nl, group=group)
+            nls = [int(x.item()) for x in nls]
+            ct = torch.as_tensor(cnt.reshape(-1), device=cdev)
+            cts = [torch.zeros_like(ct) for _ in range(W)]
+            dist.all_gather(cts, ct, group=group)
+            S.allc = np.stack([c.cpu().numpy().reshape(P, 2) for c in cts])
+    S.base, S.n_glob = sum(nls[:S.rank]), sum(nls)
+
+
+def read_caps(allc, cutoffs, rank):
+    """How many of its forward and of its reverse-half routed reads rank `rank` sends for every partition, when a partition's graph
+    consumes the first cutoffs[p] reads of the global strand-doubled order (multibridging.py:26-30).  allc [W, P, 2]: every rank's
+    routed reads per partition, forward / reverse half.  The kept reads are prefixes of the rank's two halves.  -> (keep_f, keep_r) [P]"""
+    allc, cutoffs = np.asarray(allc, dtype=np.int64), np.asarray(cutoffs, dtype=np.int64)
     # position of this rank's first forward / first RC routed read of partition p in the global order
     fwd_before = allc[:rank, :, 0].sum(axis=0)
     rc_before = allc[:, :, 0].sum(axis=0) + allc[:rank, :, 1].sum(axis=0)
-    paired = ops.paired
-    # owner of every partition: largest first onto the least loaded rank (load = the reads its graph will consume, known to
-    # every rank from the gathered counts) -- the reference's size-sorted job list (shannon.py:546-551) dealt over the ranks
-    cutoffs = np.array([10 * ops.n_nodes(part, nm, K) + 1 for nm in names], dtype=np.int64)
-    owner = deal_partitions(np.minimum(allc.sum(axis=(0, 2)), cutoffs) + 1, W)
-    payload = [[] for _ in range(W)]                # per destination rank: (partition, global doubled indices, reads)
-    for i, nm in enumerate(names):
-        cutoff = int(cutoffs[i])
-        r = part["routes"][nm]                      # array, or a RouteView: only the kept prefixes are fetched
-        f = int(cnt[i, 0])
-        keep_f = int(max(0, min(f, cutoff - fwd_before[i])))
-        keep_r = int(max(0, min(len(r) - f, cutoff - rc_before[i])))
-        if keep_f + keep_r == 0:
-            continue
-        rf, rr = np.asarray(r[:keep_f], dtype=np.int64), np.asarray(r[f:f + keep_r], dtype=np.int64)
-        sel = np.concatenate([rf, rr])
-        gidx = np.concatenate([base + rf, n_glob + base + (rr - n_local)])
-        if not ss and int(owner[i]) == rank and getattr(ops, "resident_rows", False) and int(allc[:, i, :].sum()) == int(cnt[i].sum()):
-            # every routed read of this partition is a row of this rank's own resident input, and this rank owns the partition:
-            # nothing is collected -- the graph stage names the reads by their rows, as the single-GPU pipeline does
-            payload[rank].append((i, gidx, LocalRows(sel)))
-        else:
-            payload[int(owner[i])].append((i, gidx, ops.collect(sel)))
-    tick("collect reads", t0)
-    lock.release()
-    t0 = time.time()
-    if getattr(ops, "array_payload", False):        # code rows + flags: one all-to-all(v) of bytes; what a rank owns itself stays put
-        got = exchange.all_to_all_bytes([exchange.pack_read_pieces(items if d != rank else []) for d, items in enumerate(payload)], ops.device, group)
-        recv = [exchange.unpack_read_pieces(b) if src != rank else payload[rank] for src, b in enumerate(got)]
-    else:                                           # python objects (the oracle-backed test ops): small inputs only
-        recv = [None] * W
-        _a2a_objects(recv, payload, group)
-    tick("x:read exchange", t0)
-    # ---- 4. owned partitions: graph + sparse flow
-    lock.acquire()
-    t0 = time.time()
-    mine = {}
-    for lst in recv:
-        for p, gidx, data in lst:
-            mine.setdefault(p, []).append((gidx, data))
-    owned = sorted((i for i in range(P) if int(owner[i]) == rank), key=lambda i: -int(min(allc[:, i, :].sum(), cutoffs[i])))
+    keep_f = np.maximum(0, np.minimum(allc[rank, :, 0], cutoffs - fwd_before))
+    keep_r = np.maximum(0, np.minimum(allc[rank, :, 1], cutoffs - rc_before))
+    return keep_f, keep_r
 
-    if hasattr(ops, "graph_batch"):
-        # the owned partitions through the single-GPU graph stage: GPU unitigs, distinct reads found on the device, native sparse flow
-        err = None
+
+def _deal_and_collect(S):
+    """3b. The owner of every partition, the reads under its cap, and this rank's share of them per destination (S.payload: per rank
+    [(partition, global doubled indices, reads)]).  No collective: every rank deals alike from the gathered counts."""
+    ops, part, names, allc, rank = S.ops, S.part, S.names, S.allc, S.rank
+    with S.clock.stage("collect reads"):
+        # owner of every partition: largest first onto the least loaded rank (load = the reads its graph will consume, known to
+        # every rank from the gathered counts) -- the reference's size-sorted job list (shannon.py:546-551) dealt over the ranks
+        S.cutoffs = np.array([10 * ops.n_nodes(part, nm, S.K) + 1 for nm in names], dtype=np.int64)
+        S.owner = deal_partitions(np.minimum(allc.sum(axis=(0, 2)), S.cutoffs) + 1, S.W)
+        keep_f, keep_r = read_caps(allc, S.cutoffs, rank)
+        S.payload = [[] for _ in range(S.W)]
+        for i, nm in enumerate(names):
+            kf, kr = int(keep_f[i]), int(keep_r[i])
+            if kf + kr == 0:
+                continue
+            r = part["routes"][nm]                      # array, or a RouteView: only the kept prefixes are fetched
+            f = int(allc[rank, i, 0])
+            rf, rr = np.asarray(r[:kf], dtype=np.int64), np.asarray(r[f:f + kr], dtype=np.int64)
+            sel = np.concatenate([rf, rr])
+            gidx = np.concatenate([S.base + rf, S.n_glob + S.base + (rr - S.n_local)])
+            if not S.ss and int(S.owner[i]) == rank and ops.resident_rows and int(allc[:, i, :].sum()) == int(allc[rank, i].sum()):
+                # every routed read of this partition is a row of this rank's own resident input, and this rank owns the partition:
+                # nothing is collected -- the graph stage names the reads by their rows, as the single-GPU pipeline does
+                S.payload[rank].append((i, gidx, LocalRows(sel)))
+            else:
+                S.payload[int(S.owner[i])].append((i, gidx, ops.collect(sel)))
+
+
+def _exchange_reads(S):
+    """3c. The capped reads to the partitions' owners -> S.recv, per source rank.  Collective: one all-to-all(v) of bytes
+    (array_payload), or of python objects through one all-gather (the oracle-backed test ops: small inputs only)."""
+    ops, rank = S.ops, S.rank
+    with S.clock.collective("x:read exchange"):
+        if ops.array_payload:                       # code rows + flags; what a rank owns itself stays put
+            got = exchange.all_to_all_bytes([exchange.pack_read_pieces(items if d != rank else []) for d, items in enumerate(S.payload)], ops.device, S.group)
+            S.recv = [exchange.unpack_read_pieces(b) if src != rank else S.payload[rank] for src, b in enumerate(got)]
+        else:
+            S.recv = [None] * S.W
+            _a2a_objects(S.recv, S.payload, S.group)
+    del S.payload
+
+
+def _graphs(S):
+    """4. Graph + sparse flow of the partitions this rank owns -> S.texts {partition: FASTA}.  No collective.  Either all of them
+    through the single-GPU graph stage (ops.graph_batch), whose failure is kept in S.err and told to every rank in the gather --
+    nobody waits there for a rank that has left; or, where the ops have no batch or it declines, one partition at a time."""
+    ops = S.ops
+    with S.clock.stage("graph"):
+        mine = {}
+        for lst in S.recv:
+            for p, gidx, data in lst:
+                mine.setdefault(p, []).append((gidx, data))
+        del S.recv
+        owned = sorted((i for i in range(len(S.names)) if int(S.owner[i]) == S.rank), key=lambda i: -int(min(S.allc[:, i, :].sum(), S.cutoffs[i])))
+    S.texts = None
+    if ops.graph_batch is not None:
         try:
-            texts = ops.graph_batch(part, names, owned, mine, K, paired, sample, seed, T)
-        except Exception as ex:                     # told to every rank below: nobody waits in the gather for a rank that has left
-            texts, err = {}, "%s: %s" % (type(ex).__name__, ex)
-        if texts is not None:
-            extra = None
-            if filter_fp:
-                texts, extra, err = _filter_step(ops, part, texts, names, owner, group, tick, lock, err)
-            lock.release()
-            return _gather_and_merge(texts, names, res, gk, group, rank, W, lock, tick, error=err, ops=ops, double_stranded=double_stranded,
-                                     extra=extra)
+            S.texts = ops.graph_batch(S.part, S.names, owned, mine, S.K, ops.paired, S.sample, S.seed)
+        except Exception as ex:
+            S.texts, S.err = {}, "%s: %s" % (type(ex).__name__, ex)
+    if S.texts is None:
+        S.texts = _graphs_one_by_one(S, owned, mine)
+
+
+def _graphs_one_by_one(S, owned, mine):
+    """ops.graph per owned partition (independent: threads, the native stage releases the GIL), one ops.sparse_flow over all"""
+    ops, names = S.ops, S.names
 
     def one(i):
-        singles, comps = ops.graph(part, names[i], mine.get(i, []), K, paired)      # pieces: [(global indices, reads)] per source rank
+        singles, comps = ops.graph(S.part, names[i], mine.get(i, []), S.K, ops.paired)      # pieces: [(global indices, reads)] per source rank
         return (i, singles, comps)
 
-    nthreads = min(len(owned), getattr(ops, "graph_threads", 1))
-    if nthreads > 1:                      # owned partitions are independent; the native stage releases the GIL
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=nthreads) as pool:
-            jobs = list(pool.map(one, owned))
-    else:
-        jobs = [one(i) for i in owned]
-    tick("graph", t0)
-    t0 = time.time()
-    flat = [(c["nodes"], c["edges"], c["paths"]) for _, _, comps in jobs for c in comps]
-    ids = [c for _, _, comps in jobs for c in range(len(comps))]
-    trs = ops.sparse_flow(flat, ids, seed) if flat else []
-    k = 0
-    texts = {}
-    for i, singles, comps in jobs:
-        sname = "%s_%s" % (sample, names[i])
-        txt = ""
-        for c in range(len(comps)):
-            txt += sparse_flow.fasta_records(sname, str(c), trs[k])
-            k += 1
-        txt += sparse_flow.single_nodes_fasta(sname, singles)
-        texts[i] = txt
-    tick("sparse flow", t0)
-    extra, err = None, None
-    if filter_fp:
-        texts, extra, err = _filter_step(ops, part, texts, names, owner, group, tick, lock, None)
-    lock.release()
-    return _gather_and_merge(texts, names, res, gk, group, rank, W, lock, tick, error=err, ops=ops, double_stranded=double_stranded, extra=extra)
+    with S.clock.stage("graph"):
+        nthreads = min(len(owned), ops.graph_threads)
+        if nthreads > 1:
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(max_workers=nthreads) as pool:
+                jobs = list(pool.map(one, owned))
+        else:
+            jobs = [one(i) for i in owned]
+    with S.clock.stage("sparse flow"):
+        flat = [(c["nodes"], c["edges"], c["paths"]) for _, _, comps in jobs for c in comps]
+        ids = [c for _, _, comps in jobs for c in range(len(comps))]
+        trs = ops.sparse_flow(flat, ids, S.seed) if flat else []
+        k, texts = 0, {}
+        for i, singles, comps in jobs:
+            sname = "%s_%s" % (S.sample, names[i])
+            texts[i] = "".join(sparse_flow.fasta_records(sname, str(c), trs[k + c]) for c in range(len(comps))) + sparse_flow.single_nodes_fasta(sname, singles)
+            k += len(comps)
+    return texts
 
 
-def _filter_step(ops, part, texts, names, owner, group, tick, lock, err):
-    """--filter_FP between the owners' sparse flow and the gather: (texts for the merge, what travels beside them, error).  Whether
-    the step runs is decided from what every rank holds (the flag, ops.paired), so every rank reaches its collectives or none does."""
+def _filter_step(ops, part, texts, names, owner, group, clock, err):
+    """5. --filter_FP between the owners' sparse flow and the gather: (texts for the merge, what travels beside them, error).  Whether
+    it runs is decided from what every rank holds (the flag, ops.paired): all ranks reach filter_owned_texts' collectives or none."""
     if not ops.paired:
         return texts, {"note": "--filter_FP: single-end input -- the reference sets the flag only for paired-end runs "
                                "(run_MB_SF_fn.py:110); nothing filtered"}, err
     kept, org, logs, stats, ferr = filter_owned_texts(texts, names, owner, lambda seqs, part_of, n_parts: ops.filter_cover(part, seqs, part_of, n_parts),
-                                                      ops.filter_count, getattr(ops, "device", None), group, tick, lock)
+                                                      ops.filter_count, ops.device, group, clock)
     return kept, {"org": org, "logs": logs, "stats": stats}, err or ferr
 
 
@@ -435,7 +528,7 @@ def _runs_of(owner, d):
     return [tuple(r) for r in runs]
 
 
-def filter_owned_texts(texts, names, owner, cover, count, device=None, group=None, tick=None, lock=None):
+def filter_owned_texts(texts, names, owner, cover, count, device=None, group=None, clock=None):
     """--filter_FP on N ranks (filter_FP.py:29-55 as run_MB_SF_fn.py:272-277 runs it per partition).  A fragment lives on one rank; its
     minimum cost and the placements that attain it depend on the fragment and on its partition's transcripts alone, and coverage is a
     set union over fragments: the OR over the ranks of what each rank's pairs cover IS the one-process bitmap, provided every rank
@@ -448,105 +541,89 @@ def filter_owned_texts(texts, names, owner, cover, count, device=None, group=Non
     2. cover; 3. for every owner the words under each run of its partitions (one all-to-all of bytes; a boundary word may carry a
     neighbour's bits, count ignores them), the owner counts over the W pieces; 4. the owner decides (filter_fp._filter_records).
     Every rank reaches every collective: a rank whose cover or count raises goes on with zeros and returns the message.
-    lock: held on entry and on return, released around the collectives.
+    clock: one stage "filter_FP" with the three collectives inside it (Clock); called between two stages.
     Returns (kept {i: text}, org {i: text as given}, logs {i: rec.log text}, stats summed over the ranks, error or None)."""
-    import time
     from . import filter_fp as ffp
     W, rank = dist.get_world_size(group), dist.get_rank(group)
-    lock = lock or _NoLock()
-    tick = tick or (lambda name, t0: None)
+    clock = clock or Clock()
     cdev = exchange.coll_device(device, group)
     P = len(names)
     err = None
-    # ---- 1. texts to every rank
-    t0 = time.time()
-    mine = {int(i): _as_bytes(t) for i, t in texts.items()}
-    buf = _pack_columns({i: [a] for i, a in mine.items()}, 1)
-    tick("filter_FP", t0)
-    lock.release()
-    t0 = time.time()
-    got = exchange.all_gather_arrays((buf,), cdev, group, "filter_FP texts (the owners' unfiltered transcripts to every rank, all-gather)")
-    tick("x:filter_FP texts", t0)
-    lock.acquire()
-    t0 = time.time()
-    n_words = 0
-    seqs, part_of, first = [], [], np.zeros(P + 1, dtype=np.int64)
-    parsed = [([], [])] * P
-    try:
-        every = {}
-        for (b,) in got:
-            every.update({i: cols[0] for i, cols in _unpack_columns(b, 1).items()})
-        parsed = [ffp.records(every[i]) if i in every else ([], []) for i in range(P)]
-        for i, (_nm, sq) in enumerate(parsed):
-            seqs += sq
-            part_of += [i] * len(sq)
-            first[i + 1] = len(seqs)
-        t_off = ffp.text_offsets(seqs)
-        n_words = (int(t_off[-1]) + 63) // 64
-    except Exception as ex:
-        err = "%s: %s" % (type(ex).__name__, ex)
-        seqs, part_of, first, t_off = [], [], np.zeros(P + 1, dtype=np.int64), np.zeros(1, np.uint64)
-    # ---- 2. what this rank's routes cover
-    st = {}
-    bitmap = None
-    if err is None:
+    with clock.stage("filter_FP"):
+        # ---- 1. texts to every rank
+        mine = {int(i): _as_bytes(t) for i, t in texts.items()}
+        buf = _pack_columns({i: [a] for i, a in mine.items()}, 1)
+        with clock.collective("x:filter_FP texts"):
+            got = exchange.all_gather_arrays((buf,), cdev, group, "filter_FP texts (the owners' unfiltered transcripts to every rank, all-gather)")
+        n_words = 0
+        seqs, part_of, first = [], [], np.zeros(P + 1, dtype=np.int64)
+        parsed = [([], [])] * P
         try:
-            bitmap, st = cover(seqs, part_of, P)
-            bitmap = np.ascontiguousarray(bitmap, dtype=np.uint64)
-            if bitmap.shape != (n_words,):
-                raise ValueError("filter_owned_texts: a bitmap of %s words for a text of %d" % (bitmap.shape, n_words))
-        except Exception as ex:
-            err, bitmap = "%s: %s" % (type(ex).__name__, ex), None
-    if bitmap is None:
-        bitmap = np.zeros(n_words, dtype=np.uint64)
-    # ---- 3. the words under every owner's partitions to that owner
-    def windows(d):           # [(first transcript, behind the last, first word, behind the last word)] per run of d's partitions
-        out = []
-        for a, b in _runs_of(owner, d):
-            ta, tb = int(first[a]), int(first[b])
-            if tb > ta:
-                out.append((ta, tb, int(t_off[ta]) >> 6, (int(t_off[tb]) + 63) // 64))
-        return out
-    send = [np.concatenate([bitmap[w0:w1] for _a, _b, w0, w1 in windows(d)] + [np.zeros(0, np.uint64)]).view(np.uint8) for d in range(W)]
-    tick("filter_FP", t0)
-    lock.release()
-    t0 = time.time()
-    got = exchange.all_to_all_bytes(send, device, group, "filter_FP coverage (every rank's bitmap words under an owner's partitions, all-to-all)")
-    tick("x:filter_FP coverage", t0)
-    lock.acquire()
-    t0 = time.time()
-    hits = np.zeros(len(seqs), dtype=np.uint32)
-    if err is None:
-        try:
-            pieces = [np.ascontiguousarray(b).view(np.uint64) for b in got]
-            at = 0
-            for ta, tb, w0, w1 in windows(rank):
-                covers = np.stack([p_[at:at + (w1 - w0)] for p_ in pieces])
-                hits[ta:tb] = count(covers, t_off[ta:tb + 1], w0)
-                at += w1 - w0
+            every = {}
+            for (b,) in got:
+                every.update({i: cols[0] for i, cols in _unpack_columns(b, 1).items()})
+            parsed = [ffp.records(every[i]) if i in every else ([], []) for i in range(P)]
+            for i, (_nm, sq) in enumerate(parsed):
+                seqs += sq
+                part_of += [i] * len(sq)
+                first[i + 1] = len(seqs)
+            t_off = ffp.text_offsets(seqs)
+            n_words = (int(t_off[-1]) + 63) // 64
         except Exception as ex:
             err = "%s: %s" % (type(ex).__name__, ex)
-    # ---- 4. the owner decides
-    kept, org, logs = {}, {}, {}
-    n_tr = n_kept = 0
-    for i in sorted(mine):
-        nm, sq = parsed[i]
-        k, lg = "", ""
+            seqs, part_of, first, t_off = [], [], np.zeros(P + 1, dtype=np.int64), np.zeros(1, np.uint64)
+        # ---- 2. what this rank's routes cover
+        st = {}
+        bitmap = None
         if err is None:
             try:
-                k, lg = ffp._filter_records(nm, sq, hits[int(first[i]):int(first[i + 1])].tolist())
+                bitmap, st = cover(seqs, part_of, P)
+                bitmap = np.ascontiguousarray(bitmap, dtype=np.uint64)
+                if bitmap.shape != (n_words,):
+                    raise ValueError("filter_owned_texts: a bitmap of %s words for a text of %d" % (bitmap.shape, n_words))
+            except Exception as ex:
+                err, bitmap = "%s: %s" % (type(ex).__name__, ex), None
+        if bitmap is None:
+            bitmap = np.zeros(n_words, dtype=np.uint64)
+        # ---- 3. the words under every owner's partitions to that owner
+        def windows(d):           # [(first transcript, behind the last, first word, behind the last word)] per run of d's partitions
+            out = []
+            for a, b in _runs_of(owner, d):
+                ta, tb = int(first[a]), int(first[b])
+                if tb > ta:
+                    out.append((ta, tb, int(t_off[ta]) >> 6, (int(t_off[tb]) + 63) // 64))
+            return out
+        send = [np.concatenate([bitmap[w0:w1] for _a, _b, w0, w1 in windows(d)] + [np.zeros(0, np.uint64)]).view(np.uint8) for d in range(W)]
+        with clock.collective("x:filter_FP coverage"):
+            got = exchange.all_to_all_bytes(send, device, group, "filter_FP coverage (every rank's bitmap words under an owner's partitions, all-to-all)")
+        hits = np.zeros(len(seqs), dtype=np.uint32)
+        if err is None:
+            try:
+                pieces = [np.ascontiguousarray(b).view(np.uint64) for b in got]
+                at = 0
+                for ta, tb, w0, w1 in windows(rank):
+                    covers = np.stack([p_[at:at + (w1 - w0)] for p_ in pieces])
+                    hits[ta:tb] = count(covers, t_off[ta:tb + 1], w0)
+                    at += w1 - w0
             except Exception as ex:
                 err = "%s: %s" % (type(ex).__name__, ex)
-        kept[i], org[i], logs[i] = k, mine[i], lg
-        n_tr += len(sq)
-        n_kept += k.count(">")
-    tick("filter_FP", t0)
-    lock.release()
-    t0 = time.time()
-    parts = exchange.all_gather_object((int(st.get("routes", 0)), int(st.get("placed", 0)), n_tr, n_kept), group, "filter_FP counters")
-    tick("x:filter_FP coverage", t0)
-    lock.acquire()
-    tot = np.asarray(parts, dtype=np.int64).sum(axis=0).tolist()
+        # ---- 4. the owner decides
+        kept, org, logs = {}, {}, {}
+        n_tr = n_kept = 0
+        for i in sorted(mine):
+            nm, sq = parsed[i]
+            k, lg = "", ""
+            if err is None:
+                try:
+                    k, lg = ffp._filter_records(nm, sq, hits[int(first[i]):int(first[i + 1])].tolist())
+                except Exception as ex:
+                    err = "%s: %s" % (type(ex).__name__, ex)
+            kept[i], org[i], logs[i] = k, mine[i], lg
+            n_tr += len(sq)
+            n_kept += k.count(">")
+        with clock.collective("x:filter_FP coverage"):
+            parts = exchange.all_gather_object((int(st.get("routes", 0)), int(st.get("placed", 0)), n_tr, n_kept), group, "filter_FP counters")
+        tot = np.asarray(parts, dtype=np.int64).sum(axis=0).tolist()
     return kept, org, logs, dict(zip(("routes", "placed", "transcripts", "kept"), tot)), err
 
 
@@ -602,58 +679,54 @@ def _unpack_columns(b, ncol):
     return out
 
 
-def _gather_and_merge(texts, names, res, gk, group, rank, W, lock, tick, error=None, ops=None, double_stranded=True, extra=None):
-    """the per-partition FASTA of every owner to rank 0, which merges (shannon.py:584-604).  error: what went wrong in this rank's
+def _gather_and_merge(texts, names, res, n_k1mers, group, clock=None, error=None, device=None, ctx=None, double_stranded=True, extra=None):
+    """6. The per-partition FASTA of every owner to rank 0, which merges (shannon.py:584-604).  error: what went wrong in this rank's
     graph stage, if anything -- it travels with the gather, so every rank raises together and none is left waiting.
     extra (--filter_FP): {"org", "logs": {i: text}, "stats"} -- the unfiltered texts and the rec.log texts travel beside the kept
     ones (three columns per partition instead of one), rank 0's dict gains partitions_org / filter_logs / filter_fp_stats; or
-    {"note": ...} for a run that was not filtered."""
-    import time
-    t0 = time.time()
-    # what went wrong, if anything (a few bytes per rank); then the texts as bytes to rank 0 -- what rank 0 produced itself stays put
-    errs = exchange.all_gather_object(error, group, "FASTA gather (status of the ranks)")
-    errors = ["rank %d: %s" % (r, e) for r, e in enumerate(errs) if e]
-    if errors:
-        tick("x:gather fasta", t0)
-        raise RuntimeError("graph stage failed on " + "; ".join(errors))
+    {"note": ...} for a run that was not filtered.  device, ctx: the ops' (where the bytes are staged; the merge on the device).
+    Collectives ("x:gather fasta"): the status of the ranks (one all-gather of objects), the texts (one all-to-all of bytes)."""
+    W, rank = dist.get_world_size(group), dist.get_rank(group)
+    clock = clock or Clock()
     filtered = extra is not None and "org" in extra
     ncol = 3 if filtered else 1
-    mine = {int(i): [_as_bytes(t)] + ([_as_bytes(extra["org"][i]), _as_bytes(extra["logs"][i])] if filtered else []) for i, t in texts.items()}
     cols = {}
-    if W > 1:
-        if rank != 0:
-            out = _pack_columns(mine, ncol)
-        bufs = [out if (d == 0 and rank != 0) else np.zeros(0, np.uint8) for d in range(W)]
-        got = exchange.all_to_all_bytes(bufs, getattr(ops, "device", None), group, "FASTA gather (per-partition transcripts to rank 0)")
-        if rank == 0:
-            for src, b in enumerate(got):
-                if src != 0:
-                    cols.update(_unpack_columns(b, ncol))
-    tick("x:gather fasta", t0)
+    with clock.collective("x:gather fasta"):
+        # what went wrong, if anything (a few bytes per rank); then the texts as bytes to rank 0 -- what rank 0 produced itself stays put
+        errs = exchange.all_gather_object(error, group, "FASTA gather (status of the ranks)")
+        errors = ["rank %d: %s" % (r, e) for r, e in enumerate(errs) if e]
+        if errors:
+            raise RuntimeError("graph stage failed on " + "; ".join(errors))
+        mine = {int(i): [_as_bytes(t)] + ([_as_bytes(extra["org"][i]), _as_bytes(extra["logs"][i])] if filtered else []) for i, t in texts.items()}
+        if W > 1:
+            if rank != 0:
+                out = _pack_columns(mine, ncol)
+            bufs = [out if (d == 0 and rank != 0) else np.zeros(0, np.uint8) for d in range(W)]
+            got = exchange.all_to_all_bytes(bufs, device, group, "FASTA gather (per-partition transcripts to rank 0)")
+            if rank == 0:
+                for src, b in enumerate(got):
+                    if src != 0:
+                        cols.update(_unpack_columns(b, ncol))
     if rank != 0:
         return None
-    lock.acquire()
-    t0 = time.time()
-    cols.update(mine)
-    merged = {i: c[0] for i, c in cols.items()}
-    single = "".join(">Single_%d\n%s\n" % (i, c) for i, c in enumerate(res.single_contigs))
-    order = [merged[i] for i in range(len(names))]
-    # the merge over the texts as they are (process_concatenated_fasta.py + faster_reps.py: post.finalize_texts, on the device when
-    # the ops have a context); transcripts with characters outside ACGT go through the Python form
-    try:
-        final = post.finalize_texts([single] + order, double_stranded, ctx=getattr(ops, "ctx", None))
-    except _lib.ShannonError as ex:
-        if "non-ACGT" not in str(ex) and "empty line" not in str(ex):
-            raise
-        lines = single.splitlines(True)
-        for a in order:
-            lines += bytes(memoryview(a)).decode().splitlines(True)
-        final = post.finalize(lines, double_stranded)
-    parts = _Texts(names, order)
-    tick("merge (rank 0)", t0)
-    lock.release()
-    out = {"partitions": parts, "final": final, "contigs": res.contigs,
-           "n_k1mers": int(gk.numel()) if gk is not None else int(getattr(res, "n_k1mers_table", 0)),
+    with clock.stage("merge (rank 0)"):
+        cols.update(mine)
+        merged = {i: c[0] for i, c in cols.items()}
+        single = "".join(">Single_%d\n%s\n" % (i, c) for i, c in enumerate(res.single_contigs))
+        order = [merged[i] for i in range(len(names))]
+        # the merge over the texts as they are (process_concatenated_fasta.py + faster_reps.py: post.finalize_texts, on the device when
+        # there is a context); transcripts with characters outside ACGT go through the Python form
+        try:
+            final = post.finalize_texts([single] + order, double_stranded, ctx=ctx)
+        except _lib.ShannonError as ex:
+            if "non-ACGT" not in str(ex) and "empty line" not in str(ex):
+                raise
+            lines = single.splitlines(True)
+            for a in order:
+                lines += bytes(memoryview(a)).decode().splitlines(True)
+            final = post.finalize(lines, double_stranded)
+        parts = _Texts(names, order)
+    out = {"partitions": parts, "final": final, "contigs": res.contigs, "n_k1mers": int(n_k1mers or 0),
            "extension": {k: getattr(res, k, None) for k in ("iterations", "n_walks", "total_steps", "wave_steps", "fresh_steps", "dense_rounds")}}
     if filtered:
         out["partitions_org"] = _Texts(names, [cols[i][1] for i in range(len(names))])
@@ -673,7 +746,7 @@ def _a2a_objects(recv, payload, group):
         recv[src] = everything[src][rank]
 
 
-def component_table(cc, group, tick, lock, dev):
+def component_table(cc, group, clock=None, dev=None):
     """Component labelling on owner shards, the collectives around it.  cc: this rank's shard behind the steps of
     include/shannon_hip.h's shn_cc_* (GpuOps: the device kernels; the CPU tests: a numpy restatement) --
       cc.n                                     k1-mers of the shard
@@ -685,75 +758,58 @@ def component_table(cc, group, tick, lock, dev):
       cc.shard(glabel, big labels ascending, their ranks) -> (keys i64, counts i32, per destination rank)
     Collectives: the shard sizes (all-gather), the queries (all-to-all), the edges (all-gather), the sizes of the large components
     (objects), the pairs of whole components (all-to-all).  Returns ((keys, counts) received: this rank's components, k1-mers of
-    the job).  lock: held while this rank computes (see assemble_distributed)."""
-    import time
+    the job).  clock: the "labels: ..." stages and the collectives between them (Clock); called between two stages."""
     W, rank = dist.get_world_size(group), dist.get_rank(group)
-    lock = lock or _NoLock()
+    clock = clock or Clock()
     cdev = exchange.coll_device(dev, group)
-    t0 = time.time()
-    n_loc = int(cc.n)
-    qk, ql, per = cc.queries()
-    tick("labels: local components + queries", t0)
-    lock.release()
-    t0 = time.time()
-    nt = torch.tensor([n_loc], dtype=torch.int64, device=cdev)
-    nts = [torch.zeros_like(nt) for _ in range(W)]
-    dist.all_gather(nts, nt, group=group)
-    sizes = [int(x.item()) for x in nts]
-    base = [sum(sizes[:r]) for r in range(W)]
-    n_glob = sum(sizes)
-    rk, rl, rcl = exchange.all_to_all_pairs(qk, ql, per, group, name="component labelling: neighbour queries to the owners (all-to-all)")
-    del qk, ql
-    tick("x:label queries", t0)
-    lock.acquire()
-    t0 = time.time()
-    edges = cc.answer(rk, rl, rcl, base)
-    del rk, rl
-    tick("labels: answers", t0)
-    lock.release()
-    t0 = time.time()
-    ge, _ = _all_gather_var(edges, group, name="component labelling: edges between shards (all-gather)")
-    del edges
-    tick("x:label edges", t0)
-    lock.acquire()
-    t0 = time.time()
-    ids, labels = cc.solve(ge, n_glob + 1)
-    del ge
-    glabel = cc.labels(base[rank], ids, labels)
-    del ids, labels
-    # the large components are balanced by size (largest first onto the least loaded rank, as shn_extend_sharded does on a
-    # replicated table); everything else goes by the hash of its label.  A component of T k1-mers spread evenly has T / W of them
-    # here: every rank reports what it holds of components above a quarter of that, every rank sums the same reports.
-    T = max(1024, n_glob // (64 * W))
-    mine = cc.sizes(glabel, max(32, T // (4 * W)))
-    tick("labels: component graph", t0)
-    lock.release()
-    t0 = time.time()
-    parts = exchange.all_gather_object(mine, group, "component labelling: sizes of the large components")
-    tick("x:label sizes", t0)
-    lock.acquire()
-    t0 = time.time()
-    tot = {}
-    for lab, cnt in parts:
-        for a, b in zip(np.asarray(lab).tolist(), np.asarray(cnt).tolist()):
-            tot[a] = tot.get(a, 0) + b
-    big = sorted((a for a, b in tot.items() if b >= T // 2), key=lambda a: (-tot[a], a))
-    load = [0] * W
-    own = {}
-    for a in big:
-        r = min(range(W), key=lambda q: (load[q], q))
-        own[a] = r
-        load[r] += tot[a]
-    bl = sorted(own)
-    sk, sc, send = cc.shard(glabel, np.asarray(bl, dtype=np.int64), np.asarray([own[a] for a in bl], dtype=np.uint8))
-    del glabel
-    tick("labels: owners + shard", t0)
-    lock.release()
-    t0 = time.time()
-    rk, rc, _ = exchange.all_to_all_pairs(sk, sc, send, group, name="component exchange (the k1-mers of whole components to their rank, all-to-all)")
-    del sk, sc
-    tick("x:component exchange", t0)
-    lock.acquire()
+    with clock.stage("labels: local components + queries"):
+        n_loc = int(cc.n)
+        qk, ql, per = cc.queries()
+    with clock.collective("x:label queries"):
+        nt = torch.tensor([n_loc], dtype=torch.int64, device=cdev)
+        nts = [torch.zeros_like(nt) for _ in range(W)]
+        dist.all_gather(nts, nt, group=group)
+        sizes = [int(x.item()) for x in nts]
+        base = [sum(sizes[:r]) for r in range(W)]
+        n_glob = sum(sizes)
+        rk, rl, rcl = exchange.all_to_all_pairs(qk, ql, per, group, name="component labelling: neighbour queries to the owners (all-to-all)")
+        del qk, ql
+    with clock.stage("labels: answers"):
+        edges = cc.answer(rk, rl, rcl, base)
+        del rk, rl
+    with clock.collective("x:label edges"):
+        ge, _ = _all_gather_var(edges, group, name="component labelling: edges between shards (all-gather)")
+        del edges
+    with clock.stage("labels: component graph"):
+        ids, labels = cc.solve(ge, n_glob + 1)
+        del ge
+        glabel = cc.labels(base[rank], ids, labels)
+        del ids, labels
+        # the large components are balanced by size (largest first onto the least loaded rank, as shn_extend_sharded does on a
+        # replicated table); everything else goes by the hash of its label.  A component of T k1-mers spread evenly has T / W of them
+        # here: every rank reports what it holds of components above a quarter of that, every rank sums the same reports.
+        T = max(1024, n_glob // (64 * W))
+        mine = cc.sizes(glabel, max(32, T // (4 * W)))
+    with clock.collective("x:label sizes"):
+        parts = exchange.all_gather_object(mine, group, "component labelling: sizes of the large components")
+    with clock.stage("labels: owners + shard"):
+        tot = {}
+        for lab, cnt in parts:
+            for a, b in zip(np.asarray(lab).tolist(), np.asarray(cnt).tolist()):
+                tot[a] = tot.get(a, 0) + b
+        big = sorted((a for a, b in tot.items() if b >= T // 2), key=lambda a: (-tot[a], a))
+        load = [0] * W
+        own = {}
+        for a in big:
+            r = min(range(W), key=lambda q: (load[q], q))
+            own[a] = r
+            load[r] += tot[a]
+        bl = sorted(own)
+        sk, sc, send = cc.shard(glabel, np.asarray(bl, dtype=np.int64), np.asarray([own[a] for a in bl], dtype=np.uint8))
+        del glabel
+    with clock.collective("x:component exchange"):
+        rk, rc, _ = exchange.all_to_all_pairs(sk, sc, send, group, name="component exchange (the k1-mers of whole components to their rank, all-to-all)")
+        del sk, sc
     return (rk, rc), n_glob
 
 
@@ -813,7 +869,7 @@ class _GpuComponents(object):
         self.cc.close()
 
 
-class GpuOps(object):
+class GpuOps(RankOps):
     """Per-rank compute on the local GPU through the C ABI."""
 
     def __init__(self, ctx, d1, d2, store, K):
@@ -824,8 +880,6 @@ class GpuOps(object):
         self._dev = device
 
     supports_strand_specific = True
-    strand_specific = False              # set by assemble_distributed
-    min_weight, min_length, kmer_hard_cutoff = 3, 75, 1      # set by assemble_distributed (shannon.py:55-57, 237-247)
 
     def n_reads(self):
         return len(self.d1)
@@ -847,12 +901,10 @@ class GpuOps(object):
     def owner_labelling(self):
         """components labelled on the owner shards, no replicated table (SHN_OWNER_LABELS=0: the table all-gathered to every rank and
         labelled there -- the path of rounds 2-4, kept for comparison)"""
-        import os
         return os.environ.get("SHN_OWNER_LABELS", "1") != "0"
 
     def _digest(self, name, table):
         """SHN_DIST_DIGEST=1 (diagnostics): a checksum of a table's sorted (key, count) pairs per stage, in self.digests"""
-        import os
         if os.environ.get("SHN_DIST_DIGEST") != "1":
             return
         import hashlib
@@ -880,25 +932,22 @@ class GpuOps(object):
         self._digest("owned", t)
         return t
 
-    def component_table(self, owned, group, tick):
+    def component_table(self, owned, group):
         """owned: this rank's shard of the k1-mers (by minimizer).  Returns (a table of the whole components dealt to this rank,
-        the number of k1-mers of the job): component_table() below with the device kernels (include/shannon_hip.h: shn_cc_*)."""
-        import time
+        the number of k1-mers of the job): component_table() above with the device kernels (include/shannon_hip.h: shn_cc_*)."""
         W, rank = dist.get_world_size(group), dist.get_rank(group)
         n_loc = len(owned)
-        t0 = time.time()
-        cc = _GpuComponents(self, owned, W, rank)
-        tick("labels: local components + queries", t0)
+        with self.clock.stage("labels: local components + queries"):
+            cc = _GpuComponents(self, owned, W, rank)
         try:
-            pairs, n_glob = component_table(cc, group, tick, getattr(self, "lock", None), self.device)
+            pairs, n_glob = component_table(cc, group, self.clock, self.device)
         finally:
             cc.close()
-        t0 = time.time()
-        owned.close()
-        rk, rc = pairs
-        torch.cuda.synchronize()
-        table = self._dev.Table.from_pairs(self.ctx, rk.data_ptr(), rc.data_ptr(), rk.numel(), self.K + 1, not self.strand_specific)
-        tick("table", t0)
+        with self.clock.stage("table"):
+            owned.close()
+            rk, rc = pairs
+            torch.cuda.synchronize()
+            table = self._dev.Table.from_pairs(self.ctx, rk.data_ptr(), rc.data_ptr(), rk.numel(), self.K + 1, not self.strand_specific)
         self._digest("components", table)
         self.component_table_sizes = (int(n_loc), int(len(table)), int(n_glob))      # owned shard, walked table, the job (tests, bench)
         return table, n_glob
@@ -924,17 +973,12 @@ class GpuOps(object):
         return t
 
     graph_threads = 8
-    sharded_extension = True
 
     @property
     def resident_rows(self):
         """a partition whose routed reads are all rows of this rank's resident input is handed to the graph stage by rows"""
-        def _matrix(m):
-            return isinstance(m, np.ndarray) and m.dtype == np.uint8 and m.ndim == 2 and m.flags["C_CONTIGUOUS"]
-        import os
-        # (mates of two different lengths: the duplicate search on the device takes read sets of one length, as in pipeline.py)
-        return (self.unitigs is not None and _matrix(getattr(self.store, "r1", None)) and (not self.paired or _matrix(getattr(self.store, "r2", None)))
-                and self.one_length and os.environ.get("SHN_GRAPH_ROWS", "1") != "0")
+        # (one_length: the duplicate search on the device takes read sets of one length, as in pipeline.py; -s: the driver excludes it)
+        return self.unitigs is not None and graph_intake.rows_possible(self.store, self.d1, self.d2, self.paired, False) and self.one_length
     array_payload = True               # collect() returns (code rows, strand flags): travels as bytes, not as pickles
 
     def extension(self, table, partition_size, group=None, presharded=None):
@@ -942,42 +986,28 @@ class GpuOps(object):
         contigs + their connections (a few MB) are all-gathered and merged in the global walk order.
         presharded = the number of k1-mers of the job: `table` holds the whole components dealt to this rank already (component_table);
         the walks are the unsharded ones on it, everything after them as before."""
-        import time
         from . import extension_correction as ec
         W, rank = dist.get_world_size(group), dist.get_rank(group)
-        lock = getattr(self, "lock", None) or _NoLock()
-        self.coll_wait = 0.0               # seconds inside the contig stage's collectives (waiting for the slowest rank included)
+        clock, cdev = self.clock, exchange.coll_device(self.device, group)
 
-        class Gather(object):                     # the collectives of the sharded contig stage
-            world, rank = W, None
+        class Gather(object):                     # the collectives of the sharded contig stage (waiting for the slowest rank included)
+            world = W
 
             @staticmethod
             def all_gather(obj):
-                lock.release()
-                t0 = time.time()
-                parts = exchange.all_gather_object(obj, group, "contig gathers (accepted contigs + connections of the shards)")
-                self.coll_wait += time.time() - t0
-                lock.acquire()
-                return parts
+                with clock.collective("x:contig gathers"):
+                    return exchange.all_gather_object(obj, group, "contig gathers (accepted contigs + connections of the shards)")
 
             @staticmethod
             def all_gather_arrays(arrays):
-                lock.release()
-                t0 = time.time()
-                parts = exchange.all_gather_arrays(arrays, exchange.coll_device(self.device, group), group,
-                                                   "contig gathers (candidates of the shards: seed weights, keys, offsets, text)")
-                self.coll_wait += time.time() - t0
-                lock.acquire()
-                return parts
+                with clock.collective("x:contig gathers"):
+                    return exchange.all_gather_arrays(arrays, cdev, group, "contig gathers (candidates of the shards: seed weights, keys, offsets, text)")
 
             @staticmethod
             def all_reduce_max(v):
-                t = torch.tensor([int(v)], dtype=torch.int64, device=exchange.coll_device(self.device, group))
-                lock.release()
-                t0 = time.time()
-                dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
-                self.coll_wait += time.time() - t0
-                lock.acquire()
+                t = torch.tensor([int(v)], dtype=torch.int64, device=cdev)
+                with clock.collective("x:contig gathers"):
+                    dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
                 return int(t.item())
 
         Gather.rank = rank
@@ -985,21 +1015,18 @@ class GpuOps(object):
         # "sharded walks + one replicated GPU contig stage" inside run_correction; a few deep gene families per rank -- the
         # weak-scaling workload, 5 M k1-mers per family -- keep their contig stages sharded too: SHN_CONTIG_GPU=1 / 0 forces either)
         res = ec.run_correction(self.ctx, table, self.min_weight, self.min_length, partition_size, want_allowed=False, shard=None if presharded is not None else (W, rank),
-                                gather=Gather, timings=getattr(self, "timings", None), table_size=presharded)
+                                gather=Gather, timings=clock.timings, table_size=presharded)
         table.close()
-        if presharded is not None:
-            res.n_k1mers_table = int(presharded)
         return res
 
     def route(self, res, K, partition_size, part_vectors):
         from . import kmers_for_component as kfc, mbgraph_native
-        import os
         self.unitigs, self.part_index = None, None
         # (which way collect() goes on this rank; the CLI puts it beside its stage times -- the timings dict itself holds seconds only)
         self.collect_path = "device" if self.collect_on_device else "host"
         gpu_graph = K <= 31 and os.environ.get("SHN_GRAPH_GPU", "1") != "0"
         part = kfc.kmers_for_component(self.ctx, res, self.d1, self.d2, K, partition_size, part_vectors=part_vectors, want_rows=False,
-                                       timings=getattr(self, "timings", None), lazy_routes=True, lazy_graph_inputs=gpu_graph,
+                                       timings=self.clock.timings, lazy_routes=True, lazy_graph_inputs=gpu_graph,
                                        strand_specific=self.strand_specific)
         names = list(part["new_components"])
         if gpu_graph and names:
@@ -1015,23 +1042,26 @@ class GpuOps(object):
         return part["n_kmer_nodes"][name]
 
     @staticmethod
-    def _as_ragged(data, halves=False):
-        """a fixed-length piece (rows, flags) as a RaggedPiece; halves: the rows hold the two mates of a -s pair side by side"""
-        if isinstance(data, exchange.RaggedPiece):
-            return data
-        rows, rc1 = data
+    def _split_mates(rows, halves):
+        """code rows of one length as (codes, offsets, codes of the second mates or None).  halves: the rows hold reads_1[i] and
+        reads_2[i] of a -s pair side by side (collect), both mates under the same offsets"""
         n, L2 = rows.shape
         L = L2 // 2 if halves else L2
         off = np.arange(n + 1, dtype=np.uint64) * np.uint64(L)
-        if not halves:
-            return exchange.RaggedPiece(rows.reshape(-1), off, rc1)
-        return exchange.RaggedPiece(np.ascontiguousarray(rows[:, :L]).reshape(-1), off, rc1, np.ascontiguousarray(rows[:, L:]).reshape(-1), off)
+        return np.ascontiguousarray(rows[:, :L]).reshape(-1), off, (np.ascontiguousarray(rows[:, L:]).reshape(-1) if halves else None)
+
+    @staticmethod
+    def _as_ragged(data, halves=False):
+        """a fixed-length piece (rows, flags) as a RaggedPiece; halves: see _split_mates"""
+        if isinstance(data, exchange.RaggedPiece):
+            return data
+        b1, off, b2 = GpuOps._split_mates(data[0], halves)
+        return exchange.RaggedPiece(b1, off, data[1], b2, off if halves else None)
 
     @staticmethod
     def _merge_ragged(pieces, halves=False):
         """_merge_pieces for pieces that carry lengths: one RaggedPiece in the order of the global indices (a stable sort of the
         indices, one gather of the reads' runs of codes per mate)"""
-        from . import _lib
         gidx = np.concatenate([g for g, _ in pieces])
         ps = [GpuOps._as_ragged(d, halves) for _, d in pieces]
         if any(p.paired != ps[0].paired for p in ps):
@@ -1066,22 +1096,21 @@ class GpuOps(object):
         rows = np.ascontiguousarray(pieces[0][1][0] if one else np.concatenate([d[0] for _, d in pieces]))
         rc1 = np.ascontiguousarray(pieces[0][1][1] if one else np.concatenate([d[1] for _, d in pieces]))
         if len(gidx) > 1 and not bool((gidx[1:] > gidx[:-1]).all()):      # (one source rank: already in order)
-            from . import _lib
             order = np.argsort(gidx, kind="stable")
             rows = _lib.gather_rows(rows, order)
             rc1 = np.ascontiguousarray(rc1[order])
         return rows, rc1
 
-    def graph_batch(self, part, names, owned, mine, K, paired, sample, seed, T):
+    def graph_batch(self, part, names, owned, mine, K, paired, sample, seed):
         """multibridging.main + algorithm_SF for the owned partitions, as the single-GPU pipeline runs them: the received code rows
         become a resident read set of their own (row i forward = doubled index i, reverse strand = n + i), the distinct reads are
-        found on the device (shn_mbgraph_run_rows), all components go through shn_sparse_flow in one call.  {partition: FASTA}."""
-        import time, threading
+        found on the device (shn_mbgraph_run_rows), all components go through shn_sparse_flow in one call.  {partition: FASTA};
+        None without unitigs (SHN_GRAPH_GPU=0, K > 31): graph() per partition then."""
+        import threading
         from concurrent.futures import ThreadPoolExecutor
-        from . import mbgraph_native, _lib, graph_intake
+        from . import mbgraph_native
         if self.unitigs is None:
             return None
-        t0 = time.time()
         up = threading.Lock()
 
         def one(i):
@@ -1091,23 +1120,12 @@ class GpuOps(object):
             ragged = merged if isinstance(merged, exchange.RaggedPiece) else None
             rows, rc1 = (np.zeros((0, 1), np.uint8), np.zeros(0, np.uint8)) if ragged is not None else merged
             def run(rb):
-                if ragged is not None:
-                    # reads that carry their lengths: codes + offsets straight to the graph stage, as the one-process path hands
-                    # ragged reads over (pipeline.py: gather_codes / gather_codes_ss -> run_partition_handle)
-                    b1, o1, b2, o2, r1, r2 = self._ragged_args(ragged, paired)
+                if ragged is not None or (self.strand_specific and len(rows)):
+                    # reads that carry their lengths, or -s rows: codes + offsets straight to the graph stage, as the one-process
+                    # path hands them over (pipeline.py: gather_codes / gather_codes_ss -> run_partition_handle)
+                    b1, o1, b2, o2, r1, r2 = self._ragged_args(ragged, paired) if ragged is not None else self._rows_args(rows, rc1, paired)
                     return mbgraph_native.run_partition_handle(rb, 0 if rb is None else len(rb) // (K + 1), K, b1, o1, b2, o2, ctx=self.ctx, enc=1,
                                                                rc1=r1, rc2=r2, unitigs=self.unitigs, part=i)
-                if self.strand_specific and len(rows):
-                    # -s: the rows hold reads_1[i] and, for pairs, reads_2[i] side by side (collect); the second mate is read on its
-                    # reverse strand (rc2 = 1): the pairs (reads_1[i], RC(reads_2[i])) of shannon.py:407-411, not strand-doubled
-                    n, L2 = rows.shape
-                    L = L2 // 2 if paired else L2
-                    b1 = np.ascontiguousarray(rows[:, :L]).reshape(-1)
-                    o1 = np.arange(n + 1, dtype=np.uint64) * np.uint64(L)
-                    b2 = np.ascontiguousarray(rows[:, L:]).reshape(-1) if paired else None
-                    return mbgraph_native.run_partition_handle(rb, 0 if rb is None else len(rb) // (K + 1), K, b1, o1, b2, o1 if paired else None,
-                                                               ctx=self.ctx, enc=1, rc1=np.zeros(n, np.uint8), rc2=np.ones(n, np.uint8) if paired else None,
-                                                               unitigs=self.unitigs, part=i)
                 if local is not None and len(local):
                     # this rank's own reads, named by their rows in its resident input (as pipeline.assemble_resident does)
                     return mbgraph_native.run_partition_rows(self.ctx, self.unitigs, i, self.d1, self.d2 if paired else None, self.store.r1,
@@ -1129,17 +1147,16 @@ class GpuOps(object):
         nthreads = max(1, min(len(owned), _lib.host_cpus()))
         graphs, futs = [], []
         try:
-            if nthreads > 1:
-                with ThreadPoolExecutor(max_workers=nthreads) as pool:
-                    futs = [pool.submit(one, i) for i in owned]
-                    graphs = [f.result() for f in futs]
-            else:
-                for i in owned:
-                    graphs.append(one(i))
-            T["graph"] = T.get("graph", 0.0) + time.time() - t0
-            t0 = time.time()
-            texts = mbgraph_native.sparse_flow_native(self.ctx, graphs, ["%s_%s" % (sample, names[i]) for i in owned], seed, raw=True) if owned else []
-            T["sparse flow"] = T.get("sparse flow", 0.0) + time.time() - t0
+            with self.clock.stage("graph"):
+                if nthreads > 1:
+                    with ThreadPoolExecutor(max_workers=nthreads) as pool:
+                        futs = [pool.submit(one, i) for i in owned]
+                        graphs = [f.result() for f in futs]
+                else:
+                    for i in owned:
+                        graphs.append(one(i))
+            with self.clock.stage("sparse flow"):
+                texts = mbgraph_native.sparse_flow_native(self.ctx, graphs, ["%s_%s" % (sample, names[i]) for i in owned], seed, raw=True) if owned else []
             return {i: txt for i, txt in zip(owned, texts)}
         finally:
             # whatever happened: the graphs built so far and the unitigs go back now (a failing partition must not leave them to
@@ -1165,6 +1182,17 @@ class GpuOps(object):
             return b1, m.off, None, None, m.rc, None
         return b1, m.off, b1, m.off, m.rc, (1 - m.rc).astype(np.uint8)
 
+    def _rows_args(self, rows, rc1, paired):
+        """_ragged_args for merged code rows of one length + strand flags.  -s: reads_1[i] and, for pairs, reads_2[i] side by side
+        (collect), the second mate read on its reverse strand -- the pairs (reads_1[i], RC(reads_2[i])) of shannon.py:407-411"""
+        ss = self.strand_specific and len(rows) > 0
+        b1, o1, b2 = self._split_mates(rows, ss and paired)
+        o2 = o1 if paired else None
+        if ss:
+            return b1, o1, b2, o2, np.zeros(len(rows), np.uint8), (np.ones(len(rows), np.uint8) if paired else None)
+        b1 = b1 if b1.size else np.zeros(1, np.uint8)
+        return b1, o1, (b1 if paired else None), o2, rc1, ((1 - rc1).astype(np.uint8) if paired else None)
+
     def filter_cover(self, part, seqs, part_of, n_parts):
         """--filter_FP, this rank's half: (what ALL routes of this rank's reads cover on the transcripts `seqs`, as the bitmap of
         filter_fp.coverage_bitmap; routes looked at / fragments placed).  A rank without reads or routes covers nothing."""
@@ -1183,10 +1211,10 @@ class GpuOps(object):
     @property
     def one_length(self):
         """both stored mates are code matrices of one common read length: the pieces travel as rows"""
-        def _matrix(m):
-            return isinstance(m, np.ndarray) and m.ndim == 2
+        # (any 2-D array, not only graph_intake.is_code_matrix: a matrix of another dtype or layout still travels as rows)
         r1, r2 = getattr(self.store, "r1", None), getattr(self.store, "r2", None)
-        return _matrix(r1) and (not self.paired or (_matrix(r2) and r2.shape[1] == r1.shape[1]))
+        return (isinstance(r1, np.ndarray) and r1.ndim == 2 and
+                (not self.paired or (isinstance(r2, np.ndarray) and r2.ndim == 2 and r2.shape[1] == r1.shape[1])))
 
     @property
     def collect_on_device(self):
@@ -1254,43 +1282,14 @@ class GpuOps(object):
         return (codes[:n_sel * L].reshape(n_sel, L), rc1)
 
     def graph(self, part, name, pieces, K, paired):
+        """one partition without unitigs (graph_batch declined: SHN_GRAPH_GPU=0, K > 31): the pieces merged into the global
+        strand-doubled order -- the reference's file order -- and handed to the graph stage as codes + offsets"""
         from . import mbgraph_native
         rb = part["k1mer_bytes"][name]                     # the partition's k1-mer file as fixed-width rows
-        if any(isinstance(d, exchange.RaggedPiece) and len(g) for g, d in pieces):
-            b1, o1, b2, o2, r1, r2 = self._ragged_args(self._merge_pieces(pieces, self.strand_specific and paired), paired)
-            singles, comps, _log = mbgraph_native.run_partition_arrays(rb if len(rb) else np.zeros(1, np.uint8), len(rb) // (K + 1), K, b1, o1, b2, o2,
-                                                                       ctx=self.ctx, enc=1, rc1=r1, rc2=r2)
-            return singles, comps
-        if any(len(p[0]) for p in pieces):
-            # global strand-doubled order = the reference's file order
-            pieces = [p for p in pieces if len(p[0])]
-            one = len(pieces) == 1                                    # (no copy of a 100 MB piece)
-            gidx = pieces[0][0] if one else np.concatenate([g for g, _ in pieces])
-            rows = np.ascontiguousarray(pieces[0][1][0] if one else np.concatenate([d[0] for _, d in pieces]))
-            rc1 = np.ascontiguousarray(pieces[0][1][1] if one else np.concatenate([d[1] for _, d in pieces]))
-            if len(gidx) > 1 and not bool((gidx[1:] > gidx[:-1]).all()):      # (one source rank: already in order)
-                from . import _lib
-                order = np.argsort(gidx, kind="stable")
-                rows = _lib.gather_rows(rows, order)
-                rc1 = np.ascontiguousarray(rc1[order])
-        else:
-            rows, rc1 = np.zeros((0, 1), np.uint8), np.zeros(0, np.uint8)
-        if self.strand_specific and len(rows):
-            # -s: reads_1[i] | reads_2[i] side by side (collect), the second mate read on its reverse strand
-            n, L2 = rows.shape
-            L = L2 // 2 if paired else L2
-            off = np.arange(n + 1, dtype=np.uint64) * np.uint64(L)
-            b1 = np.ascontiguousarray(rows[:, :L]).reshape(-1)
-            b2 = np.ascontiguousarray(rows[:, L:]).reshape(-1) if paired else None
-            singles, comps, _log = mbgraph_native.run_partition_arrays(rb if len(rb) else np.zeros(1, np.uint8), len(rb) // (K + 1), K, b1, off, b2,
-                                                                       off if paired else None, ctx=self.ctx, enc=1, rc1=np.zeros(n, np.uint8),
-                                                                       rc2=np.ones(n, np.uint8) if paired else None)
-            return singles, comps
-        off = np.arange(len(rows) + 1, dtype=np.uint64) * np.uint64(rows.shape[1])
-        b1 = rows.reshape(-1) if rows.size else np.zeros(1, np.uint8)
-        singles, comps, _log = mbgraph_native.run_partition_arrays(rb if len(rb) else np.zeros(1, np.uint8), len(rb) // (K + 1), K,
-                                                                   b1, off, b1 if paired else None, off if paired else None, ctx=self.ctx,
-                                                                   enc=1, rc1=rc1, rc2=(1 - rc1).astype(np.uint8) if paired else None)
+        merged = self._merge_pieces(pieces, self.strand_specific and paired)
+        b1, o1, b2, o2, r1, r2 = self._ragged_args(merged, paired) if isinstance(merged, exchange.RaggedPiece) else self._rows_args(*merged, paired)
+        singles, comps, _log = mbgraph_native.run_partition_arrays(rb if len(rb) else np.zeros(1, np.uint8), len(rb) // (K + 1), K, b1, o1, b2, o2,
+                                                                   ctx=self.ctx, enc=1, rc1=r1, rc2=r2)
         return singles, comps
 
     def sparse_flow(self, flat, ids, seed):

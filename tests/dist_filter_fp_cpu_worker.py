@@ -56,16 +56,12 @@ def main():
         return rank_bitmap(rank, (int(ffp.text_offsets(seqs)[-1]) + 63) // 64), {"routes": 10 * (rank + 1), "placed": rank + 1}
 
     T = {}
-
-    def tick(name, t0):
-        T[name] = T.get(name, 0.0) + 1.0
-
+    clock = distributed.Clock(T)
     kept, org, logs, stats, err = distributed.filter_owned_texts(mine, names, owner, cover, lambda c, t, w: ffp.hits_from_bitmaps(None, c, t, w),
-                                                                 tick=tick)
+                                                                 clock=clock)
     msg, res = "", None
     try:
-        res = distributed._gather_and_merge(kept, names, _Res(), None, None, rank, W, distributed._NoLock(), tick, error=err,
-                                            extra={"org": org, "logs": logs, "stats": stats})
+        res = distributed._gather_and_merge(kept, names, _Res(), None, None, clock, error=err, extra={"org": org, "logs": logs, "stats": stats})
     except RuntimeError as ex:
         msg = str(ex)
     json.dump({"kept": {str(i): t for i, t in kept.items()}, "logs": {str(i): t for i, t in logs.items()}, "stats": stats, "error": msg,

@@ -12,7 +12,7 @@ from oracle import seqs, count, extension, partition, sparse_flow as osf
 from shannon_amd import distributed, exchange, kmers_for_component as kfc
 
 
-class OracleOps(object):
+class OracleOps(distributed.RankOps):
     def __init__(self, r1, r2, K):
         self.r1, self.r2, self.K = r1, r2, K
         self.paired = r2 is not None
@@ -21,8 +21,7 @@ class OracleOps(object):
         self.store = kfc.ReadStore(r1, r2)
 
     supports_strand_specific = True
-    strand_specific = False              # set by assemble_distributed
-    min_weight, min_length, kmer_hard_cutoff = 3, 75, 1      # set by assemble_distributed
+    OWN_KEY = "x:test ops: the components of all ranks"      # the one collective these ops make themselves (extension)
 
     def n_reads(self):
         return len(self.r1)
@@ -38,12 +37,12 @@ class OracleOps(object):
         k, c = self.reduce_pairs(rk, rc)
         return k.numpy().view(np.uint64), c.numpy()
 
-    def component_table(self, owned, group, tick):
+    def component_table(self, owned, group):
         """the steps of the owner-shard labelling in numpy (tests/cc_reference.py) behind the product's choreography"""
         from cc_reference import NumpyComponents
         W, rank = dist.get_world_size(group), dist.get_rank(group)
         cc = NumpyComponents(owned[0], owned[1], W, rank, self.K + 1, not self.strand_specific)
-        (rk, rc), n_glob = distributed.component_table(cc, group, tick, None, self.device)
+        (rk, rc), n_glob = distributed.component_table(cc, group, self.clock, self.device)
         self.component_keys = (owned[0], rk.numpy().view(np.uint64).copy())
         return (rk, rc), n_glob
 
@@ -101,7 +100,8 @@ class OracleOps(object):
             from cc_reference import reference_labels
             rk, rc = tab
             parts = [None] * dist.get_world_size(group)
-            dist.all_gather_object(parts, (rk.numpy().view(np.uint64), rc.numpy(), self.component_keys[0]), group=group)
+            with self.clock.collective(self.OWN_KEY):
+                dist.all_gather_object(parts, (rk.numpy().view(np.uint64), rc.numpy(), self.component_keys[0]), group=group)
             keys = np.concatenate([p[0] for p in parts])
             assert len(keys) == presharded == len(np.unique(keys)) == sum(len(p[2]) for p in parts)
             assert np.array_equal(np.sort(keys), np.sort(np.concatenate([p[2] for p in parts])))       # the owned shards, moved, not changed
@@ -167,6 +167,33 @@ class OracleOps(object):
         return [osf.sparse_flow_component(nd, ed, pt, seed=seed, comp_id=c) for (nd, ed, pt), c in zip(flat, ids)]
 
 
+class RecordingLock(object):
+    """the lock= of assemble_distributed, watched: taking it twice or giving it back twice ends the rank at once"""
+    held = False
+
+    def acquire(self):
+        assert not self.held, "the lock is acquired while held"
+        self.held = True
+
+    def release(self):
+        assert self.held, "the lock is released while free"
+        self.held = False
+
+
+def watch_collectives(lock):
+    """wraps the collectives of torch.distributed that shannon_amd calls.  -> (names of all that ran, names of those that ran while
+    `lock` was held: the lock discipline of distributed.Clock says there are none)"""
+    ran, held = [], []
+    for nm in ("all_gather", "all_to_all_single", "all_gather_object", "all_reduce"):
+        def watched(*a, _f=getattr(dist, nm), _nm=nm, **k):
+            ran.append(_nm)
+            if lock.held:
+                held.append(_nm)
+            return _f(*a, **k)
+        setattr(dist, nm, watched)
+    return ran, held
+
+
 def main():
     name, out = sys.argv[1], sys.argv[2]
     dist.init_process_group("gloo")
@@ -182,6 +209,13 @@ def main():
     pv = [part_vectors(len(b["contigs"]), psize) for b in g["big_components"]] or None
     ops = OracleOps(r1, r2, m["K"])
     ops.owner_labelling = os.environ.get("SHN_TEST_OWNER_LABELS") == "1"
+    T, lock = {}, RecordingLock()
+    ran, held = watch_collectives(lock)
+
+    def note_clock():
+        # what the test holds against the lock discipline and the timing keys (the test ops' own key is not the product's)
+        json.dump({"keys": sorted(k for k in T if k != OracleOps.OWN_KEY), "collectives": len(ran), "with_lock_held": held, "lock_held_after": lock.held},
+                  open(out + ".clock%d" % rank, "w"))
     if len(sys.argv) > 3:                    # a rank whose graph stage fails: every rank must raise together (no rank left in the gather)
         fail = int(sys.argv[3])
 
@@ -191,15 +225,17 @@ def main():
             return None
         ops.graph_batch = graph_batch
         try:
-            distributed.assemble_distributed(ops, m["K"], psize, "s", m["sf_seed"], pv)
+            distributed.assemble_distributed(ops, m["K"], psize, "s", m["sf_seed"], pv, timings=T, lock=lock)
             msg = "no error"
         except RuntimeError as ex:
             msg = str(ex)
         open(out + ".rank%d" % rank, "w").write(msg)
+        note_clock()
         dist.destroy_process_group()
         return
     res = distributed.assemble_distributed(ops, m["K"], psize, "s", m["sf_seed"], pv, double_stranded=not m.get("strand_specific"),
-                                           min_weight=m.get("kmer_soft_cutoff", 3), kmer_hard_cutoff=m.get("kmer_hard_cutoff", 1))
+                                           min_weight=m.get("kmer_soft_cutoff", 3), kmer_hard_cutoff=m.get("kmer_hard_cutoff", 1), timings=T, lock=lock)
+    note_clock()
     if rank == 0:
         json.dump({"partitions": dict(res["partitions"]), "final": res["final"], "contigs": res["contigs"],
                    "owner_labelling_ran": hasattr(ops, "component_keys"), "n_k1mers": res["n_k1mers"]}, open(out, "w"))

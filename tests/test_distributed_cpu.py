@@ -96,6 +96,24 @@ def test_ranks_equal_single_process(name, port, world, chunk, tmp_path):
     _ranks_equal_single(name, port, world, chunk, tmp_path, {})
 
 
+# the keys of assemble_distributed's timings at world 2 on rank 0 (the other ranks do not merge), as the driver left them before
+# its stages were named and one Clock took over the stopwatch: what a stage or a collective is called is part of the interface
+REPLICATED_KEYS = {"collect reads", "count", "extension", "graph", "merge (rank 0)", "partition+route", "reduce", "sparse flow", "table",
+                   "x:allgather table", "x:bucket exchange", "x:gather fasta", "x:read exchange", "x:route counts"}
+OWNER_SHARD_KEYS = (REPLICATED_KEYS - {"table", "x:allgather table"}) | {
+    "labels: local components + queries", "labels: answers", "labels: component graph", "labels: owners + shard",
+    "x:label queries", "x:label edges", "x:label sizes", "x:component exchange"}
+
+
+def _lock_was_free_around_every_collective(out, world):
+    """what every rank's worker saw (dist_worker.py: RecordingLock, watch_collectives): collectives ran, none of them with the lock=
+    of assemble_distributed held, and the lock was free when the call returned or raised.  -> the ranks' records"""
+    clocks = [json.load(open("%s.clock%d" % (out, r))) for r in range(world)]
+    for r, c in enumerate(clocks):
+        assert c["collectives"] > 0 and c["with_lock_held"] == [] and c["lock_held_after"] is False, (r, c)
+    return clocks
+
+
 def _ranks_equal_single(name, port, world, chunk, tmp_path, env_extra):
     from oracle import pipeline as opipe
     out = str(tmp_path / "res.json")
@@ -107,7 +125,12 @@ def _ranks_equal_single(name, port, world, chunk, tmp_path, env_extra):
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:]
     got = json.load(open(out))
-    assert got["owner_labelling_ran"] == (env_extra.get("SHN_TEST_OWNER_LABELS") == "1")
+    owner_shards = env_extra.get("SHN_TEST_OWNER_LABELS") == "1"
+    assert got["owner_labelling_ran"] == owner_shards
+    clocks = _lock_was_free_around_every_collective(out, world)
+    if name == "syn_pe_s0" and world == 2:
+        for r in range(world):
+            assert set(clocks[r]["keys"]) == (OWNER_SHARD_KEYS if owner_shards else REPLICATED_KEYS) - ({"merge (rank 0)"} if r else set()), r
     m = MANIFEST[name]
     g = load_case(name)
     inp = load_inputs(name)
@@ -132,6 +155,7 @@ def test_a_failing_graph_stage_is_told_to_every_rank(tmp_path):
     for r in (0, 1):
         msg = open(out + ".rank%d" % r).read()
         assert "graph stage failed on rank 1" in msg and "boom on purpose" in msg, msg
+    _lock_was_free_around_every_collective(out, 2)                # after the raise too, on both ranks
 
 
 def test_read_pieces_travel_as_bytes():
@@ -159,3 +183,89 @@ def test_strand_specific_is_refused_by_ops_that_do_not_implement_it():
     from shannon_amd import distributed
     with pytest.raises(NotImplementedError, match="strand_specific"):
         distributed.assemble_distributed(object(), double_stranded=False)
+
+
+def test_clock_takes_a_collective_out_of_its_stage_and_frees_the_lock_for_it():
+    """distributed.Clock alone, with a lock that refuses to be taken or given back twice and a clock that is moved by hand: a
+    collective inside a stage has its seconds to itself and the lock free, also between two stages; an exception in either block
+    leaves the lock free and the seconds booked, and the clock goes on working"""
+    from shannon_amd import distributed
+
+    class Lock(object):
+        held = False
+
+        def acquire(self):
+            assert not self.held
+            self.held = True
+
+        def release(self):
+            assert self.held
+            self.held = False
+    now, T, lock = [100.0], {}, Lock()
+    clock = distributed.Clock(T, lock, now=lambda: now[0])
+    assert clock.timings is T and not lock.held
+    with clock.stage("a"):
+        assert lock.held
+        now[0] += 1
+        with clock.collective("x:c"):
+            assert not lock.held
+            now[0] += 10
+        assert lock.held
+        now[0] += 2
+    assert not lock.held and T == {"a": 3.0, "x:c": 10.0}
+    with clock.collective("x:c"):                           # between two stages: nothing to pause, the lock stays free
+        assert not lock.held
+        now[0] += 5
+    assert not lock.held and T == {"a": 3.0, "x:c": 15.0}
+    with pytest.raises(KeyError):
+        with clock.stage("b"):
+            now[0] += 1
+            with clock.collective("x:d"):
+                now[0] += 4
+                raise KeyError("in the collective")
+    assert not lock.held and T["b"] == 1.0 and T["x:d"] == 4.0
+    with pytest.raises(KeyError):
+        with clock.stage("b"):
+            now[0] += 2
+            raise KeyError("in the stage")
+    assert not lock.held and T["b"] == 3.0
+    with pytest.raises(RuntimeError, match="inside stage"):
+        with clock.stage("a"):
+            with clock.stage("b"):
+                pass
+    assert not lock.held
+    with clock.stage("a"):
+        assert lock.held
+        now[0] += 1
+    assert T == {"a": 4.0, "x:c": 15.0, "b": 3.0, "x:d": 4.0}
+    inert = distributed.Clock()                             # no lock, a dict of its own
+    with inert.stage("s"):
+        with inert.collective("x"):
+            pass
+    assert set(inert.timings) == {"s", "x"}
+
+
+def test_read_caps_are_the_ranks_shares_of_the_first_reads_in_the_global_order():
+    """distributed.read_caps against the order written out: a partition's global strand-doubled order is all ranks' forward routed
+    reads in rank order, then all ranks' reverse halves; its graph consumes the first `cutoff` of them, and what a rank sends is
+    exactly its reads among those -- a prefix of its forward and a prefix of its reverse reads.  W 1..5, P 1..4, 0..6 reads per
+    rank and half; cut-offs 0, inside, exactly the total and beyond it."""
+    from shannon_amd import distributed
+    rng = np.random.default_rng(11)
+    seen = set()
+    for case in range(400):
+        W, P = 1 + case % 5, 1 + (case // 5) % 4
+        allc = rng.integers(0, 7, (W, P, 2))
+        tot = allc.sum(axis=(0, 2))
+        cut = np.array([[0, int(rng.integers(0, t + 1)), int(t), int(t) + 3][(case // 20 + p) % 4] for p, t in enumerate(tot)], dtype=np.int64)
+        kept = []
+        for p in range(P):
+            order = [(r, half, j) for half in (0, 1) for r in range(W) for j in range(int(allc[r, p, half]))]
+            kept.append(order[:int(cut[p])])
+            seen.add("none" if cut[p] == 0 else "all" if cut[p] >= tot[p] else "some")
+        for r in range(W):
+            keep_f, keep_r = distributed.read_caps(allc, cut, r)
+            for p in range(P):
+                for half, keep in ((0, keep_f), (1, keep_r)):
+                    assert [j for q, h, j in kept[p] if q == r and h == half] == list(range(int(keep[p]))), (allc.tolist(), cut.tolist(), r, p, half)
+    assert seen == {"none", "some", "all"}

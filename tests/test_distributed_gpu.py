@@ -121,6 +121,14 @@ def test_replicated_table_path_equals_single_process(world, paired, n_genes, see
     _ranks_vs_single(world, paired, n_genes, seed, port, big, ss, tmp_path, {"SHN_OWNER_LABELS": "0"})
 
 
+@pytest.mark.parametrize("world,paired,n_genes,seed,port,big,ss", [(2, True, 3, 11, 29631, False, False), (2, True, 12, 4, 29632, False, True)])
+def test_graphs_one_partition_at_a_time_equal_single_process(world, paired, n_genes, seed, port, big, ss, tmp_path):
+    """SHN_GRAPH_GPU=0 on the ranks (the reference run below keeps its default): no unitigs, GpuOps.graph_batch declines and every
+    owned partition goes through GpuOps.graph -- the pieces of its source ranks merged into the global order, -s rows split into
+    their mates -- and one ops.sparse_flow; also the path of K > 31."""
+    _ranks_vs_single(world, paired, n_genes, seed, port, big, ss, tmp_path, {"SHN_GRAPH_GPU": "0"})
+
+
 def _ranks_vs_single(world, paired, n_genes, seed, port, big, ss, tmp_path, env_extra):
     """world_size > 1 with the product's per-rank compute (GpuOps): every rank holds a slice of the reads and runs its HIP
     kernels on cuda:0; the collectives go through gloo (RCCL does not take two ranks on one device).  Covers the sharded

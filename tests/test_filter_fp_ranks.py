@@ -151,7 +151,7 @@ def test_single_end_ranks_are_not_filtered_and_say_so():
     class Ops(object):
         paired = False
     texts = {0: ">a\nACGT\n"}
-    got, extra, err = distributed._filter_step(Ops(), {}, texts, ["c0"], [0], None, None, None, None)
+    got, extra, err = distributed._filter_step(Ops(), {}, texts, ["c0"], [0], None, None, None)
     assert got is texts and err is None and list(extra) == ["note"] and "single-end" in extra["note"]
 
 

@@ -786,6 +786,40 @@ int shn_quorum_table(shn_ctx* ctx, const shn_reads* const* sets, const shn_qmask
  * above 4 (what a walk keeps in registers for the revert).                                                                        */
 int shn_quorum_correct(shn_ctx* ctx, const shn_reads* reads, const shn_table* table, int k, uint32_t anchor_count, uint32_t window,
                        uint32_t max_subs, shn_reads** out, uint64_t* stats5);
+/* ---- python -m shannon_amd.correct: tables added up, and --trim --------------------------------------------------
+ * shn_quorum_add_tables: the key-wise sum of two tables of shn_quorum_table (one k, both canonical): the table of the reads of both.
+ * Every count is held at 2^31 - 1 BEFORE the sum (shn_table_from_pairs adds 32-bit counts and would wrap without a word; the rule
+ * reads only c >= 1 and c >= A), so a count of the result is exact below 2^31 and at least 2^31 - 1 otherwise.  shn_table_total of
+ * the result is the 64-bit sum of the two totals.  Either table may be empty; both stay as they are.                                */
+int shn_quorum_add_tables(shn_ctx* ctx, const shn_table* a, const shn_table* b, shn_table** out);
+/* shn_qspans: per read of a set the span [lo, hi) its walks vouch for (rule 6).  shn_qspans_create: from the host, lo_hi[2 r] = lo and
+ * lo_hi[2 r + 1] = hi of read r (SHN_ERR_ARG: some lo > hi).  shn_qspans_download: the same layout back, 2 n numbers.               */
+typedef struct shn_qspans shn_qspans;
+int shn_qspans_create(shn_ctx* ctx, const uint32_t* lo_hi, uint64_t n_reads, shn_qspans** out);
+void shn_qspans_destroy(shn_qspans* s);
+uint64_t shn_qspans_count(const shn_qspans* s);
+int shn_qspans_download(shn_ctx* ctx, const shn_qspans* s, uint32_t* lo_hi_out);
+/* shn_quorum_correct_spans: shn_quorum_correct (same arguments, same *out, same stats5) and in *spans_out the span of every read:
+ * empty (0, 0) for a read shorter than k or without an anchor; else lo = i0 - e_b, hi = i0 + k + e_f, where a direction vouches for
+ * all its steps if it reaches the read's end, for the steps before the one it stopped at, and at a window revert for the steps
+ * before the first substitution it set back.                                                                                       */
+int shn_quorum_correct_spans(shn_ctx* ctx, const shn_reads* reads, const shn_table* table, int k, uint32_t anchor_count, uint32_t window,
+                             uint32_t max_subs, shn_reads** out, shn_qspans** spans_out, uint64_t* stats5);
+/* shn_qspans_keep (rule 7): read r is kept when hi - lo >= min_len -- with a second set (the mates: reads_b, spans_b; NULL for single
+ * reads) when that holds for read r of both.  stats5 = { reads kept, kept reads whose span is shorter than the read, bases cut from
+ * kept reads, reads whose own span is below min_len, pairs dropped (0 without mates) }, the reads of both sets counted.
+ * SHN_ERR_ARG: min_len == 0, spans that are not of their set's read count, mates of another read count.                           */
+typedef struct shn_qkeep shn_qkeep;
+int shn_qspans_keep(shn_ctx* ctx, const shn_reads* reads_a, const shn_qspans* spans_a, const shn_reads* reads_b, const shn_qspans* spans_b,
+                    uint32_t min_len, shn_qkeep** out, uint64_t* stats5);
+void shn_qkeep_destroy(shn_qkeep* k);
+uint64_t shn_qkeep_count(const shn_qkeep* k);           /* reads (pairs) kept */
+/* shn_reads_slice: *out = a NEW ragged read set whose read j is bases [lo, hi) of the j-th kept read of `src` (keep == NULL: every
+ * read), kept reads in order; `src` (fixed-length or ragged) stays as it is.  The layout is shn_reads_create's: every read on its
+ * own even word boundary, zero bits behind its last base, bases outside ACGT kept and counted.  SHN_ERR_ARG before any launch:
+ * spans or keep flags that are not of the set's read count, and -- for spans that came from the host -- a hi beyond the reads'
+ * (largest) length.  Spans from the device are held inside their read by the kernel itself.                                       */
+int shn_reads_slice(shn_ctx* ctx, const shn_reads* src, const shn_qspans* spans, const shn_qkeep* keep, shn_reads** out);
 
 /* ---- --compare: a finished assembly against a reference transcriptome ------------------------------------------------------------
  * Replaces the BLAT run of the reference's comparison (shannon.py:620-622 starts run_MB_SF_fn.py --compare; run_MB_SF_fn.py:299 runs

@@ -189,6 +189,16 @@ SIGNATURES = {
     "shn_qmask_download": (C.c_int, [vp, vp, vp]),
     "shn_quorum_table": (C.c_int, [vp, vpp, vpp, C.c_int, C.c_int, vpp]),
     "shn_quorum_correct": (C.c_int, [vp, vp, vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vpp, vp]),
+    "shn_quorum_add_tables": (C.c_int, [vp, vp, vp, vpp]),
+    "shn_qspans_create": (C.c_int, [vp, vp, C.c_uint64, vpp]),
+    "shn_qspans_destroy": (None, [vp]),
+    "shn_qspans_count": (C.c_uint64, [vp]),
+    "shn_qspans_download": (C.c_int, [vp, vp, vp]),
+    "shn_quorum_correct_spans": (C.c_int, [vp, vp, vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vpp, vpp, vp]),
+    "shn_qspans_keep": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vpp, vp]),
+    "shn_qkeep_destroy": (None, [vp]),
+    "shn_qkeep_count": (C.c_uint64, [vp]),
+    "shn_reads_slice": (C.c_int, [vp, vp, vp, vp, vpp]),
     "shn_compare_rows": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_int, C.c_uint32, vpp]),
     "shn_cmprows_sizes": (C.c_int, [vp, vp]),
     "shn_cmprows_export": (C.c_int, [vp, vp]),

@@ -69,7 +69,9 @@ enum {
   // quant -b (abundance.hip): the bootstrap replicates' class counts, the EM over all live replicates at once
   T_ABD_RESAMPLE, T_ABD_EM_BATCH,
   // quant on several read files or ranks (abundance.hip): the parts' classes merged -- keys, sort, heads, members, weights
-  T_ABD_MERGE, T_N = 72                        // (T_N: device.TIMER_SLOTS)
+  T_ABD_MERGE,
+  // correct --trim (reads_slice.hip): which reads are kept, the scans, the sub-reads copied into a new set
+  T_QUORUM_TRIM, T_N = 73                      // (T_N: device.TIMER_SLOTS)
 };
 
 // grow-only device workspace slot (process-wide ones: g_shn_ws below; per-context ones: shn_ctx::cws)
@@ -179,6 +181,13 @@ struct shn_qmask {
   uint64_t n_hq;           // bases marked
   uint64_t* d_hq;
 };
+
+// the span [lo, hi) of every read of a set that the walks of shn_quorum_correct_spans vouch for (rule 6): lo and hi
+// of read r at d_span[2 r], d_span[2 r + 1].  host: the same numbers where the spans came from the host (shn_qspans_create), empty
+// otherwise -- what shn_reads_slice can check before it launches
+struct shn_qspans { shn_ctx* ctx; int device; uint64_t n_reads; uint32_t* d_span; std::vector<uint32_t> host; };
+// which reads of a set (which pairs of two sets) rule 7 keeps: one 32-bit flag per read, and how many are set
+struct shn_qkeep { shn_ctx* ctx; int device; uint64_t n_reads, n_kept; uint32_t* d_keep; };
 
 // text on the device (the candidate contigs as shn_ext_emit_device leaves them): n bytes + 64 zeroed
 struct shn_devtext { shn_ctx* ctx; uint8_t* d; uint64_t n; };

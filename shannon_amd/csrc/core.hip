@@ -31,7 +31,7 @@ static const char* kTimerNames[T_N] = {
   "extend.audit", "filter_fp.index", "filter_fp.map", "filter_fp.count", "filter_fp.merge", "reads.collect", "reads.fasta", "k1mers.dict",
   "abundance.index", "abundance.map", "abundance.classes", "abundance.em", "quorum.count", "quorum.table", "quorum.correct",
   "compare.index", "compare.seeds", "compare.score", "compare.rows", "compare.chain",
-  "abundance.resample", "abundance.em_batch", "abundance.merge"};
+  "abundance.resample", "abundance.em_batch", "abundance.merge", "quorum.trim"};
 extern "C" const char* shn_timer_name(int slot) {
   if (slot < 0 || slot >= T_N || !kTimerNames[slot]) return "";
   return kTimerNames[slot];

@@ -65,11 +65,15 @@ __global__ __launch_bounds__(Q_BLK) void quorum_fill_kernel(ReadSetView S, const
 
 // One read per thread.  S: the reads as they are (read only); ow / om: the output set's words and mask, already a copy of S's.
 // ctr[5]: reads with an anchor, reads changed, substitutions, stopped directions, window reverts.
+// SPANS (shn_quorum_correct_spans): span[2 r], span[2 r + 1] = the [lo, hi) the walks of read r vouch for (rule 6), (0, 0) for a read
+// that is too short or has no anchor.  The instantiation without it is the kernel shn_quorum_correct always ran.
+template <bool SPANS>
 __global__ __launch_bounds__(Q_BLK) void quorum_correct_kernel(ReadSetView S, TabIdx T, const uint32_t* __restrict__ counts, int k, uint32_t A, uint32_t W,
                                                                uint32_t E, uint64_t* __restrict__ ow, uint64_t* __restrict__ om,
-                                                               unsigned long long* __restrict__ ctr) {
+                                                               unsigned long long* __restrict__ ctr, uint32_t* __restrict__ span) {
   const uint64_t kmask = k == 32 ? ~0ULL : ((1ULL << (2 * k)) - 1);
   SHN_GRID_FOR(r, S.n) {
+    if (SPANS) { span[2 * r] = 0; span[2 * r + 1] = 0; }
     const uint32_t len = q_len(S, r);
     if (len < (uint32_t)k) continue;
     const uint64_t wb = S.word_base(r);
@@ -92,8 +96,9 @@ __global__ __launch_bounds__(Q_BLK) void quorum_correct_kernel(ReadSetView S, Ta
     QWalkStats st{0, 0, 0};
     uint64_t* rw = ow + wb;
     uint64_t* rm = om + (wb >> 1);
-    q_walk<true>(cur, rw, rm, x, k, kmask, W, E, i0 + (uint32_t)k, len - i0 - (uint32_t)k, present, st);
-    q_walk<false>(cur, rw, rm, x, k, kmask, W, E, i0 - 1, i0, present, st);
+    const uint32_t ef = q_walk<true>(cur, rw, rm, x, k, kmask, W, E, i0 + (uint32_t)k, len - i0 - (uint32_t)k, present, st);
+    const uint32_t eb = q_walk<false>(cur, rw, rm, x, k, kmask, W, E, i0 - 1, i0, present, st);
+    if (SPANS) { span[2 * r] = i0 - eb; span[2 * r + 1] = i0 + (uint32_t)k + ef; }
     atomicAdd(&ctr[0], 1ULL);
     if (st.subs) { atomicAdd(&ctr[1], 1ULL); atomicAdd(&ctr[2], (unsigned long long)st.subs); }
     if (st.stops) atomicAdd(&ctr[3], (unsigned long long)st.stops);
@@ -174,42 +179,113 @@ extern "C" int shn_quorum_table(shn_ctx* ctx, const shn_reads* const* sets, cons
   return SHN_OK;
 }
 
-extern "C" int shn_quorum_correct(shn_ctx* ctx, const shn_reads* reads, const shn_table* table, int k, uint32_t anchor_count, uint32_t window,
-                                  uint32_t max_subs, shn_reads** out, uint64_t* stats5) {
-  if (!ctx || !reads || !table || !out || !stats5) return shn_fail(SHN_ERR_ARG, "shn_quorum_correct: NULL argument");
+// shn_quorum_correct and shn_quorum_correct_spans: one body, the kernel instantiated with or without the span output
+static int quorum_correct_impl(shn_ctx* ctx, const char* who, const shn_reads* reads, const shn_table* table, int k, uint32_t anchor_count, uint32_t window,
+                               uint32_t max_subs, shn_reads** out, shn_qspans** spans_out, uint64_t* stats5) {
+  const std::string name(who);
+  if (!ctx || !reads || !table || !out || !stats5) return shn_fail(SHN_ERR_ARG, name + ": NULL argument");
   *out = nullptr;
-  if (k < 15 || k > 32) return shn_fail(SHN_ERR_ARG, "shn_quorum_correct: k outside 15 .. 32");
-  if (table->k != k || !table->canonical) return shn_fail(SHN_ERR_ARG, "shn_quorum_correct: the table is not a canonical table of k-mers of this k");
-  if (anchor_count == 0) return shn_fail(SHN_ERR_ARG, "shn_quorum_correct: anchor_count is 0 (every window would be an anchor)");
+  if (spans_out) *spans_out = nullptr;
+  if (k < 15 || k > 32) return shn_fail(SHN_ERR_ARG, name + ": k outside 15 .. 32");
+  if (table->k != k || !table->canonical) return shn_fail(SHN_ERR_ARG, name + ": the table is not a canonical table of k-mers of this k");
+  if (anchor_count == 0) return shn_fail(SHN_ERR_ARG, name + ": anchor_count is 0 (every window would be an anchor)");
   if (max_subs > (uint32_t)QUORUM_MAX_E)
-    return shn_fail(SHN_ERR_ARG, "shn_quorum_correct: max_subs above " + std::to_string(QUORUM_MAX_E) + ", what a walk keeps in registers for the revert");
-  if (table->device != reads->device) return shn_fail(SHN_ERR_ARG, "shn_quorum_correct: table and reads on different devices");
+    return shn_fail(SHN_ERR_ARG, name + ": max_subs above " + std::to_string(QUORUM_MAX_E) + ", what a walk keeps in registers for the revert");
+  if (table->device != reads->device) return shn_fail(SHN_ERR_ARG, name + ": table and reads on different devices");
   SHN_ENTER(ctx);
   hipStream_t s = ctx->stream;
   ShnDevBufs B(s);
   unsigned long long* d_ctr = nullptr;
   HIP_TRY(B.get(&d_ctr, 5 * 8));
   shn_reads* r = nullptr;
+  shn_qspans* sp = nullptr;
+  if (spans_out) {
+    sp = new shn_qspans();
+    sp->ctx = ctx; sp->device = ctx->device; sp->n_reads = reads->n_reads; sp->d_span = nullptr;
+    hipError_t e = shn_hip_malloc(&sp->d_span, (reads->n_reads + 1) * 8);
+    if (e != hipSuccess) { delete sp; return shn_fail(SHN_ERR_HIP, name + ": " + hipGetErrorString(e)); }
+  }
+  auto drop = [&]() { if (r) shn_reads_destroy(r); if (sp) shn_qspans_destroy(sp); };
   unsigned long long ctr[5] = {0, 0, 0, 0, 0};
   {
-    // bytes: the copy (words and masks read and written), the walk's reads of words and masks, one probed key per base, 4 B of length per read
+    // bytes: the copy (words and masks read and written), the walk's reads of words and masks, one probed key per base, 4 B of length
+    // per read; with spans 8 B more per read
     TimerRegion t(ctx, T_QUORUM_CORRECT);
     int rc = shn_reads_clone(ctx, reads, &r);
-    if (rc) return rc;
+    if (rc) { drop(); return rc; }
     hipError_t e = hipMemsetAsync(d_ctr, 0, 5 * 8, s);
     if (e == hipSuccess && reads->n_reads) {
-      hipLaunchKernelGGL(quorum_correct_kernel, dim3(shn_grid(reads->n_reads, Q_BLK)), dim3(Q_BLK), 0, s, view_of(reads), shn_tab_idx(table), (const uint32_t*)table->d_counts, k,
-                         anchor_count, window, max_subs, r->d_words, r->d_mask, d_ctr);
+      const dim3 grid(shn_grid(reads->n_reads, Q_BLK)), blk(Q_BLK);
+      if (sp)
+        hipLaunchKernelGGL(quorum_correct_kernel<true>, grid, blk, 0, s, view_of(reads), shn_tab_idx(table), (const uint32_t*)table->d_counts, k, anchor_count, window,
+                           max_subs, r->d_words, r->d_mask, d_ctr, sp->d_span);
+      else
+        hipLaunchKernelGGL(quorum_correct_kernel<false>, grid, blk, 0, s, view_of(reads), shn_tab_idx(table), (const uint32_t*)table->d_counts, k, anchor_count, window,
+                           max_subs, r->d_words, r->d_mask, d_ctr, (uint32_t*)nullptr);
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(ctr, d_ctr, 5 * 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);              // (ctr is this frame's: the copy ends here)
-    if (e != hipSuccess) { shn_reads_destroy(r); return shn_fail(SHN_ERR_HIP, std::string("shn_quorum_correct: ") + hipGetErrorString(e)); }
-    t.bytes(reads->n_words * 12 * 3 + reads->total_bases * 8 + reads->n_reads * 4);
+    if (e != hipSuccess) { drop(); return shn_fail(SHN_ERR_HIP, name + ": " + hipGetErrorString(e)); }
+    t.bytes(reads->n_words * 12 * 3 + reads->total_bases * 8 + reads->n_reads * (sp ? 12 : 4));
   }
   int rc = shn_reads_refresh_bad(ctx, r);            // (the N that became bases are counted out)
-  if (rc) { shn_reads_destroy(r); return rc; }
+  if (rc) { drop(); return rc; }
   for (int i = 0; i < 5; i++) stats5[i] = ctr[i];
   *out = r;
+  if (spans_out) *spans_out = sp;
+  return SHN_OK;
+}
+
+extern "C" int shn_quorum_correct(shn_ctx* ctx, const shn_reads* reads, const shn_table* table, int k, uint32_t anchor_count, uint32_t window,
+                                  uint32_t max_subs, shn_reads** out, uint64_t* stats5) {
+  return quorum_correct_impl(ctx, "shn_quorum_correct", reads, table, k, anchor_count, window, max_subs, out, nullptr, stats5);
+}
+
+extern "C" int shn_quorum_correct_spans(shn_ctx* ctx, const shn_reads* reads, const shn_table* table, int k, uint32_t anchor_count, uint32_t window,
+                                        uint32_t max_subs, shn_reads** out, shn_qspans** spans_out, uint64_t* stats5) {
+  if (!spans_out) return shn_fail(SHN_ERR_ARG, "shn_quorum_correct_spans: NULL argument");
+  return quorum_correct_impl(ctx, "shn_quorum_correct_spans", reads, table, k, anchor_count, window, max_subs, out, spans_out, stats5);
+}
+
+// ---- tables added up: the pairs of both, every count held at 2^31 - 1, then the sum by key of shn_table_from_pairs
+namespace {
+constexpr uint32_t Q_COUNT_CAP = 0x7fffffffu;
+__global__ __launch_bounds__(Q_BLK) void quorum_concat_kernel(const uint64_t* __restrict__ ka, const uint32_t* __restrict__ ca, uint64_t na,
+                                                              const uint64_t* __restrict__ kb, const uint32_t* __restrict__ cb, uint64_t nb,
+                                                              uint64_t* __restrict__ keys, uint32_t* __restrict__ cnts) {
+  SHN_GRID_FOR(i, na + nb) {
+    const bool first = i < na;
+    const uint64_t j = first ? i : i - na;
+    keys[i] = first ? ka[j] : kb[j];
+    cnts[i] = min(first ? ca[j] : cb[j], Q_COUNT_CAP);
+  }
+}
+}  // namespace
+
+extern "C" int shn_quorum_add_tables(shn_ctx* ctx, const shn_table* a, const shn_table* b, shn_table** out) {
+  if (!ctx || !a || !b || !out) return shn_fail(SHN_ERR_ARG, "shn_quorum_add_tables: NULL argument");
+  *out = nullptr;
+  if (a->k != b->k || !a->canonical || !b->canonical) return shn_fail(SHN_ERR_ARG, "shn_quorum_add_tables: two canonical tables of one k");
+  if (a->device != b->device) return shn_fail(SHN_ERR_ARG, "shn_quorum_add_tables: tables on different devices");
+  const uint64_t n = a->n + b->n;
+  if (n >= 0xFFFFFFFFULL) return shn_fail(SHN_ERR_OVERFLOW, "shn_quorum_add_tables: 2^32 pairs or more");
+  SHN_ENTER(ctx);
+  hipStream_t s = ctx->stream;
+  ShnDevBufs B(s);
+  uint64_t* d_k = nullptr; uint32_t* d_c = nullptr;
+  HIP_TRY(B.get(&d_k, (n + 1) * 8)); HIP_TRY(B.get(&d_c, (n + 1) * 4));
+  {
+    // bytes: 12 B per pair read and written; the table build reads and writes the pairs once more
+    TimerRegion t(ctx, T_QUORUM_TABLE);
+    if (n) hipLaunchKernelGGL(quorum_concat_kernel, dim3(shn_grid(n, Q_BLK)), dim3(Q_BLK), 0, s, (const uint64_t*)a->d_keys, (const uint32_t*)a->d_counts, a->n,
+                              (const uint64_t*)b->d_keys, (const uint32_t*)b->d_counts, b->n, d_k, d_c);
+    HIP_TRY(hipGetLastError());
+    t.bytes(n * 24 + n * 24);
+    int rc = shn_table_from_pairs(ctx, d_k, d_c, n, a->k, 1, out);
+    if (rc) return rc;
+  }
+  (*out)->total = a->total + b->total;
+  HIP_TRY(hipStreamSynchronize(s));
   return SHN_OK;
 }

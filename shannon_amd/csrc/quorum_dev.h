@@ -41,8 +41,10 @@ struct QWalkStats { uint32_t subs, stops, reverts; };
 // the output read (ow / om).  present(QKmer) is the table probe.  The last QUORUM_MAX_E substitutions (step, original code) are
 // held in hd / ho, newest first: every substitution within the window of a step is among them, because a walk that finds E <=
 // QUORUM_MAX_E of them there ends.
+// Returns the steps the walk vouches for (rule 6): n_steps at the read's end, d at a stop, the smallest step among
+// the substitutions it set back at a window revert.  A caller that drops the value pays nothing for it.
 template <bool FWD, class Cursor, class Present>
-SHN_XHD void q_walk(Cursor& cur, uint64_t* ow, uint64_t* om, QKmer x, int k, uint64_t kmask, uint32_t W, uint32_t E, uint32_t p0, uint32_t n_steps,
+SHN_XHD uint32_t q_walk(Cursor& cur, uint64_t* ow, uint64_t* om, QKmer x, int k, uint64_t kmask, uint32_t W, uint32_t E, uint32_t p0, uint32_t n_steps,
                     Present&& present, QWalkStats& st) {
   uint32_t hd[QUORUM_MAX_E], ho[QUORUM_MAX_E], nh = 0;
 #pragma unroll
@@ -70,18 +72,22 @@ SHN_XHD void q_walk(Cursor& cur, uint64_t* ow, uint64_t* om, QKmer x, int k, uin
       }
       S = (S2 && (S2 & (S2 - 1)) == 0) ? S2 : 0;
     }
-    if (!S) { st.stops++; return; }
+    if (!S) { st.stops++; return d; }
     const uint32_t c = S & 1 ? 0u : S & 2 ? 1u : S & 4 ? 2u : 3u;
     // substitutions of this direction inside the window: steps d' with d - W < d' < d
     uint32_t in_window = 0;
 #pragma unroll
     for (int i = 0; i < QUORUM_MAX_E; i++) in_window += ((uint32_t)i < nh && (uint64_t)hd[i] + W > d) ? 1u : 0u;
     if (in_window >= E) {
+      uint32_t first = d;
 #pragma unroll
       for (int i = 0; i < QUORUM_MAX_E; i++)
-        if ((uint32_t)i < nh && (uint64_t)hd[i] + W > d) { q_put(ow, om, FWD ? p0 + hd[i] : p0 - hd[i], ho[i]); st.subs--; }
+        if ((uint32_t)i < nh && (uint64_t)hd[i] + W > d) {
+          q_put(ow, om, FWD ? p0 + hd[i] : p0 - hd[i], ho[i]); st.subs--;
+          first = hd[i] < first ? hd[i] : first;
+        }
       st.reverts++; st.stops++;
-      return;
+      return first;
     }
     q_put(ow, om, p, c);
 #pragma unroll
@@ -91,4 +97,5 @@ SHN_XHD void q_walk(Cursor& cur, uint64_t* ow, uint64_t* om, QKmer x, int k, uin
     st.subs++;
     x = q_step<FWD>(x, c, k, kmask);
   }
+  return n_steps;
 }

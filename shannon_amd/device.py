@@ -6,7 +6,7 @@ from . import _lib
 ENC_ASCII, ENC_CODES = 0, 1
 ALPHA = "ACGT"
 ALPHA_BYTES = np.frombuffer(b"ACGTN", dtype=np.uint8)        # (code 4 = a base outside ACGT)
-TIMER_SLOTS = 72      # T_N of csrc/common.h: a slot without a name is skipped
+TIMER_SLOTS = 73      # T_N of csrc/common.h: a slot without a name is skipped
 
 
 class Context(object):

@@ -70,7 +70,7 @@ def _all_gather_var_(t, group=None):
     return out.to(t.device), ns
 
 
-def ingest_rank_slice(paths, rank, world, group, device, ctx=None, stats=None, ragged=False):
+def ingest_rank_slice(paths, rank, world, group, device, ctx=None, stats=None, ragged=False, text_spans=None):
     """The N-rank CLI's reads by BYTES of the files (round 6; the reference streams its read files once, 10 M reads at a time:
     kmers_for_component.py:322-403).  Every rank counts the records that start in its share of each file's bytes
     (shn_text_records_in_range), the counts of all ranks say which record every share starts with, and the records
@@ -82,7 +82,9 @@ def ingest_rank_slice(paths, rank, world, group, device, ctx=None, stats=None, r
     device.RaggedCodes it ingests as; the ranks tell each other (the flags all-gather), and where some rank's slice of a file is
     ragged -- or two ranks hold matrices of two lengths -- every rank's slice of that file becomes RaggedCodes (a matrix is codes
     + arange * L already): one kind of store per file on all ranks.
-    stats (dict): bytes this rank looked at / holds."""
+    stats (dict): bytes this rank looked at / holds.
+    text_spans (list): gets one (a, b) per file appended -- the bytes [a, b) of the file that hold this rank's records (a == b: it
+    holds none); a caller that needs more of the records than their bases (the quality lines: shannon_amd.correct) reads them there."""
     import ctypes as C
     from . import _lib, device as dev_mod
     if any(p.endswith(".gz") for p in paths):
@@ -138,6 +140,8 @@ def ingest_rank_slice(paths, rank, world, group, device, ctx=None, stats=None, r
             return int(off.value)
         rlo, rhi = rank * n // world, (rank + 1) * n // world
         a, b = locate(rlo), locate(rhi)
+        if text_spans is not None:
+            text_spans.append((a, b) if rhi > rlo else (a, a))
         if rhi == rlo:                                        # (more ranks than records: this rank holds none)
             codes = np.zeros((0, 0), np.uint8)
         else:

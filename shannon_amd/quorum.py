@@ -9,6 +9,12 @@ rule run on the device (csrc/quorum.hip, the quality bits by cs
     apply          the whole step on the read sets of a run: corrected sets, corrected host codes for kfc.ReadStore, stats
     write_fasta    corrected_reads*.fa from the device, through the record formatter of --inDisk
 
+and what the command python -m shannon_amd.correct adds:
+
+    add_tables     the key-wise sum of two trusted tables: the table of a sample is the sum of its lanes' (its ranks') tables
+    correct(.., spans=True)  also the span [lo, hi) of every read that its walks vouch for (rule 6; shn_quorum_correct_spans)
+    trim           rule 7: the kept reads (pairs) cut to their spans as NEW resident sets, and the five counters (shn_reads_slice)
+
 The defaults are Quorum's documented ones (k = 24, quality 5, anchor count 3) and its "3 errors in a window of 10"."""
 import ctypes as C
 import os
@@ -18,6 +24,8 @@ from . import _lib, device
 
 K, MIN_QUALITY, ANCHOR_COUNT, WINDOW, MAX_SUBS = 24, 5, 3, 10, 3
 STAT_NAMES = ("anchored", "changed", "substitutions", "stopped", "reverts")
+TRIM_NAMES = ("kept", "trimmed", "bases_cut", "below_min", "pairs_dropped")
+COUNT_CAP = (1 << 31) - 1           # what a count is held at before two tables are added (shn_quorum_add_tables)
 
 
 class QMask(object):
@@ -81,13 +89,95 @@ def trusted_table(ctx, read_sets, masks, k=K):
     return device.Table(ctx, h)
 
 
-def correct(ctx, reads, table, k=K, anchor_count=ANCHOR_COUNT, window=WINDOW, max_subs=MAX_SUBS):
-    """(a new device.Reads with the rule's substitutions, {counter: value}); `reads` stays resident and unchanged"""
+def add_tables(ctx, a, b):
+    """a NEW device.Table: the key-wise sum of two trusted tables of one k (c(x) of rule 1 is a sum over reads, so the table of a
+    sample is the sum of its parts' tables).  Counts are held at COUNT_CAP before they are added -- the rule reads c >= 1 and c >= A
+    only, and a 32-bit sum must not wrap; `total` is the 64-bit sum of the two totals.  a and b stay as they are."""
+    h = C.c_void_p()
+    _lib.check(_lib.lib().shn_quorum_add_tables(ctx.h, a.h, b.h, C.byref(h)))
+    return device.Table(ctx, h)
+
+
+class QSpans(object):
+    """per read of a set the span [lo, hi) its walks vouch for (rule 6), resident"""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+
+    @classmethod
+    def from_array(cls, ctx, lo_hi):
+        """from a host array [n, 2] of (lo, hi)"""
+        a = np.ascontiguousarray(lo_hi, dtype=np.uint32).reshape(-1, 2)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().shn_qspans_create(ctx.h, a.ctypes.data if len(a) else None, len(a), C.byref(h)))
+        return cls(ctx, h)
+
+    def __len__(self):
+        return int(_lib.lib().shn_qspans_count(self.h))
+
+    def download(self):
+        """uint32 [n, 2]: (lo, hi) of every read"""
+        out = np.zeros((max(len(self), 1), 2), dtype=np.uint32)
+        _lib.check(_lib.lib().shn_qspans_download(self.ctx.h, self.h, out.ctypes.data))
+        return out[:len(self)]
+
+    def close(self):
+        if self.h:
+            _lib.lib().shn_qspans_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def correct(ctx, reads, table, k=K, anchor_count=ANCHOR_COUNT, window=WINDOW, max_subs=MAX_SUBS, spans=False):
+    """(a new device.Reads with the rule's substitutions, {counter: value}); `reads` stays resident and unchanged.  spans=True: a
+    third value, the QSpans of the reads (rule 6) -- the corrected set and the counters are those of the call without it."""
     h = C.c_void_p()
     st = np.zeros(5, dtype=np.uint64)
+    if spans:
+        sp = C.c_void_p()
+        _lib.check(_lib.lib().shn_quorum_correct_spans(ctx.h, reads.h, table.h, int(k), int(anchor_count), int(window), int(max_subs), C.byref(h),
+                                                       C.byref(sp), st.ctypes.data))
+        return device.Reads(ctx, h, fixed_len=reads.fixed_len), dict(zip(STAT_NAMES, (int(v) for v in st))), QSpans(ctx, sp)
     _lib.check(_lib.lib().shn_quorum_correct(ctx.h, reads.h, table.h, int(k), int(anchor_count), int(window), int(max_subs), C.byref(h),
                                              st.ctypes.data))
     return device.Reads(ctx, h, fixed_len=reads.fixed_len), dict(zip(STAT_NAMES, (int(v) for v in st)))
+
+
+def slice_reads(ctx, reads, spans, keep=None):
+    """a NEW ragged device.Reads: bases [lo, hi) of every read of `reads` (keep: a handle of shn_qspans_keep -- of the kept ones only),
+    in order (shn_reads_slice); `reads` stays as it is"""
+    h = C.c_void_p()
+    _lib.check(_lib.lib().shn_reads_slice(ctx.h, reads.h, spans.h, keep, C.byref(h)))
+    return device.Reads(ctx, h)
+
+
+def trim(ctx, sets, spans, min_len=K):
+    """rule 7 on one set, or on the two mate sets of a run: (new resident sets of the kept reads cut to their spans, {counter:
+    value} for TRIM_NAMES).  A read is kept when its span holds min_len bases or more, a pair when both mates are; the new sets are
+    ragged and stay aligned read for read.  sets and spans stay as they are."""
+    if len(sets) not in (1, 2) or len(sets) != len(spans):
+        raise ValueError("trim: %d read sets, %d span arrays" % (len(sets), len(spans)))
+    keep = C.c_void_p()
+    st = np.zeros(5, dtype=np.uint64)
+    paired = len(sets) == 2
+    _lib.check(_lib.lib().shn_qspans_keep(ctx.h, sets[0].h, spans[0].h, sets[1].h if paired else None, spans[1].h if paired else None, int(min_len),
+                                          C.byref(keep), st.ctypes.data))
+    out = []
+    try:
+        for r, sp in zip(sets, spans):
+            out.append(slice_reads(ctx, r, sp, keep))
+    except Exception:
+        for c in out:
+            c.close()
+        raise
+    finally:
+        _lib.lib().shn_qkeep_destroy(keep)
+    return out, dict(zip(TRIM_NAMES, (int(v) for v in st)))
 
 
 def host_codes(reads, like=None):
@@ -147,22 +237,28 @@ def apply(ctx, read_sets, sources, host=None, k=K, min_quality=MIN_QUALITY, anch
     return out, codes, stats
 
 
-def write_fasta(ctx, read_sets, out_dir):
+def write_fasta(ctx, read_sets, out_dir, first_name=0, suffix=""):
     """corrected_reads_1.fa + corrected_reads_2.fa (one set: corrected_reads.fa) under out_dir, all reads in order, formatted on the
-    device by the record formatter of --inDisk (record i named i, the mates _1 / _2); returns {file name: bytes}"""
+    device by the record formatter of --inDisk (record i named first_name + i, the mates _1 / _2); returns {file name: bytes}.
+    suffix: appended to the file names on disk (a part of a file that the caller puts together), not to the names returned."""
     from . import kmers_for_component as kfc
     n = len(read_sets[0])
     paired = len(read_sets) == 2
+    if n == 0:                                                  # (no record: nothing for the device to format)
+        names = ("corrected_reads_1.fa", "corrected_reads_2.fa") if paired else ("corrected_reads.fa",)
+        for name in names:
+            open(os.path.join(out_dir, name + suffix), "wb").close()
+        return dict.fromkeys(names, 0)
     # a route d < n names read d of the first set as it is, n + d read d of the second set as it is (the doubled mode's table)
     routes = kfc.Routes.from_arrays(ctx, np.zeros(2 * n if paired else n, np.uint32), np.arange(2 * n if paired else n, dtype=np.uint32),
                                     reads=(read_sets[0], read_sets[1] if paired else None))
     got = {}
     try:
         if paired:
-            got["corrected_reads_1.fa"] = routes.fasta_file(os.path.join(out_dir, "corrected_reads_1.fa"), 0, n, kfc.READS_DOUBLED, 1)
-            got["corrected_reads_2.fa"] = routes.fasta_file(os.path.join(out_dir, "corrected_reads_2.fa"), n, n, kfc.READS_DOUBLED, 2)
+            got["corrected_reads_1.fa"] = routes.fasta_file(os.path.join(out_dir, "corrected_reads_1.fa" + suffix), 0, n, kfc.READS_DOUBLED, 1, first_name)
+            got["corrected_reads_2.fa"] = routes.fasta_file(os.path.join(out_dir, "corrected_reads_2.fa" + suffix), n, n, kfc.READS_DOUBLED, 2, first_name)
         else:
-            got["corrected_reads.fa"] = routes.fasta_file(os.path.join(out_dir, "corrected_reads.fa"), 0, n, kfc.READS_DOUBLED, 0)
+            got["corrected_reads.fa"] = routes.fasta_file(os.path.join(out_dir, "corrected_reads.fa" + suffix), 0, n, kfc.READS_DOUBLED, 0, first_name)
     finally:
         routes.close()
     return got

@@ -203,6 +203,23 @@ int shn_debug_sorted_runs(shn_ctx* ctx, const uint64_t* keys, uint64_t n, int sh
                           uint64_t* pos_out, uint64_t* n_runs_out);
 int shn_debug_table_find(shn_ctx* ctx, const shn_table* table, const uint64_t* keys, uint64_t n, int variant, int64_t* idx_out);
 int shn_debug_table_view(shn_ctx* ctx, const shn_table* table, int* bits, int* layout, uint64_t* bucket_off /* may be NULL */);
+/* test hooks of the extension set-up (tests/test_ext_setup_gpu.py): the product functions called unchanged, host arrays out.  Not part
+ * of the path.
+ *   shn_debug_ext_setup   what shn_extend makes of a table of n k1-mers before the first walk, for one rank: weight[n] and flags[n] (bit 0
+ *                         palindrome, bit 1 low complexity); per oriented id o = 2 i + s the eight entries of its record's rows as
+ *                         rows[2n][8] (R[0..3] then L[0..3]: the oriented id reached by appending / prepending base b, or -1), the
+ *                         record's weight and seed rank (0xFFFFFFFF: no seed); the number of seeds and their oriented ids in walk
+ *                         order (order holds 2n elements, n_seeds are written).  No walk runs.  Every output may be NULL
+ *   shn_debug_fine_dict   builds the one-line dictionary of the table's k1-mers (csrc/k1dict.h) in a block of its own and looks the n
+ *                         queries up in it, eight lanes per query, as the records kernel does; the queries are used as passed (the
+ *                         caller canonicalises them).  id_out[i] = table index | palindrome << 31, or 0xFFFFFFFF; home_line_out[i] =
+ *                         the line the look-up starts at; stats_out[4] = hashed lines, lines (spare ones included) whose count word
+ *                         exceeds the slots of a line, table k1-mers stored in another line than their own, table k1-mers that are
+ *                         not low-complexity and stored in no line.  Every output may be NULL                                       */
+int shn_debug_ext_setup(shn_ctx* ctx, const shn_table* table, uint32_t min_weight, uint32_t* weight_out, uint8_t* flags_out, int32_t* rows_out,
+                        uint32_t* rec_weight_out, uint32_t* seed_rank_out, uint64_t* n_seeds_out, uint32_t* order_out);
+int shn_debug_fine_dict(shn_ctx* ctx, const shn_table* table, const uint64_t* queries, uint64_t n, uint32_t* id_out, uint64_t* home_line_out,
+                        uint64_t* stats_out /* [4] */);
 /* per walk (host arrays of shn_ext_n_walks entries): right/left extension lengths (n_right ==
  * 0xFFFFFFFF marks a void walk) and the weight sum including the seed (tot_wt, :351)          */
 int shn_ext_stats(shn_ctx* ctx, const shn_ext* e, uint32_t* n_right, uint32_t* n_left, uint64_t* tot_weight);

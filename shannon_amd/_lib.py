@@ -161,6 +161,8 @@ SIGNATURES = {
     "shn_debug_sorted_runs": (C.c_int, [vp, vp, C.c_uint64, C.c_int, vp, vp, vp, vp, vp]),
     "shn_debug_table_find": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_int, vp]),
     "shn_debug_table_view": (C.c_int, [vp, vp, vp, vp, vp]),
+    "shn_debug_ext_setup": (C.c_int, [vp, vp, C.c_uint32, vp, vp, vp, vp, vp, u64p, vp]),
+    "shn_debug_fine_dict": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, vp]),
     "shn_extend_sharded": (C.c_int, [vp, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, vpp]),
     "shn_ext_seed_info": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp]),
     "shn_ext_live_stats": (C.c_int, [vp, vp, u64p, vp, vp, vp, vp]),

@@ -1272,8 +1272,11 @@ static int ext_build_records(ExtRun& R, uint32_t min_weight) {
       unsigned long long* lines = nullptr;
       uint64_t n_lines = 0;
       { int rca = build_fine_dict(ctx, t, e->d_flags, &lines, &n_lines, e->d_claim); if (rca) return rca; }
+      // (the kernel strides over the k1-mers its grid does not cover: above 2^22 blocks -- 134 M k1-mers -- or, in tests, SHN_EXT_ADJ_BLOCKS)
+      const uint64_t full_grid = std::min<uint64_t>(cdiv(n * 8, 256), 1u << 22);
+      const uint64_t adj_blocks = shn_env_u64("SHN_EXT_ADJ_BLOCKS", full_grid, 1, full_grid);
       { TimerRegion ta(ctx, T_EXT_ADJ);                  // (one launch: bench.py's roofline entry for this kernel)
-        hipLaunchKernelGGL(ext_records_kernel, dim3((uint32_t)std::min<uint64_t>(cdiv(n * 8, 256), 1u << 22)), dim3(256), 0, s, shn_tab_idx(t),
+        hipLaunchKernelGGL(ext_records_kernel, dim3((uint32_t)adj_blocks), dim3(256), 0, s, shn_tab_idx(t),
                            e->d_flags, e->d_weight, n, t->k, t->canonical, e->d_rec, (const unsigned long long*)lines, n_lines); }
       (void)lines;                                       // (lives in the claims' block: overwritten when the claims are initialised below)
     }
@@ -1326,6 +1329,12 @@ static int ext_order_seeds(ExtRun& R) {
   return SHN_OK;
 }
 
+// the rank of the walk seeded on it into the record of every seed (hints and seed ranks live in the records: ext_records_kernel
+// wrote "none" into both)
+static void ext_seed_ranks(ExtRun& R) {
+  if (R.ns) hipLaunchKernelGGL(ext_seed_rank_kernel, dim3((uint32_t)cdiv(R.ns, 256)), dim3(256), 0, R.s, R.e->d_order, (uint64_t)R.ns, R.e->d_rec);
+}
+
 // 3. the scratch of the rounds -- memo pool, per-walk plan arrays, flags, claim logs -- and the first block
 static int ext_setup_rounds(ExtRun& R) {
   shn_ctx* ctx = R.ctx; const shn_table* t = R.t; hipStream_t s = R.s; shn_ext* e = R.e; const uint64_t n = R.n, ns = R.ns;
@@ -1358,8 +1367,7 @@ static int ext_setup_rounds(ExtRun& R) {
   if (sch.xtime) { HIP_TRY(R.bufs.get(&R.robsat, ns + 1)); HIP_TRY(hipMemsetAsync(R.robsat, 0, ns + 1, s)); }
   HIP_TRY(hipMemsetAsync(R.mvalid, 0, 2 * (ns + 1), s));
   HIP_TRY(hipMemsetAsync(R.pool, 0xFF, sch.pool_cap * 4, s));            // NONE32: "no entry"
-  // (hints and seed ranks live in the records: ext_records_kernel wrote "none" into both)
-  if (ns) hipLaunchKernelGGL(ext_seed_rank_kernel, dim3((uint32_t)cdiv(ns, 256)), dim3(256), 0, s, e->d_order, (uint64_t)ns, e->d_rec);
+  ext_seed_ranks(R);
   if (sch.digest) {
     int rd;
     if ((rd = ext_digest(ctx, e, 0, t->d_keys, n * 8, 1)) || (rd = ext_digest(ctx, e, 1, t->d_counts, n * 4, 2)) ||
@@ -1697,4 +1705,36 @@ extern "C" int shn_extend_sharded(shn_ctx* ctx, const shn_table* t, uint32_t min
   *out = R.e;
   R.e = nullptr;
   return SHN_OK;
+}
+
+// Test hook (tests/test_ext_setup_gpu.py): phases 1 and 2 of the driver above and the seed ranks, unchanged, for world = 1 -- no
+// scratch of the rounds, no walk -- and what they left on the device as host arrays.  Every output may be NULL.  Not part of the path.
+extern "C" int shn_debug_ext_setup(shn_ctx* ctx, const shn_table* t, uint32_t min_weight, uint32_t* weight_out /* n */, uint8_t* flags_out /* n */,
+                                   int32_t* rows_out /* 2n x 8: R[0..3], L[0..3] */, uint32_t* rec_weight_out /* 2n */, uint32_t* seed_rank_out /* 2n */,
+                                   uint64_t* n_seeds_out, uint32_t* order_out /* room for 2n, n_seeds written */) {
+  if (!ctx || !t) return shn_fail(SHN_ERR_ARG, "shn_debug_ext_setup: NULL argument");
+  if (2 * t->n >= 0x7FFFFFFFULL) return shn_fail(SHN_ERR_ARG, "shn_debug_ext_setup: table too large for 31-bit oriented ids");
+  SHN_ENTER(ctx);
+  shn_stage_begin(ctx);
+  ExtRun R(ctx, t, 1);
+  int rc;
+  if ((rc = ext_build_records(R, min_weight)) || (rc = ext_order_seeds(R))) return rc;
+  ext_seed_ranks(R);
+  HIP_TRY(hipGetLastError());
+  const uint64_t n = R.n, ns = R.ns;
+  hipStream_t s = R.s;
+  const shn_ext* e = R.e;
+  std::vector<Rec> rec((rows_out || rec_weight_out || seed_rank_out) ? 2 * n : 0);
+  if (n && weight_out) HIP_TRY(hipMemcpyAsync(weight_out, e->d_weight, n * 4, hipMemcpyDeviceToHost, s));
+  if (n && flags_out) HIP_TRY(hipMemcpyAsync(flags_out, e->d_flags, n, hipMemcpyDeviceToHost, s));
+  if (!rec.empty()) HIP_TRY(hipMemcpyAsync(rec.data(), e->d_rec, rec.size() * sizeof(Rec), hipMemcpyDeviceToHost, s));
+  if (ns && order_out) HIP_TRY(hipMemcpyAsync(order_out, e->d_order, ns * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (uint64_t o = 0; o < rec.size(); o++) {
+    if (rows_out) for (int b = 0; b < 4; b++) { rows_out[8 * o + b] = rec[o].R.v[b]; rows_out[8 * o + 4 + b] = rec[o].L.v[b]; }
+    if (rec_weight_out) rec_weight_out[o] = rec[o].weight;
+    if (seed_rank_out) seed_rank_out[o] = rec[o].seed_rank;
+  }
+  if (n_seeds_out) *n_seeds_out = ns;
+  return SHN_OK;                                   // (the run gives the extension under construction back)
 }

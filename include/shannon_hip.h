@@ -233,7 +233,9 @@ int shn_ext_stats_range(shn_ctx* ctx, const shn_ext* e, uint64_t lo, uint64_t n,
  * shn_ext_seed_info during the call-back only.                                                                                */
 typedef void (*shn_block_cb)(void* user, shn_ext* ext, uint64_t lo, uint64_t hi, int status);
 void shn_ext_set_block_callback(shn_block_cb cb, void* user);
-/* contig strings (ASCII) of the selected walk ranks, contig i at bases_out[offsets[i]..offsets[i+1]) */
+/* contig strings (ASCII) of the selected walk ranks, contig i at bases_out[offsets[i]..offsets[i+1]).  SHN_ERR_ARG, with nothing
+ * written outside the room given, on a rank out of range, a rank selected twice, or a room that is not the contig's length
+ * (k1 + n_right + n_left)                                                                              */
 int shn_ext_emit(shn_ctx* ctx, const shn_ext* e, const uint32_t* ranks, uint64_t n_sel, const uint64_t* offsets,
                  uint8_t* bases_out);
 /* weight (count in the strand-doubled input, 0 if absent or low-complexity) of k1-mer strings */

@@ -204,7 +204,7 @@ __global__ void ext_emit_claims_kernel(const u64* __restrict__ claim, uint64_t n
                                        const uint32_t* __restrict__ nr_a, const uint32_t* __restrict__ nl_a,
                                        const uint64_t* __restrict__ tkeys, int k, const uint64_t* __restrict__ out_off,
                                        uint8_t* __restrict__ out_bases, unsigned long long* __restrict__ counters) {
-  uint32_t n_wrote = 0, n_stray = 0;
+  uint32_t n_wrote = 0, n_stray = 0, n_misfit = 0;
   for (uint64_t y = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; y < n2; y += (uint64_t)gridDim.x * blockDim.x) {
     const u64 c = claim[y];
     const uint32_t r = RANK(c), pos = POS(c);
@@ -213,6 +213,8 @@ __global__ void ext_emit_claims_kernel(const u64* __restrict__ claim, uint64_t n
     if (t < 0) continue;
     const uint32_t nr = nr_a[r], nl = nl_a[r];
     if (nr == UNCLAIMED || pos > nr + nl) { n_stray++; continue; }    // claim of a void walk / beyond its recorded path
+    // the caller's room for this contig is not the contig's length: nothing of it is written (a shorter room would be overrun)
+    if (out_off[t + 1] - out_off[t] != (uint64_t)nr + nl + (uint64_t)k) { n_misfit++; continue; }
     uint8_t* dst = out_bases + out_off[t];
     const uint64_t str = oriented_string(tkeys, (uint32_t)y, k);
     if (pos == 0) for (int j = 0; j < k; j++) dst[nl + j] = "ACGT"[(str >> (2 * (k - 1 - j))) & 3];
@@ -220,13 +222,16 @@ __global__ void ext_emit_claims_kernel(const u64* __restrict__ claim, uint64_t n
     else dst[nl - 1 - (pos - nr - 1)] = "ACGT"[(str >> (2 * (k - 1))) & 3];
     n_wrote++;
   }
-  __shared__ unsigned long long blk[2];
-  if (threadIdx.x < 2) blk[threadIdx.x] = 0;
+  __shared__ unsigned long long blk[3];
+  if (threadIdx.x < 3) blk[threadIdx.x] = 0;
   __syncthreads();
   if (n_wrote) atomicAdd(&blk[0], (unsigned long long)n_wrote);
   if (n_stray) atomicAdd(&blk[1], (unsigned long long)n_stray);
+  if (n_misfit) atomicAdd(&blk[2], (unsigned long long)n_misfit);
   __syncthreads();
+  // counters: 0 written, 1 stray, 2 selected twice (ext_select_kernel), 3 claims of walks whose room does not fit
   if (threadIdx.x < 2 && blk[threadIdx.x]) atomicAdd(&counters[threadIdx.x], blk[threadIdx.x]);
+  if (threadIdx.x == 2 && blk[2]) atomicAdd(&counters[3], blk[2]);
 }
 
 // bases_out: the contigs' text on the host; dev_out (instead): the text stays on the device (total + 64 bytes, the tail zeroed; the
@@ -266,14 +271,15 @@ static int ext_emit_impl(shn_ctx* ctx, const shn_ext* e, const uint32_t* ranks, 
     hipLaunchKernelGGL(ext_emit_claims_kernel, dim3((uint32_t)std::min<uint64_t>(cdiv(2 * e->n, 256), 4096)), dim3(256), 0, s, e->d_claim, 2 * e->n, d_sel, ns,
                        e->d_nr, e->d_nl, e->table->d_keys, e->k, d_off, d_out, d_cnt);
   }
-  unsigned long long cnt[3] = {0, 0, 0};
+  unsigned long long cnt[4] = {0, 0, 0, 0};
   if (bases_out) HIP_TRY(hipMemcpyAsync(bases_out, d_out, total, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(cnt, d_cnt, 24, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(cnt, d_cnt, 32, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   shn_dev_free(d_sel); shn_dev_free(d_off); shn_dev_free(d_cnt); shn_dev_free(d_ranks);
   struct FreeOut { uint8_t* p; ~FreeOut() { if (p) shn_dev_free(p); } } free_out{d_out};
   HIP_TRY(hipGetLastError());
   if (cnt[2]) return shn_fail(SHN_ERR_ARG, "shn_ext_emit: a walk is selected twice");
+  if (cnt[3]) return shn_fail(SHN_ERR_ARG, "shn_ext_emit: offsets do not fit the walk lengths");
   // every base of every selected contig must have been written exactly once
   if (cnt[1] || cnt[0] != expect)
     return shn_fail(SHN_ERR_INTERNAL, "shn_ext_emit: claims do not match the recorded walks (k1-mers written " + std::to_string(cnt[0]) +

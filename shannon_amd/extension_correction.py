@@ -10,6 +10,7 @@ shared K-mers (:366-397), DFS components and the METIS / contig / remaining-bin 
 import ctypes as C
 import math
 import os, sys
+import queue, time
 import numpy as np
 from . import _lib, device
 
@@ -100,29 +101,7 @@ class Extension(object):
         _lib.check(_lib.lib().shn_ext_digests(self.h, dig.ctypes.data))
         return dig.reshape(8, 64)
 
-    @property
-    def n_walks(self):
-        return int(_lib.lib().shn_ext_n_walks(self.h))
-
-    @property
-    def iterations(self):
-        return int(_lib.lib().shn_ext_iterations(self.h))
-
-    @property
-    def total_steps(self):
-        return int(_lib.lib().shn_ext_total_steps(self.h))
-
-    @property
-    def wave_steps(self):
-        return int(_lib.lib().shn_ext_wave_steps(self.h))
-
-    @property
-    def fresh_steps(self):
-        return int(_lib.lib().shn_ext_fresh_steps(self.h))
-
-    @property
-    def dense_rounds(self):
-        return int(_lib.lib().shn_ext_dense_rounds(self.h))
+    COUNTERS = ("n_walks", "iterations", "total_steps", "wave_steps", "fresh_steps", "dense_rounds")   # properties: shn_ext_<name>(h)
 
     def stats(self):
         n = self.n_walks
@@ -214,6 +193,9 @@ class Extension(object):
         except Exception:
             pass
 
+
+for _n in Extension.COUNTERS:
+    setattr(Extension, _n, property(lambda self, _f="shn_ext_" + _n: int(getattr(_lib.lib(), _f)(self.h))))
 
 import threading as _threading
 _EMIT_TLS = _threading.local()
@@ -311,15 +293,20 @@ def contig_stage_gpu(ctx, buf, offs, k1, r=15, f=0.5):
         _lib.check(_lib.lib().shn_contig_stage(ctx.h, buf.ctypes.data, offs.ctypes.data, n, int(k1), int(r), float(f), acc.ctypes.data,
                                                best.ctypes.data, C.byref(h)))
     try:
-        n_acc, n_conn = C.c_uint64(0), C.c_uint64(0)
-        _lib.check(_lib.lib().shn_cgraph_sizes(h, C.byref(n_acc), C.byref(n_conn)))
-        coff = np.zeros(n_acc.value + 1, dtype=np.uint64)
-        cnb = np.zeros(max(1, n_conn.value), dtype=np.int32)
-        cw = np.zeros(max(1, n_conn.value), dtype=np.int32)
-        _lib.check(_lib.lib().shn_cgraph_export(h, coff.ctypes.data, cnb.ctypes.data, cw.ctypes.data))
+        return (acc[:n], best[:n]) + _cgraph_export(h)
     finally:
         _lib.lib().shn_cgraph_destroy(h)
-    return acc[:n], best[:n], coff, cnb[:n_conn.value], cw[:n_conn.value]
+
+
+def _cgraph_export(h):
+    """(coff, cnb, cw) of a shn_cgraph: the connections as CSR (see contig_stage)"""
+    n_acc, n_conn = C.c_uint64(0), C.c_uint64(0)
+    _lib.check(_lib.lib().shn_cgraph_sizes(h, C.byref(n_acc), C.byref(n_conn)))
+    coff = np.zeros(n_acc.value + 1, dtype=np.uint64)
+    cnb = np.zeros(max(1, n_conn.value), dtype=np.int32)
+    cw = np.zeros(max(1, n_conn.value), dtype=np.int32)
+    _lib.check(_lib.lib().shn_cgraph_export(h, coff.ctypes.data, cnb.ctypes.data, cw.ctypes.data))
+    return coff, cnb[:n_conn.value], cw[:n_conn.value]
 
 
 def metis_text(members, n_edges, coff, cnb, cw):
@@ -404,13 +391,7 @@ class ContigGraph(object):
         return acc
 
     def connections(self):
-        n_acc, n_conn = C.c_uint64(0), C.c_uint64(0)
-        _lib.check(_lib.lib().shn_cgraph_sizes(self.h, C.byref(n_acc), C.byref(n_conn)))
-        coff = np.zeros(n_acc.value + 1, dtype=np.uint64)
-        cnb = np.zeros(max(1, n_conn.value), dtype=np.int32)
-        cw = np.zeros(max(1, n_conn.value), dtype=np.int32)
-        _lib.check(_lib.lib().shn_cgraph_export(self.h, coff.ctypes.data, cnb.ctypes.data, cw.ctypes.data))
-        return coff.tolist(), cnb[:n_conn.value].tolist(), cw[:n_conn.value].tolist()
+        return tuple(a.tolist() for a in _cgraph_export(self.h))
 
     def close(self):
         if self.h:
@@ -531,279 +512,321 @@ def foreign_interference(ctx, local, acc, best_count, foreign, r=15, f=0.5):
     return int(len(np.unique(pc[bad])))
 
 
-def run_correction(ctx, table, min_weight=3, min_length=75, comp_size_threshold=500, r=15, f=0.5, want_allowed=True, timings=None,
-                   shard=None, merge=None, gather=None, table_size=None, want_weight_arrays=False):
-    """extension_correction.run_correction (extension_correction.py:309-524) on a device k1-mer
-    table.  Returns an ExtensionResult: contigs, allowed {k1mer: int}, connections, components,
-    single_contigs, big_components [(contigs, metis_text)], remaining [[contig...]].
-    shard = (world, rank) + merge(local) -> global: the walks are sharded by connected component; `merge` receives this
-    rank's candidates [(seed weight, seed key, contig)] and returns the candidates of all ranks (any order).
-    gather (instead of merge): an object with .world, .rank, .all_gather(obj) -> [obj per rank], .all_reduce_max(int): the
-    contig stages are sharded as well -- every rank decides its own candidates, a GPU r-mer join against the other shards'
-    accepted contigs proves that none of them could have changed a duplicate_check decision (foreign_interference), else all
-    ranks fall back to the global sequential pass.
-    want_weight_arrays (--inDisk): res.k1mer_keys / res.k1mer_weights = the distinct k1-mers of the contigs (packed, ascending) and
-    their weights -- what `allowed` holds, as two arrays from one shn_ext_weights call, without a dictionary entry per window.
-    table_size: the number of k1-mers of the JOB when `table` is this rank's share of it already (whole components: shard = None
-    with a gather) -- the choice between the contig stages must be the same on every rank."""
-    import time as _t
-    T = timings if timings is not None else {}
-    _t0 = [_t.time()]
+MERGED, DEVICE, SHARDED_DEVICE, SHARDED_GUARDED, BESIDE, AFTER = "merged", "device", "sharded device", "sharded guarded", "beside", "after"
+
+
+def contig_plan(n_k1mers, world, has_merge, env=os.environ):
+    """Which of its six ways run_correction takes through the contig stage (duplicate_check + contig graph) behind the walks of a
+    table of n_k1mers k1-mers (those of the JOB: the choice is the same on every rank) on `world` ranks; each is the function
+    _contigs_<plan> below.  A merge() wins over a gather; large tables (BASELINE configs[2]: 20,000 genes, several 10^5 candidate
+    contigs; SHN_CONTIG_GPU=1 / 0 forces / forbids it) take the stage to the GPU; SHN_EXT_PIPELINE=0 keeps it from running beside
+    the walks."""
+    if has_merge:
+        return MERGED
+    cg = env.get("SHN_CONTIG_GPU", "")
+    if cg == "1" or (cg != "0" and n_k1mers >= 20_000_000):
+        return SHARDED_DEVICE if world > 1 else DEVICE
+    if world > 1:
+        return SHARDED_GUARDED
+    return BESIDE if env.get("SHN_EXT_PIPELINE", "1") != "0" else AFTER
+
+
+class _BesideWalks(object):
+    """The contig stage beside the walks (one GPU, or one shard): the rank blocks of the walks become final one after the other,
+    heaviest seeds first -- the order in which the reference's loop finishes contigs.  The candidates of a final block are filtered
+    and emitted inside the walk call (on_block, the block call-back) and handed to a host thread that runs duplicate_check +
+    contig_connections on them while the GPU iterates on the later blocks.  void: the fixpoint audit reopened blocks -- what was
+    handed over does not count and the stage runs after the walks."""
+
+    def __init__(self, k1, r, f, min_length, min_weight):
+        self.k1, self.min_length, self.min_weight = k1, min_length, min_weight
+        self.q, self.void, self.error, self.cb_seconds, self.busy, self.t_start = queue.Queue(), False, None, 0.0, 0.0, time.time()
+        self.cg, self.accepted = None, []                                    # the worker's graph and the contigs it accepted
+        self.strings, self.ranks, self._acc, self._best = [], [], [], []     # every candidate handed over, in seed order
+        self.thread = _threading.Thread(target=self._worker, args=(k1, r, f), daemon=True)
+        self.thread.start()
+
+    acc = property(lambda self: np.concatenate(self._acc) if self._acc else np.zeros(0, np.int32))
+    best = property(lambda self: np.concatenate(self._best) if self._best else np.zeros(0, np.int32))
+
+    def _worker(self, k1, r, f):
+        try:
+            self.cg = ContigGraph(k1, r, f)
+            while True:
+                item = self.q.get()
+                if item is None:
+                    break
+                w0 = time.time()
+                acc = self.cg.add(item)
+                self.accepted += [item[i] for i in np.nonzero(acc)[0].tolist()]
+                self.strings += item
+                self._acc.append(acc)
+                self._best.append(self.cg.best)
+                self.busy += time.time() - w0
+                if os.environ.get("SHN_DEBUG"):
+                    sys.stderr.write("[pipeline] contig stage: %d candidates (%d bases) %.1f ms, started %.1f ms after the walks began\n"
+                                     % (len(item), sum(len(x) for x in item), (time.time() - w0) * 1e3, (w0 - self.t_start) * 1e3))
+        except BaseException as ex:                       # surfaced on the main thread after the walks (finish)
+            self.error = ex
+
+    def on_block(self, view, lo, hi, status):
+        c0 = time.time()
+        try:
+            if status < 0:
+                self.void = True
+            elif not self.void and self.error is None and hi > lo:
+                bnr, bnl, btw = view.stats_range(lo, hi - lo)
+                alive = np.nonzero(bnr != UNCLAIMED)[0]
+                keep_b = accept_filter((alive + lo).astype(np.uint32), bnr[alive], bnl[alive], btw[alive], self.k1, self.min_length, self.min_weight)
+                if keep_b:
+                    self.ranks += [x[0] for x in keep_b]
+                    self.q.put(view.emit([x[0] for x in keep_b], [x[1] for x in keep_b]))
+                if os.environ.get("SHN_DEBUG"):
+                    sys.stderr.write("[pipeline] block [%d,%d) final %.1f ms after the walks began: %d live walks, %d candidates, call-back %.1f ms\n"
+                                     % (lo, hi, (c0 - self.t_start) * 1e3, len(alive), len(keep_b), (time.time() - c0) * 1e3))
+        except _lib.ShannonError:
+            # a block that is not at its fixpoint after all (its claims do not match its walks): the audit at the end of
+            # the walks reopens it; what was handed over is void and the stage runs after the walks
+            self.void = True
+        except BaseException as ex:                       # (an exception cannot cross the C frames of the walk call)
+            self.error = ex
+        self.cb_seconds += time.time() - c0
+
+    def finish(self):
+        """behind the walk call: the worker has taken everything handed over; its error, or the call-back's, is raised here"""
+        self.q.put(None)
+        self.thread.join()
+        if self.void or self.error is not None:
+            self.close()
+        if self.error is not None:
+            raise self.error
+
+    def connections(self):
+        return self.cg.connections()
+
+    def close(self):
+        """worker joined, graph released: any number of times, on every way out"""
+        self.q.put(None)
+        self.thread.join()
+        if self.cg is not None:
+            self.cg.close()
+
+
+def _lap_timer(T):
+    """lap(name): the seconds since the last lap (or now) are added to T[name]"""
+    t0 = [time.time()]
 
     def lap(name):
-        now = _t.time()
-        T[name] = T.get(name, 0.0) + now - _t0[0]
-        _t0[0] = now
+        now = time.time()
+        T[name] = T.get(name, 0.0) + now - t0[0]
+        t0[0] = now
+    return lap
 
-    k1 = table.k
-    UNCL = 0xFFFFFFFF
-    # Pipelined (single GPU, no sharding): the rank blocks of the walks become final one after the other, heaviest seeds
-    # first -- the order in which the reference's loop finishes contigs.  The candidates of a final block are filtered and
-    # emitted inside the walk call (block call-back) and handed to a host thread that runs duplicate_check +
-    # contig_connections on them while the GPU iterates on the later blocks.
-    pipe = None
-    # Large tables (BASELINE configs[2]: 20,000 genes, several 10^5 candidate contigs): the contig stage runs after the walks with
-    # its sorts on the GPU (contig_stage_gpu) instead of beside them on one host thread.  SHN_CONTIG_GPU=1 / 0 forces / forbids it.
-    _cg = os.environ.get("SHN_CONTIG_GPU", "")
-    big = _cg == "1" or (_cg != "0" and (len(table) if table_size is None else int(table_size)) >= 20_000_000)
-    gpu_contigs = merge is None and (gather is None or gather.world <= 1) and big
-    # ... and on several ranks: the walks sharded by connected component, the candidates of all shards gathered (0.3 GB at BASELINE
-    # configs[2]) and merged into the global seed order on every rank, ONE replicated GPU contig stage over them -- instead of every
-    # rank walking the whole table (the shards' own contig stage is the sequential host loop: 25 s at that size)
-    gpu_sharded = merge is None and gather is not None and gather.world > 1 and big
-    if merge is None and not gpu_contigs and not gpu_sharded and os.environ.get("SHN_EXT_PIPELINE", "1") != "0":
-        import threading, queue
 
-        class _Pipe(object):
-            pass
-        pipe = _Pipe()
-        pipe.q, pipe.void, pipe.error, pipe.cb_seconds, pipe.accepted, pipe.cg = queue.Queue(), False, None, 0.0, [], None
-        pipe.n_blocks, pipe.busy, pipe.t_start = 0, 0.0, _t.time()
-        pipe.strings, pipe.ranks, pipe.acc, pipe.best = [], [], [], []     # every candidate handed over, in seed order
-
-        def _worker():
-            try:
-                pipe.cg = ContigGraph(k1, r, f)
-                while True:
-                    item = pipe.q.get()
-                    if item is None:
-                        break
-                    w0 = _t.time()
-                    acc = pipe.cg.add(item)
-                    pipe.accepted += [item[i] for i in np.nonzero(acc)[0].tolist()]
-                    pipe.strings += item
-                    pipe.acc.append(acc)
-                    pipe.best.append(pipe.cg.best)
-                    pipe.busy += _t.time() - w0
-                    if os.environ.get("SHN_DEBUG"):
-                        sys.stderr.write("[pipeline] contig stage: %d candidates (%d bases) %.1f ms, started %.1f ms after the walks began\n"
-                                         % (len(item), sum(len(x) for x in item), (_t.time() - w0) * 1e3, (w0 - pipe.t_start) * 1e3))
-            except BaseException as ex:                       # surfaced on the main thread after the walks
-                pipe.error = ex
-        pipe.thread = threading.Thread(target=_worker, daemon=True)
-        pipe.thread.start()
-
-        def _on_block(view, lo, hi, status):
-            c0 = _t.time()
-            try:
-                if status < 0:
-                    pipe.void = True
-                elif not pipe.void and pipe.error is None and hi > lo:
-                    bnr, bnl, btw = view.stats_range(lo, hi - lo)
-                    alive = np.nonzero(bnr != UNCL)[0]
-                    keep_b = accept_filter((alive + lo).astype(np.uint32), bnr[alive], bnl[alive], btw[alive], k1, min_length, min_weight)
-                    if keep_b:
-                        pipe.ranks += [x[0] for x in keep_b]
-                        pipe.q.put(view.emit([x[0] for x in keep_b], [x[1] for x in keep_b]))
-                    pipe.n_blocks += 1
-                    if os.environ.get("SHN_DEBUG"):
-                        sys.stderr.write("[pipeline] block [%d,%d) final %.1f ms after the walks began: %d live walks, %d candidates, call-back %.1f ms\n"
-                                         % (lo, hi, (c0 - pipe.t_start) * 1e3, len(alive), len(keep_b), (_t.time() - c0) * 1e3))
-            except _lib.ShannonError:
-                # a block that is not at its fixpoint after all (its claims do not match its walks): the audit at the end of
-                # the walks reopens it; what was handed over is void and the stage runs after the walks
-                pipe.void = True
-            except BaseException as ex:                       # (an exception cannot cross the C frames of the walk call)
-                pipe.error = ex
-            pipe.cb_seconds += _t.time() - c0
-    if pipe is not None:
-        # the call-back needs the interpreter lock while the worker may hold it between its native calls: hand it over
-        # quickly (the default switch interval of 5 ms would stall the walk loop once per block)
-        _swi = sys.getswitchinterval()
-        sys.setswitchinterval(2e-4)
-    try:
-        ext = Extension(ctx, table, min_weight, shard=shard, on_block=_on_block if pipe is not None else None)
-    finally:
-        if pipe is not None:
-            pipe.q.put(None)
-            sys.setswitchinterval(_swi)
-    lap("ext.gpu_walks")
-    if pipe is not None:
-        T["ext.gpu_walks"] -= pipe.cb_seconds
-        T["ext.filter+emit (inside the walks)"] = T.get("ext.filter+emit (inside the walks)", 0.0) + pipe.cb_seconds
-        pipe.thread.join()
-        if pipe.error is not None:
-            raise pipe.error
-        if pipe.void:                                  # the fixpoint audit reopened blocks: what was handed over is void
-            pipe.cg.close()
-            pipe = None
-    if pipe is not None:
-        keep = None
+def _candidates(ext, k1, min_length, min_weight, lap, arrays=False):
+    """the walks that pass the accept filter, in seed order: [(rank, contig length)]; arrays (the device plans): the two as arrays,
+    and the filter itself on the device (shn_ext_accept) unless SHN_EXT_ACCEPT_DEVICE=0"""
+    if arrays and os.environ.get("SHN_EXT_ACCEPT_DEVICE", "1") != "0":
+        keep = ext.accept(k1, min_length, min_weight)
     else:
-        # non-void walks long enough for the accept filter's length clause, in seed order (compacted on the GPU)
-        if (gpu_contigs or gpu_sharded) and os.environ.get("SHN_EXT_ACCEPT_DEVICE", "1") != "0":
-            keep_r, keep_l = ext.accept(k1, min_length, min_weight)           # (the filter itself on the device)
-            keep = None
-        else:
-            live, nr, nl, tw = ext.live_stats(min_length - k1)
-            lap("ext.filter.stats")
-            if gpu_contigs or gpu_sharded:
-                keep_r, keep_l = accept_filter(live, nr, nl, tw, k1, min_length, min_weight, arrays=True)
-                keep = None
-            else:
-                keep = accept_filter(live, nr, nl, tw, k1, min_length, min_weight)
+        live, nr, nl, tw = ext.live_stats(min_length - k1)     # non-void, long enough for the length clause (compacted on the GPU)
+        lap("ext.filter.stats")
+        keep = accept_filter(live, nr, nl, tw, k1, min_length, min_weight, arrays=arrays)
     lap("ext.filter")
-    csr = None                                         # (coff, cnb, cw): connections in dict insertion order, 1-based neighbours
-    contigs = ["buffer"]
-    contig_raw = None
-    conn = None
-    sharded_contigs = False
-    dev_text = None
-    if gpu_contigs and not gpu_sharded and len(keep_r) and os.environ.get("SHN_EXT_EMIT_DEVICE", "1") != "0":
-        # one rank: the candidates' text never leaves the device (0.3 GB at BASELINE configs[2], once down and once up before);
-        # the accepted contigs are fetched afterwards
-        dev_text, offs = ext.emit_device(keep_r, keep_l)
-        buf = dev_text
-        lap("ext.emit")
-    elif gpu_contigs or gpu_sharded:
-        buf, offs = ext.emit_raw(keep_r, keep_l, reuse=True) if len(keep_r) else (np.zeros(0, np.uint8), np.zeros(1, np.uint64))
-        lap("ext.emit")
-    if gpu_contigs or gpu_sharded:
-        if gpu_sharded:
-            # every rank's candidates -> the same merged list everywhere, in the order of the reference's seed loop
-            # (weight descending, seed k1-mer ascending; a seed lies in exactly one shard, so the keys are distinct)
-            skey, sw = ext.seed_info(keep_r)
-            # (as tensors where the gather offers it -- the ranks of a real job: 0.3 GB of candidate text at BASELINE configs[2], which
-            # used to travel as pickled objects)
-            mine_ = (np.asarray(sw, dtype=np.int64), np.asarray(skey, dtype=np.uint64), np.asarray(offs, dtype=np.uint64),
-                     np.ascontiguousarray(buf[:int(offs[-1])]))
-            parts = gather.all_gather_arrays(mine_) if hasattr(gather, "all_gather_arrays") else gather.all_gather(mine_)
-            lap("ext.gathers")
-            w_all = np.concatenate([p[0] for p in parts])
-            k_all = np.concatenate([p[1] for p in parts])
-            base, segs = 0, []
-            for p in parts:
-                segs.append(p[2][:-1].astype(np.uint64) + np.uint64(base))
-                base += int(p[2][-1])
-            src_off = np.concatenate(segs + [np.array([base], dtype=np.uint64)])
-            order = np.lexsort((k_all, -w_all))
-            buf, offs = _lib.gather_segments(np.concatenate([p[3] for p in parts]), src_off, order, threads=_lib.host_cpus())
-            lap("ext.merge")
-        acc, _best, coff, cnb, cw = contig_stage_gpu(ctx, buf, offs, k1, r, f)
-        csr = (coff, cnb, cw)
-        ai = np.nonzero(acc)[0]
-        if dev_text is not None:
-            # the accepted contigs only, one after the other: from here on they are "the candidates", all of them accepted
-            buf, offs = dev_text.segments(offs, ai)
-            dev_text.close()
-            ai = np.arange(len(ai), dtype=np.int64)
-        buf = np.ascontiguousarray(buf)
-        raw = memoryview(buf)                              # (only the accepted tenth is ever turned into strings, slice by slice)
-        n_before = len(contigs)
-        contigs += [str(raw[a:b], "ascii") for a, b in zip(offs[ai].tolist(), offs[ai + 1].tolist())]
-        del raw
-        if n_before == 1:
-            # the accepted contigs as bytes (candidate buffer, its offsets, accepted candidate per contig): what lays contig text out
-            # for the device again (kmers_for_component) gathers segments instead of joining and encoding 80 MB of strings
-            contig_raw = (buf, np.asarray(offs, dtype=np.uint64), ai.astype(np.int64))
-        strings = None
-    else:
-        strings = (ext.emit([x[0] for x in keep], [x[1] for x in keep]) if keep else []) if pipe is None else None
-    if gpu_contigs or gpu_sharded:
-        pass
-    elif gather is not None and gather.world > 1:
-        if pipe is not None:                           # the shard's contig stage ran beside its walks
-            strings = pipe.strings
-            skey, sw = ext.seed_info(pipe.ranks)
-            acc = np.concatenate(pipe.acc) if pipe.acc else np.zeros(0, np.int32)
-            bestc = np.concatenate(pipe.best) if pipe.best else np.zeros(0, np.int32)
-            coff, cnb, cw = pipe.cg.connections()
-            pipe.cg.close()
-            T["ext.contig_graph (beside the walks)"] = T.get("ext.contig_graph (beside the walks)", 0.0) + pipe.busy
-            pipe = None
-        else:
-            skey, sw = ext.seed_info([x[0] for x in keep])
-            acc, coff, cnb, cw, bestc = contig_stage(strings, k1, r, f, want_best=True)
-        local = list(zip(sw.tolist(), skey.tolist(), strings))
-        lap("ext.emit")
-        mine = [local[i] for i in np.nonzero(acc)[0].tolist()]              # accepted here, local order
-        lap("ext.contig_graph")
-        everybody = gather.all_gather(mine)
-        lap("ext.gathers")
-        foreign = [c for rk, lst in enumerate(everybody) if rk != gather.rank for c in lst]
-        unsafe = foreign_interference(ctx, local, acc, bestc, foreign, r, f)
-        lap("ext.guard")
-        safe = gather.all_reduce_max(1 if unsafe else 0) == 0
-        lap("ext.gathers")
-        if safe:
-            sharded_contigs = True
-            conn = {}
-            conns = gather.all_gather((coff, cnb, cw))
-            lap("ext.gathers")
-            items = sorted(((c[0], c[1], rk, j) for rk, lst in enumerate(everybody) for j, c in enumerate(lst)), key=lambda t: (-t[0], t[1]))
-            gid = {(rk, j): g + 1 for g, (_w, _k, rk, j) in enumerate(items)}    # global 1-based accepted index
-            for _w, _k, rk, j in items:
-                contigs.append(everybody[rk][j][2])
-            for _w, _k, rk, j in items:
-                o, nb_, w_ = conns[rk]
-                conn[gid[(rk, j)]] = {gid[(rk, q - 1)]: ww for q, ww in zip(nb_[o[j]:o[j + 1]], w_[o[j]:o[j + 1]])}
-            lap("ext.merge")
-        else:
-            allc = [c for lst in gather.all_gather(local) for c in lst]
-            allc.sort(key=lambda c: (-c[0], c[1]))
-            strings = [c[2] for c in allc]
-    elif merge is not None:
-        # candidates of all shards in the global walk order (weight descending, seed k1-mer ascending; :334-345)
-        skey, sw = ext.seed_info([x[0] for x in keep])
-        allc = merge(list(zip(sw.tolist(), skey.tolist(), strings)))
-        allc.sort(key=lambda c: (-c[0], c[1]))
-        strings = [c[2] for c in allc]
-        lap("ext.emit")
-    else:
-        lap("ext.emit")
+    return keep
 
-    # duplicate_check + contig graph, sequential over candidates in seed order (:358-397)
-    if gpu_contigs or gpu_sharded:
-        pass
-    elif pipe is not None:                             # already done, beside the walks
-        csr = pipe.cg.connections()
-        pipe.cg.close()
-        contigs += pipe.accepted
-        T["ext.contig_graph (beside the walks)"] = T.get("ext.contig_graph (beside the walks)", 0.0) + pipe.busy
-    elif not sharded_contigs:
-        acc, coff, cnb, cw = contig_stage(strings, k1, r, f)
-        for i in np.nonzero(acc)[0].tolist():
-            contigs.append(strings[i])
-        csr = (coff, cnb, cw)
-    if csr is None:                                    # merged shards: the dicts in global order -> CSR
-        coff, cnb, cw = [0], [], []
-        for a in range(1, len(contigs)):
-            d = conn.get(a, {})
-            cnb += list(d.keys())
-            cw += list(d.values())
-            coff.append(len(cnb))
-        csr = (coff, cnb, cw)
+
+def _emit_strings(ext, keep):
+    return ext.emit([x[0] for x in keep], [x[1] for x in keep]) if keep else []
+
+
+def _emit_bytes(ext, keep_r, keep_l):
+    return ext.emit_raw(keep_r, keep_l, reuse=True) if len(keep_r) else (np.zeros(0, np.uint8), np.zeros(1, np.uint64))
+
+
+def _host_stage(strings, k1, r, f):
+    """duplicate_check + contig graph, sequential over candidates in seed order (:358-397) -> contigs, csr, no contig_raw"""
+    acc, coff, cnb, cw = contig_stage(strings, k1, r, f)
+    return [strings[i] for i in np.nonzero(acc)[0].tolist()], (coff, cnb, cw), None
+
+
+def _device_stage(ctx, buf, offs, k1, r, f):
+    """the same over candidates as bytes (a host array or a DevText, which is closed) on the GPU -> contigs, csr, contig_raw"""
+    acc, _best, coff, cnb, cw = contig_stage_gpu(ctx, buf, offs, k1, r, f)
+    ai = np.nonzero(acc)[0]
+    if isinstance(buf, DevText):
+        # the accepted contigs only, one after the other: from here on they are "the candidates", all of them accepted
+        text = buf
+        buf, offs = text.segments(offs, ai)
+        text.close()
+        ai = np.arange(len(ai), dtype=np.int64)
+    buf = np.ascontiguousarray(buf)
+    raw = memoryview(buf)                              # (only the accepted tenth is ever turned into strings, slice by slice)
+    contigs = [str(raw[a:b], "ascii") for a, b in zip(offs[ai].tolist(), offs[ai + 1].tolist())]
+    del raw
+    # contig_raw, the accepted contigs as bytes (candidate buffer, its offsets, accepted candidate per contig): what lays contig text out
+    # for the device again (kmers_for_component) gathers segments instead of joining and encoding 80 MB of strings
+    return contigs, (coff, cnb, cw), (buf, np.asarray(offs, dtype=np.uint64), ai.astype(np.int64))
+
+
+def _contigs_merged(ext, merge, k1, min_length, min_weight, r, f, lap):
+    """MERGED: the candidates of all shards, from merge(), in the global walk order (weight descending, seed k1-mer ascending;
+    :334-345) through the host's contig stage"""
+    keep = _candidates(ext, k1, min_length, min_weight, lap)
+    strings = _emit_strings(ext, keep)
+    skey, sw = ext.seed_info([x[0] for x in keep])
+    allc = merge(list(zip(sw.tolist(), skey.tolist(), strings)))
+    allc.sort(key=lambda c: (-c[0], c[1]))
+    strings = [c[2] for c in allc]
+    lap("ext.emit")
+    return _host_stage(strings, k1, r, f)
+
+
+def _contigs_device(ctx, ext, k1, min_length, min_weight, r, f, lap):
+    """DEVICE: the contig stage after the walks with its sorts on the GPU (contig_stage_gpu) instead of beside them on one host
+    thread.  The candidates' text never leaves the device (0.3 GB at BASELINE configs[2], once down and once up before); the accepted
+    contigs are fetched afterwards (SHN_EXT_EMIT_DEVICE=0: the text through the host)."""
+    keep_r, keep_l = _candidates(ext, k1, min_length, min_weight, lap, arrays=True)
+    if len(keep_r) and os.environ.get("SHN_EXT_EMIT_DEVICE", "1") != "0":
+        buf, offs = ext.emit_device(keep_r, keep_l)
+    else:
+        buf, offs = _emit_bytes(ext, keep_r, keep_l)
+    try:
+        lap("ext.emit")
+        return _device_stage(ctx, buf, offs, k1, r, f)
+    finally:
+        if isinstance(buf, DevText):
+            buf.close()
+
+
+def _contigs_sharded_device(ctx, ext, gather, k1, min_length, min_weight, r, f, lap):
+    """SHARDED_DEVICE: the walks sharded by connected component, the candidates of all shards gathered (0.3 GB at BASELINE configs[2])
+    and merged into the global seed order on every rank (weight descending, seed k1-mer ascending; a seed lies in exactly one shard, so
+    the keys are distinct), ONE replicated GPU contig stage over them -- instead of every rank walking the whole table (the shards'
+    own contig stage is the sequential host loop: 25 s at that size)"""
+    keep_r, keep_l = _candidates(ext, k1, min_length, min_weight, lap, arrays=True)
+    buf, offs = _emit_bytes(ext, keep_r, keep_l)
+    lap("ext.emit")
+    skey, sw = ext.seed_info(keep_r)
+    # (as tensors where the gather offers it -- the ranks of a real job: 0.3 GB of candidate text at BASELINE configs[2], which
+    # used to travel as pickled objects)
+    mine = (np.asarray(sw, dtype=np.int64), np.asarray(skey, dtype=np.uint64), np.asarray(offs, dtype=np.uint64),
+            np.ascontiguousarray(buf[:int(offs[-1])]))
+    parts = gather.all_gather_arrays(mine) if hasattr(gather, "all_gather_arrays") else gather.all_gather(mine)
+    lap("ext.gathers")
+    w_all = np.concatenate([p[0] for p in parts])
+    k_all = np.concatenate([p[1] for p in parts])
+    base, segs = 0, []
+    for p in parts:
+        segs.append(p[2][:-1].astype(np.uint64) + np.uint64(base))
+        base += int(p[2][-1])
+    src_off = np.concatenate(segs + [np.array([base], dtype=np.uint64)])
+    order = np.lexsort((k_all, -w_all))
+    buf, offs = _lib.gather_segments(np.concatenate([p[3] for p in parts]), src_off, order, threads=_lib.host_cpus())
+    lap("ext.merge")
+    return _device_stage(ctx, buf, offs, k1, r, f)
+
+
+def _contigs_sharded_guarded(ctx, ext, beside, gather, k1, min_length, min_weight, r, f, lap):
+    """SHARDED_GUARDED: a contig stage per shard (beside: its hand-over where it ran beside the shard's walks and held, else None),
+    the guard (foreign_interference) and the merge of the accepted contigs -- or the global sequential pass on every rank"""
+    if beside is not None:
+        lap("ext.filter")
+        strings, acc, bestc = beside.strings, beside.acc, beside.best
+        skey, sw = ext.seed_info(beside.ranks)
+        coff, cnb, cw = beside.connections()
+    else:
+        keep = _candidates(ext, k1, min_length, min_weight, lap)
+        strings = _emit_strings(ext, keep)
+        skey, sw = ext.seed_info([x[0] for x in keep])
+        acc, coff, cnb, cw, bestc = contig_stage(strings, k1, r, f, want_best=True)
+    local = list(zip(sw.tolist(), skey.tolist(), strings))
+    lap("ext.emit")
+    mine = [local[i] for i in np.nonzero(acc)[0].tolist()]              # accepted here, local order
     lap("ext.contig_graph")
+    everybody = gather.all_gather(mine)
+    lap("ext.gathers")
+    foreign = [c for rk, lst in enumerate(everybody) if rk != gather.rank for c in lst]
+    unsafe = foreign_interference(ctx, local, acc, bestc, foreign, r, f)
+    lap("ext.guard")
+    safe = gather.all_reduce_max(1 if unsafe else 0) == 0
+    lap("ext.gathers")
+    if not safe:                                       # the global sequential pass over everybody's candidates, on every rank
+        allc = [c for lst in gather.all_gather(local) for c in lst]
+        allc.sort(key=lambda c: (-c[0], c[1]))
+        return _host_stage([c[2] for c in allc], k1, r, f)
+    conns = gather.all_gather((coff, cnb, cw))
+    lap("ext.gathers")
+    items = sorted(((c[0], c[1], rk, j) for rk, lst in enumerate(everybody) for j, c in enumerate(lst)), key=lambda t: (-t[0], t[1]))
+    gid = {(rk, j): g + 1 for g, (_w, _k, rk, j) in enumerate(items)}    # global 1-based accepted index
+    contigs, conn = [everybody[rk][j][2] for _w, _k, rk, j in items], {}
+    for _w, _k, rk, j in items:
+        o, nb_, w_ = conns[rk]
+        conn[gid[(rk, j)]] = {gid[(rk, q - 1)]: ww for q, ww in zip(nb_[o[j]:o[j + 1]], w_[o[j]:o[j + 1]])}
+    lap("ext.merge")
+    coff, cnb, cw = [0], [], []                        # merged shards: the dicts in global order -> CSR
+    for a in range(1, len(contigs) + 1):
+        cnb += list(conn[a].keys())
+        cw += list(conn[a].values())
+        coff.append(len(cnb))
+    return contigs, (coff, cnb, cw), None
+
+
+def _contigs_beside(beside, lap):
+    """BESIDE: already done, beside the walks"""
+    lap("ext.filter")
+    lap("ext.emit")
+    return beside.accepted, beside.connections(), None
+
+
+def _contigs_after(ext, k1, min_length, min_weight, r, f, lap):
+    """AFTER: host filter + emit + contig stage behind the walks"""
+    strings = _emit_strings(ext, _candidates(ext, k1, min_length, min_weight, lap))
+    lap("ext.emit")
+    return _host_stage(strings, k1, r, f)
+
+
+def bin_components(contigs, coff, cnb, cw, comp_size_threshold, res=None):
+    """DFS components of the contig graph (:417-434, native: shn_contig_components) and the file products (:458-513): sets conn_*,
+    comp_*, single_contigs, single_ids, big_components and remaining of res (without one, of a new ExtensionResult) and returns it.
+    contigs: the accepted contigs; coff / cnb / cw: their connections as CSR (row a = contig a + 1, neighbours 1-based, in dict
+    insertion order).  Host code only."""
+    res = ExtensionResult() if res is None else res
+    coff_a = np.asarray(coff, dtype=np.uint64)
+    cnb_a = np.asarray(cnb, dtype=np.int32)
+    cw_a = np.asarray(cw, dtype=np.int32)
+    _comp_of, members, comp_off, comp_edges = contig_components(coff_a, cnb_a)
+    res.conn_off, res.conn_nb, res.conn_w = coff_a.tolist(), cnb_a.tolist(), cw_a.tolist()
+    res.comp_members, res.comp_off = members.tolist(), comp_off.tolist()
+    mem, co = res.comp_members, res.comp_off
+    sizes = np.diff(comp_off.astype(np.int64)) if len(comp_off) > 1 else np.zeros(0, np.int64)
+    res.single_contigs, res.big_components, res.remaining = [], [], [[]]
+    res.single_ids = []                               # index in contigs of every single contig
+    cur_size = 0
+    for j, sz in enumerate(sizes.tolist()):
+        if sz == 1:
+            res.single_contigs.append(contigs[mem[co[j]] - 1])
+            res.single_ids.append(mem[co[j]] - 1)
+        elif sz > comp_size_threshold:
+            mm = mem[co[j]:co[j + 1]]
+            res.big_components.append(([contigs[c - 1] for c in mm], metis_text(mm, int(comp_edges[j]), coff_a, cnb_a, cw_a)))
+        else:
+            res.remaining[-1].extend(contigs[c - 1] for c in mem[co[j]:co[j + 1]])
+            cur_size += sz
+            if cur_size > comp_size_threshold:
+                res.remaining.append([])
+                cur_size = 0
+    return res
+
+
+def _finish_result(ext, contigs, csr, contig_raw, k1, comp_size_threshold, want_allowed, want_weight_arrays, lap):
+    """the ExtensionResult of run_correction; the walk state is released as soon as it has been asked for the weights"""
     res = ExtensionResult()
     res.k1 = k1
-    res.iterations = ext.iterations
-    res.n_walks = ext.n_walks
-    res.total_steps = ext.total_steps
-    res.wave_steps = ext.wave_steps
-    res.fresh_steps = ext.fresh_steps
-    res.dense_rounds = ext.dense_rounds
+    for name in Extension.COUNTERS:
+        setattr(res, name, getattr(ext, name))
     res.ext_digests = ext.digests()                     # (SHN_EXT_DIGEST=1: bench.py names the stage at which a step differed)
-    res.contigs = contigs[1:]
+    res.contigs = contigs
     res.contig_raw = contig_raw
     # allowed k1-mers with their integer weights (:366-369, :404-408): GPU table lookup
     allowed = {}
@@ -821,34 +844,71 @@ def run_correction(ctx, table, min_weight=3, min_length=75, comp_size_threshold=
         keys = np.unique(keys)
         res.k1mer_keys, res.k1mer_weights = keys, ext.weights(keys)
     ext.close()
-
-    # DFS components (:417-434, native: shn_contig_components) and file products (:458-513)
-    coff_a = np.asarray(csr[0], dtype=np.uint64)
-    cnb_a = np.asarray(csr[1], dtype=np.int32)
-    cw_a = np.asarray(csr[2], dtype=np.int32)
-    _comp_of, members, comp_off, comp_edges = contig_components(coff_a, cnb_a)
-    res.conn_off, res.conn_nb, res.conn_w = coff_a.tolist(), cnb_a.tolist(), cw_a.tolist()
-    res.comp_members, res.comp_off = members.tolist(), comp_off.tolist()
-    mem, co = res.comp_members, res.comp_off
-    sizes = np.diff(comp_off.astype(np.int64)) if len(comp_off) > 1 else np.zeros(0, np.int64)
-    res.single_contigs, res.big_components, res.remaining = [], [], [[]]
-    res.single_ids = []                               # index in res.contigs of every single contig
-    cur_size = 0
-    for j, sz in enumerate(sizes.tolist()):
-        if sz == 1:
-            res.single_contigs.append(contigs[mem[co[j]]])
-            res.single_ids.append(mem[co[j]] - 1)
-        elif sz > comp_size_threshold:
-            mm = mem[co[j]:co[j + 1]]
-            res.big_components.append(([contigs[c] for c in mm], metis_text(mm, int(comp_edges[j]), coff_a, cnb_a, cw_a)))
-        else:
-            res.remaining[-1].extend(contigs[c] for c in mem[co[j]:co[j + 1]])
-            cur_size += sz
-            if cur_size > comp_size_threshold:
-                res.remaining.append([])
-                cur_size = 0
+    bin_components(contigs, csr[0], csr[1], csr[2], comp_size_threshold, res)
     lap("ext.components")
     return res
+
+
+def run_correction(ctx, table, min_weight=3, min_length=75, comp_size_threshold=500, r=15, f=0.5, want_allowed=True, timings=None,
+                   shard=None, merge=None, gather=None, table_size=None, want_weight_arrays=False):
+    """extension_correction.run_correction (extension_correction.py:309-524) on a device k1-mer
+    table.  Returns an ExtensionResult: contigs, allowed {k1mer: int}, connections, components,
+    single_contigs, big_components [(contigs, metis_text)], remaining [[contig...]].
+    shard = (world, rank) + merge(local) -> global: the walks are sharded by connected component; `merge` receives this
+    rank's candidates [(seed weight, seed key, contig)] and returns the candidates of all ranks (any order).
+    gather (instead of merge): an object with .world, .rank, .all_gather(obj) -> [obj per rank], .all_reduce_max(int): the
+    contig stages are sharded as well -- every rank decides its own candidates, a GPU r-mer join against the other shards'
+    accepted contigs proves that none of them could have changed a duplicate_check decision (foreign_interference), else all
+    ranks fall back to the global sequential pass.
+    want_weight_arrays (--inDisk): res.k1mer_keys / res.k1mer_weights = the distinct k1-mers of the contigs (packed, ascending) and
+    their weights -- what `allowed` holds, as two arrays from one shn_ext_weights call, without a dictionary entry per window.
+    table_size: the number of k1-mers of the JOB when `table` is this rank's share of it already (whole components: shard = None
+    with a gather) -- the choice between the contig stages must be the same on every rank."""
+    T = timings if timings is not None else {}
+    lap = _lap_timer(T)
+    k1 = table.k
+    par = (k1, min_length, min_weight, r, f)
+    plan = contig_plan(len(table) if table_size is None else int(table_size), 1 if gather is None else gather.world, merge is not None)
+    pipelined = plan == BESIDE or (plan == SHARDED_GUARDED and os.environ.get("SHN_EXT_PIPELINE", "1") != "0")
+    beside = _BesideWalks(k1, r, f, min_length, min_weight) if pipelined else None
+    ext = None
+    swi = sys.getswitchinterval()
+    try:
+        try:
+            if beside is not None:
+                # the call-back needs the interpreter lock while the worker may hold it between its native calls: hand it over
+                # quickly (the default switch interval of 5 ms would stall the walk loop once per block)
+                sys.setswitchinterval(2e-4)
+            ext = Extension(ctx, table, min_weight, shard=shard, on_block=beside.on_block if beside is not None else None)
+        finally:
+            sys.setswitchinterval(swi)
+        lap("ext.gpu_walks")
+        if beside is not None:
+            T["ext.gpu_walks"] -= beside.cb_seconds
+            T["ext.filter+emit (inside the walks)"] = T.get("ext.filter+emit (inside the walks)", 0.0) + beside.cb_seconds
+            beside.finish()
+        held = beside if beside is not None and not beside.void else None      # the hand-over, where there is one and it counts
+        if plan == MERGED:
+            out = _contigs_merged(ext, merge, *par, lap)
+        elif plan == DEVICE:
+            out = _contigs_device(ctx, ext, *par, lap)
+        elif plan == SHARDED_DEVICE:
+            out = _contigs_sharded_device(ctx, ext, gather, *par, lap)
+        elif plan == SHARDED_GUARDED:
+            out = _contigs_sharded_guarded(ctx, ext, held, gather, *par, lap)
+        elif held is not None:
+            out = _contigs_beside(held, lap)
+        else:
+            out = _contigs_after(ext, *par, lap)
+        if held is not None:
+            T["ext.contig_graph (beside the walks)"] = T.get("ext.contig_graph (beside the walks)", 0.0) + held.busy
+        lap("ext.contig_graph")
+        return _finish_result(ext, *out, k1, comp_size_threshold, want_allowed, want_weight_arrays, lap)
+    finally:                                           # on every way out: worker joined, its graph and the walk state released
+        if beside is not None:
+            beside.close()
+        if ext is not None:
+            ext.close()
 
 
 def write_outputs(res, directory, outfile=None):

@@ -1,5 +1,6 @@
 """GPU parity: contig extension (rows a3-a7) -- HIP walk fixpoint + host bookkeeping vs the
 oracle and the reference's golden vectors."""
+import copy
 import numpy as np
 import pytest
 from golden_util import *
@@ -195,7 +196,7 @@ def _run_virtual_ranks(world, run):
                 if k < len(history):
                     assert history[k][0] == kind
                     return history[k][1]
-                pending[rank] = (kind, obj)
+                pending[rank] = (kind, copy.deepcopy(obj))     # as sent: a rank may hand in views of buffers it uses again
                 raise _Abort()
             g.all_gather = lambda obj, c=collective: c("gather", obj)
             g.all_reduce_max = lambda v, c=collective: c("max", v)
@@ -425,6 +426,59 @@ def test_gpu_contig_stage_on_many_genes(ctx):
     assert [list(v) for v in got.connections.values()] == [list(v) for v in ref.connections.values()]
     assert got.components == ref.components and got.single_contigs == ref.single_contigs
     assert got.remaining == ref.remaining and got.big_components == ref.big_components and got.allowed == ref.allowed
+
+
+@pytest.fixture(scope="module")
+def plan_case(ctx):
+    """(table, reference) for the device plans: 20 genes, and the plain run_correction with the contig stage on the host"""
+    from shannon_amd import device, synth, extension_correction as ec
+    import os
+    (r1, r2), _ = synth.make_dataset(60000, 20, seed=80)
+    t = device.count_k1mers(ctx, [device.Reads.from_codes(ctx, np.concatenate([r1, r2]))], 26)
+    os.environ["SHN_CONTIG_GPU"] = "0"
+    try:
+        ref = ec.run_correction(ctx, t, 3, 75, 500, want_allowed=False)
+    finally:
+        del os.environ["SHN_CONTIG_GPU"]
+    assert len(ref.contigs) > 20 and ref.contig_raw is None
+    yield t, ref
+    t.close()
+
+
+def _assert_same_contig_stage(got, ref):
+    assert got.contigs == ref.contigs
+    assert got.connections == ref.connections and [list(v) for v in got.connections.values()] == [list(v) for v in ref.connections.values()]
+    assert got.components == ref.components
+    assert got.single_contigs == ref.single_contigs and got.remaining == ref.remaining
+
+
+@pytest.mark.parametrize("host_form", [None, "SHN_EXT_ACCEPT_DEVICE", "SHN_EXT_EMIT_DEVICE"])
+def test_device_plan_and_its_host_forms_equal_the_host_stage(ctx, plan_case, host_form, monkeypatch):
+    """SHN_CONTIG_GPU=1 on one rank (accept filter, emit and contig stage on the device), and with the accept filter or the candidates'
+    text on the host instead: the result of the host's contig stage, and contig_raw beside it"""
+    from shannon_amd import extension_correction as ec
+    t, ref = plan_case
+    monkeypatch.setenv("SHN_CONTIG_GPU", "1")
+    if host_form is not None:
+        monkeypatch.setenv(host_form, "0")
+    got = ec.run_correction(ctx, t, 3, 75, 500, want_allowed=False)
+    _assert_same_contig_stage(got, ref)
+    assert got.contig_raw is not None
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_sharded_device_plan_on_virtual_ranks_equals_the_host_stage(ctx, plan_case, world, monkeypatch):
+    """SHN_CONTIG_GPU=1 on several ranks: sharded walks, ONE gather of the candidates, the replicated contig stage on the device --
+    every rank ends with the result of the unsharded run"""
+    from shannon_amd import extension_correction as ec
+    t, ref = plan_case
+    monkeypatch.setenv("SHN_CONTIG_GPU", "1")
+    results, history = _run_virtual_ranks(world, lambda rank, g: ec.run_correction(ctx, t, 3, 75, 500, want_allowed=False,
+                                                                                   shard=(world, rank), gather=g))
+    assert len(history) == 1 and history[0][0] == "gather" and len(history[0][1]) == world
+    for rank in range(world):
+        _assert_same_contig_stage(results[rank], ref)
+        assert results[rank].contig_raw is not None
 
 
 @pytest.mark.parametrize("env", [{"SHN_EXT_BULK": "1"}, {"SHN_EXT_BULK": "1", "SHN_EXT_DENSE": "1"}, {"SHN_EXT_BULK": "1", "SHN_EXT_DENSE": "1000000000"},

@@ -73,6 +73,49 @@ def test_product_sparse_flow_host_logic(name, monkeypatch):
                 assert abs(float(t1[1]) - float(t2[1])) <= 1e-9 * max(1.0, abs(float(t1[1])))
 
 
+_ORACLE_WALKS = {}
+
+
+def _oracle_walks(name):
+    """(k1-mer items, the seed loop's walks) of a golden case: walked once, shared by the thresholds"""
+    if name not in _ORACLE_WALKS:
+        dbl = read_files(name, load_inputs(name))
+        tab = count.count_k1mers_dict([r for f in dbl for r in f], load_case(name)["K"] + 1)
+        items = [(k, tab[k]) for k in sorted(tab, reverse=True)]
+        kmers, k1 = extension.load_kmers(items)
+        _ORACLE_WALKS[name] = (items, list(extension.python_walks(kmers, k1, 3)))
+    return _ORACLE_WALKS[name]
+
+
+# (case, threshold) -> (contigs per remaining bin, big components): the bin roll-over, the trailing empty bin and the METIS text
+_BINS_PINNED = {("se_K24", 3): ([4, 4, 4, 0], 0), ("syn_pe_L250_K20_part1", 3): ([4, 2], 1), ("se_K24", 1): (None, 6)}
+
+
+@pytest.mark.parametrize("threshold", [500, 3, 1])
+@pytest.mark.parametrize("name", ["se_K24", "syn_part_s33", "syn_pe_L250_K20_part1"])
+def test_bin_components_against_the_oracle(name, threshold):
+    """extension_correction.bin_components (native DFS components, bins, METIS text) over the oracle's contigs and connections ==
+    the oracle's components, single contigs, remaining bins and big components (extension_correction.py:417-513)"""
+    from shannon_amd import extension_correction as ec
+    items, walks = _oracle_walks(name)
+    ref = extension.run_correction(items, comp_size_threshold=threshold, walks=walks)
+    assert list(ref.connections) == list(range(1, len(ref.contigs) + 1))
+    coff, cnb, cw = [0], [], []                              # the connections dict as CSR, in insertion order
+    for a in ref.connections:
+        cnb += list(ref.connections[a].keys())
+        cw += list(ref.connections[a].values())
+        coff.append(len(cnb))
+    if (name, threshold) in _BINS_PINNED:
+        bins, n_big = _BINS_PINNED[(name, threshold)]
+        assert len(ref.big_components) == n_big and (bins is None or [len(b) for b in ref.remaining] == bins)
+    got = ec.bin_components(ref.contigs, coff, cnb, cw, threshold)
+    assert got.components == ref.components and list(got.components) == list(ref.components)
+    assert got.connections == ref.connections and [list(v) for v in got.connections.values()] == [list(v) for v in ref.connections.values()]
+    assert got.single_contigs == ref.single_contigs and [ref.contigs[i] for i in got.single_ids] == ref.single_contigs
+    assert got.remaining == ref.remaining
+    assert got.big_components == ref.big_components
+
+
 def test_own_partitioner_is_balanced_and_deterministic():
     rng = np.random.default_rng(0)
     n = 300

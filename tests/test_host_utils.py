@@ -213,6 +213,30 @@ def test_metis_text_of_a_component_equals_the_line_by_line_form():
         assert ec.metis_text(mm, 13, coff, cnb, cw) == want
 
 
+def test_contig_plan_truth_table():
+    """extension_correction.contig_plan over every combination of its inputs against the table written out here: which of the six
+    ways of running the contig stage a call of run_correction takes.  A table with a merge is all MERGED; "big" is
+    SHN_CONTIG_GPU == "1", or not "0" and at least 20,000,000 k1-mers."""
+    from shannon_amd import extension_correction as ec
+    D, SD, SG = ec.DEVICE, ec.SHARDED_DEVICE, ec.SHARDED_GUARDED
+    P = "BESIDE unless SHN_EXT_PIPELINE is 0, then AFTER"
+    # (world, k1-mers): the plan without a merge for SHN_CONTIG_GPU unset / "0" / "1"
+    table = {(1, 0): (P, P, D), (1, 19_999_999): (P, P, D), (1, 20_000_000): (D, P, D),
+             (2, 0): (SG, SG, SD), (2, 19_999_999): (SG, SG, SD), (2, 20_000_000): (SD, SG, SD)}
+    assert len({ec.MERGED, ec.DEVICE, ec.SHARDED_DEVICE, ec.SHARDED_GUARDED, ec.BESIDE, ec.AFTER}) == 6
+    seen = set()
+    for (world, n), row in table.items():
+        for cg, cell in zip((None, "0", "1"), row):
+            for pl in (None, "0", "1"):
+                env = {k: v for k, v in (("SHN_CONTIG_GPU", cg), ("SHN_EXT_PIPELINE", pl)) if v is not None}
+                want = cell if cell is not P else (ec.AFTER if pl == "0" else ec.BESIDE)
+                assert ec.contig_plan(n, world, False, env) == want, (world, n, env)
+                assert ec.contig_plan(n, world, True, env) == ec.MERGED, (world, n, env)
+                assert env == {k: v for k, v in (("SHN_CONTIG_GPU", cg), ("SHN_EXT_PIPELINE", pl)) if v is not None}
+                seen.add(want)
+    assert seen == {ec.DEVICE, ec.SHARDED_DEVICE, ec.SHARDED_GUARDED, ec.BESIDE, ec.AFTER}
+
+
 def test_partitions_contig_lists_by_one_sort_equal_the_loop():
     """kmers_for_component._contigs_by_part == the reference's loop (kmers_for_component.py:239-262): the same lists under the
     same names IN THE SAME ORDER of first appearance (the partition order decides the order of all_reconstructed.fasta)"""
